@@ -6,7 +6,14 @@ libjodo_hip.so) plus the ancestral update of the reference's sampler, inputs res
 `value` = molecules/s of a full 1000-step sampling round = (B * n_gpus) / (1000 * step_time);
 per-step cost is independent of the step index, so K timed steps measure it directly.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload qm9|geom|geom384|cond]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload qm9|geom|geom384|cond] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up (W steps), times K steps and prints the JSON line: the headline (`value`, `ms_per_step`) and the
+roofline figures derived from the same timed steps.  Every other leg listed below (HIP-graph replay, steady state, split-bf16,
+decode, complete rounds, scaling prediction, CPU baseline) runs only with --full; without it their keys are null or absent.
+--dump-outputs DIR writes the sampler state after the last timed step (x, edge_x, x_mean, edge_x_mean of rank 0) as float32
+DIR/<name>.npy, at most 64 MB in all: a larger batch is cut to a fixed, seeded sample of molecules.  The inputs (atom counts,
+initial noise, weights, in-kernel noise) depend only on the arguments, so two builds can be compared output for output.
 
 N > 1: one process per GPU.  `python bench.py --gpus N` launches the ranks itself (it re-executes under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`); started by a launcher
@@ -66,6 +73,31 @@ WORKLOADS = {
 }
 PEAK_FP32_MFMA = 157.3e12      # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 dense peak
 SAMPLING_STEPS = 1000
+DUMP_BYTES = 60_000_000         # --dump-outputs payload cap (64 MB with headers and margin)
+DUMP_KEYS = ('x', 'edge_x', 'x_mean', 'edge_x_mean')
+
+
+def step_index(i):
+    """Schedule index of the i-th step of the run.  Past the end of the 1000-step round the run goes on from index 2 (0 is the
+    round's first evaluation, 1 pins the kernel paths), so warm-up + timed steps may exceed one round: a step's cost does not
+    depend on its index."""
+    return i if i < SAMPLING_STEPS else 2 + (i - 2) % (SAMPLING_STEPS - 2)
+
+
+def dump_outputs(out_dir, st):
+    """The arrays of the sampler state `st` (DUMP_KEYS, batch first) as float32 out_dir/<name>.npy.  Over DUMP_BYTES in all, every
+    array keeps the same fixed, seeded sample of molecules (sorted batch indices)."""
+    import numpy as np
+    arrs = {k: st[k].detach().float().cpu() for k in DUMP_KEYS if torch.is_tensor(st.get(k))}
+    B = next(iter(arrs.values())).shape[0]
+    per_mol = sum(a[0].numel() * 4 for a in arrs.values())
+    if per_mol * B > DUMP_BYTES:
+        keep = max(1, DUMP_BYTES // per_mol)
+        idx = torch.randperm(B, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        arrs = {k: a[idx] for k, a in arrs.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, k + '.npy'), a.numpy())
 
 
 def reference_formulation_flops(d, n_nodes, shared_time):
@@ -289,7 +321,14 @@ def main():
     ap.add_argument('--breakdown', action='store_true',
                     help='time every kernel class with HIP events (costs ~0.5 ms/step of event packets; default: only the '
                          'dominant pair-update class, which the roofline object needs) and print the table to stderr')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the legs beside the headline (graph replay, steady state, split-bf16, decode, complete rounds, '
+                         'scaling prediction, CPU baseline); the --no-* options above still skip single legs')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the sampler state after the last timed step as float32 DIR/<name>.npy (at most 64 MB in all)')
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N`: become the launcher — one process per GPU over RCCL (same command line per rank)
@@ -371,6 +410,8 @@ def main():
         # eager step 0 + warm-up step, capture, then untimed / timed replays (per-class HIP-event profiling is not
         # available inside a captured graph: the roofline leg needs the default eager mode)
         from jodo_amd.graphed import GraphedAncestralRound
+        if 2 + max(args.warmup - 2, 0) + args.steps > SAMPLING_STEPS:
+            raise SystemExit("--graph replays one %d-step round: --warmup + --steps must not exceed it" % SAMPLING_STEPS)
         with torch.no_grad():
             rnd = GraphedAncestralRound(sampler, model, node_mask, edge_mask, context)
             rnd.prepare(z, edge_z)
@@ -388,12 +429,12 @@ def main():
                 dist.barrier()
             torch.cuda.synchronize()
             elapsed = time.perf_counter() - t0
-        st = dict(x_mean=rnd.x_mean, edge_x_mean=rnd.e_mean)
+        st = dict(x=rnd.x, edge_x=rnd.e, x_mean=rnd.x_mean, edge_x_mean=rnd.e_mean)
     else:
         with torch.no_grad():
             st = sampler.init_state(z, edge_z)
             for i in range(args.warmup):
-                st = sampler.step(model, i, st, node_mask, edge_mask, context)
+                st = sampler.step(model, step_index(i), st, node_mask, edge_mask, context)
                 if i == 0 and args.warmup > 1:
                     model.profile_enable(1)            # class timers on every launch class for the rest of the warm-up
             # roofline leg: the timed region brackets the dominant KERNEL — the single dispatch that took the most time in the
@@ -414,12 +455,15 @@ def main():
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for i in range(args.warmup, args.warmup + args.steps):
-                st = sampler.step(model, i, st, node_mask, edge_mask, context)
+                st = sampler.step(model, step_index(i), st, node_mask, edge_mask, context)
             torch.cuda.synchronize()
             if use_dist:
                 dist.barrier()
             torch.cuda.synchronize()
             elapsed = time.perf_counter() - t0
+    # what the last timed step computed, before any leg below advances the state
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, st)
     # HIP-event timings of exactly the timed region above
     ms, cnt = model.profile_read()
     model.profile_enable(0)
@@ -427,7 +471,7 @@ def main():
     work = model.work_model()
     n_sub = len(model._last_plans)                  # sub-batches evaluated concurrently (--streams)
     graph_info = None
-    if not args.graph and world == 1:
+    if args.full and not args.graph and world == 1:
         # extra, reported beside the headline: the same step replayed as ONE captured HIP graph (no per-step
         # Python / launch overhead).  The headline stays the eager loop, whose kernels carry the HIP-event brackets
         # the roofline leg needs.
@@ -450,12 +494,12 @@ def main():
             graph_info = {'error': repr(exc)}
     # ---- >= 100 steady-state steps when the timed region above was shorter -----------------------
     steady = None
-    if not args.graph and world == 1 and args.steps < 100:
+    if args.full and not args.graph and world == 1 and args.steps < 100:
         with torch.no_grad():
             torch.cuda.synchronize()
             ts0 = time.perf_counter()
             for i in range(args.warmup + args.steps, args.warmup + args.steps + 100):
-                st = sampler.step(model, i, st, node_mask, edge_mask, context)
+                st = sampler.step(model, step_index(i), st, node_mask, edge_mask, context)
             torch.cuda.synchronize()
             steady = {'steps': 100, 'ms_per_step': (time.perf_counter() - ts0) * 10.0}
         steady['value'] = B / (SAMPLING_STEPS * steady['ms_per_step'] * 1e-3)
@@ -464,7 +508,7 @@ def main():
     # and every roofline figure are the exact-fp32 default.  nf 256 unconditional workloads only; 50 steps with the pair-update class
     # bracketed.  Parity of this path: tests/test_split_gate.py (same stated tolerance / K64 as the default).
     split_info = None
-    if not args.graph and world == 1 and dims.D in (256, 384) and not dims.cond_ch and not args.no_pin and not args.no_split_leg:
+    if args.full and not args.graph and world == 1 and dims.D in (256, 384) and not dims.cond_ch and not args.no_pin and not args.no_split_leg:
         try:
             with torch.no_grad():
                 model.unpin_paths()
@@ -472,12 +516,12 @@ def main():
                 model.pin_paths()                          # (re-pins the last call's plan; hands the weight tape over)
                 i0 = args.warmup + args.steps + (100 if steady is not None else 0)
                 for i in range(i0, i0 + 3):
-                    st = sampler.step(model, i, st, node_mask, edge_mask, context)
+                    st = sampler.step(model, step_index(i), st, node_mask, edge_mask, context)
                 model.profile_enable(16 + 6)
                 torch.cuda.synchronize()
                 tsp = time.perf_counter()
                 for i in range(i0 + 3, i0 + 53):
-                    st = sampler.step(model, i, st, node_mask, edge_mask, context)
+                    st = sampler.step(model, step_index(i), st, node_mask, edge_mask, context)
                 torch.cuda.synchronize()
                 tsp = (time.perf_counter() - tsp) / 50
                 sms, scnt = model.profile_read()
@@ -499,15 +543,17 @@ def main():
     step_s = elapsed / args.steps
 
     # not timed: finish the round's host side once so the whole path is exercised (device decode)
-    with torch.no_grad():
-        pos, at, fc, et = fused.decode(cfg, st['x_mean'], st['edge_x_mean'], fused.n_nodes_from_mask(node_mask))
-    n_total = len(fused.mols_from_decoded(pos, at, fc, et, n_nodes))
+    n_total = None
+    if args.full:
+        with torch.no_grad():
+            pos, at, fc, et = fused.decode(cfg, st['x_mean'], st['edge_x_mean'], fused.n_nodes_from_mask(node_mask))
+        n_total = len(fused.mols_from_decoded(pos, at, fc, et, n_nodes))
     nan_fired = model.nan_guard_fired()
 
     # ---- one complete round through the public entry points, wall clock ---------------------------------------------
     prop = _SyntheticContext(dims.cond_ch) if dims.cond_ch else None
     full_round = None
-    if world == 1 and not args.no_full_round and (args.workload == 'qm9' or args.full_round):
+    if args.full and world == 1 and not args.no_full_round and (args.workload == 'qm9' or args.full_round):
         full_round = {}
         # (under a launcher the sharded round below is the third complete round: leave the torch.randn variant out there)
         for mode, hg, dn in (('eager', False, not args.torch_noise), ('eager_torch_randn', False, False))[:1 if use_dist else 2]:
@@ -533,7 +579,7 @@ def main():
                               % int(cfg.sampling.steps))
     # ---- BASELINE configs[4]'s own metric: one complete round of the hybrid DPM-solver at 50 NFE (conditional workload only) --------------
     dpm_round = None
-    if world == 1 and dims.cond_ch and not args.no_full_round:
+    if args.full and world == 1 and dims.cond_ch and not args.no_full_round:
         try:
             import copy
             cfg2 = copy.deepcopy(cfg)
@@ -558,7 +604,7 @@ def main():
             dpm_round = {'error': repr(exc)}
     # ---- under a launcher (any N): one complete SHARDED round + the RCCL gather of the generated molecules --------------------------------
     sharded = None
-    if use_dist and not args.no_full_round:
+    if args.full and use_dist and not args.no_full_round:
         from jodo_amd.dist import gather_sampled
         try:
             fn = get_sampling_fn(cfg, ns, nodes_dist, B, B * world, get_data_inverse_scaler(cfg), prop_dist=prop, return_raw=True,
@@ -641,7 +687,7 @@ def main():
         # multi-GPU balance predicted on the host (jodo_amd/scaling.py): rank r of `bench.py --gpus N` draws its own B
         # molecules from seed + r — executed-work model per rank, mean / max = the efficiency the n^2 variance of the draws allows
         scaling_pred = None
-        if world == 1:
+        if args.full and world == 1:
             try:
                 from jodo_amd import scaling
                 fr = {k_: v_['mfma_frac'] for k_, v_ in (classes or {}).items() if v_.get('mfma_frac')}
@@ -720,7 +766,7 @@ def main():
         }
         if args.breakdown:
             print(json.dumps(per_class), file=sys.stderr)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(cfg.seed, config2_steps=args.cpu_config2_steps)
         os.write(json_fd, (json.dumps(out) + '\n').encode())
     if use_dist:

@@ -29,6 +29,8 @@ cond_DGT_concat with `jodo_amd.models.init_utils.deterministic_init_` (weights a
   traj_cond_dpm_multi8.npz / _single3.npz / _single1.npz
                                                hybrid DPM-solver: 2nd-order multistep (8 NFE), single-step order 3
                                                (6 NFE) and order 1 (3 NFE)
+  ckpt_ref_qm9.pth.xz                          a checkpoint file written by the reference's utils.save_checkpoint (QM9 model,
+                                               EMA, Adam state, step), xz-compressed; patterned weights keep it small
 
 While doing so it asserts the oracle restatement (oracle/dgt_oracle.py) against the reference:
 faithful == reference bit-for-bit, dense within 1e-5.
@@ -501,6 +503,36 @@ def cfg0_fixture(ref, fname, batch=64, steps=50, seed=42, model_seed=42):
           'atom types', np.unique(rec['one_hot'].argmax(2).numpy()), 'bond types', np.unique(rec['et'].numpy()))
 
 
+def checkpoint_fixture(ref, fname, step=123):
+    """A checkpoint file written by the reference's own utils.save_checkpoint (DataParallel `module.` keys, the reference's EMA
+    state, an Adam state_dict, the step), xz-compressed byte for byte.  Every parameter is an offset of its own plus a ramp of
+    period 251, so the 27.5 M-parameter QM9 model (220 MB on disk) compresses to about 90 kB while a swapped, misnamed or transposed tensor is still
+    detected."""
+    import importlib
+    import lzma
+    import tempfile
+    rcfg = reference_config('vpsde_qm9_uncond_jodo')
+    rcfg.device = torch.device('cpu')
+    ref.models                                               # puts the stand-ins and the reference on sys.path
+    rutils = importlib.import_module('utils')                # the reference's top-level utils.py
+    rmodel = importlib.import_module('models.utils').create_model(rcfg)
+    with torch.no_grad():
+        for i, p in enumerate(rmodel.parameters()):
+            p.copy_(((i + 1) / 1024.0 + (torch.arange(p.numel()) % 251) / 65536.0).reshape(p.shape))
+    rema = importlib.import_module('models.ema').ExponentialMovingAverage(rmodel.parameters(), decay=0.999)
+    with torch.no_grad():
+        for p in rmodel.parameters():
+            p.add_(0.01)
+    rema.update(rmodel.parameters())
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, 'checkpoint_ref.pth')
+        rutils.save_checkpoint(path, dict(optimizer=torch.optim.Adam(rmodel.parameters()), model=rmodel, ema=rema, step=step))
+        raw = open(path, 'rb').read()
+    with open(os.path.join(OUT, fname), 'wb') as f:
+        f.write(lzma.compress(raw, preset=9 | lzma.PRESET_EXTREME))
+    print(fname, 'ok;', len(raw), 'bytes raw,', os.path.getsize(os.path.join(OUT, fname)), 'compressed')
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     ref = load_reference()
@@ -528,6 +560,7 @@ def main():
         ('cond_eval.npz', lambda f: cond_eval_fixture(ref, f)),
         # BASELINE configs[0] at its own size (batch 64, 50 steps) through the reference's get_sampling_fn
         ('traj_qm9_cfg0.npz', lambda f: cfg0_fixture(ref, f)),
+        ('ckpt_ref_qm9.pth.xz', lambda f: checkpoint_fixture(ref, f)),
     ]
     want = sys.argv[1:]
     for fname, job in jobs:

@@ -1,6 +1,5 @@
 """Checkpoint ingestion: reference-format files (utils.py:7-30, models/ema.py:79-85)."""
 import os
-import sys
 
 import pytest
 import torch
@@ -62,37 +61,36 @@ def test_round_trip_and_ema_overwrite(tmp_path):
         load_for_sampling(str(tmp_path / 'missing.pth'), cfg)
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference'), reason='reference tree only exists in the build container')
-def test_reference_written_checkpoint_loads_strict(tmp_path):
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    sys.path.insert(0, os.path.join(root, 'oracle'))
-    from ref_import import load_reference, reference_config
-    ref = load_reference()
-    rcfg = reference_config('vpsde_qm9_uncond_jodo')
-    rcfg.device = torch.device('cpu')
-    torch.manual_seed(11)
-    import importlib
-    ref.models                                               # puts the stand-ins and the reference on sys.path
-    rutils = importlib.import_module('utils')                # the reference's top-level utils.py
-    rmodel = importlib.import_module('models.utils').create_model(rcfg)
-    rema = importlib.import_module('models.ema').ExponentialMovingAverage(rmodel.parameters(), decay=0.999)
-    with torch.no_grad():
-        for p in rmodel.parameters():
-            p.add_(0.01)
-    rema.update(rmodel.parameters())
+def test_reference_written_checkpoint_loads_strict(tmp_path, golden_dir):
+    """tests/golden/ckpt_ref_qm9.pth.xz: the bytes the reference's utils.save_checkpoint wrote for its own create_model(QM9)
+    wrapper, EMA (one update) and Adam (oracle/make_golden.py checkpoint_fixture)."""
+    import lzma
     path = str(tmp_path / 'checkpoint_ref.pth')
-    rutils.save_checkpoint(
-        path, dict(optimizer=torch.optim.Adam(rmodel.parameters()), model=rmodel, ema=rema, step=123))
+    with lzma.open(os.path.join(golden_dir, 'ckpt_ref_qm9.pth.xz'), 'rb') as f, open(path, 'wb') as out:
+        out.write(f.read())
+    raw = torch.load(path)
+    ref_sd = raw['model']                                    # the reference wrapper's state_dict (`module.` keys)
+    assert all(k.startswith('module.') for k in ref_sd)
     model, ema, step = load_for_sampling(path, _cfg(), use_ema=False)
     assert step == 123
-    for (k, a), (k2, b) in zip(rmodel.state_dict().items(), model.state_dict().items()):
+    assert len(ref_sd) == len(model.state_dict())
+    for (k, a), (k2, b) in zip(ref_sd.items(), model.state_dict().items()):
         assert k == k2 and torch.equal(a, b), (k, k2)
     ema.copy_to(model.parameters())
-    for s, b in zip(rema.shadow_params, model.parameters()):
+    shadow = raw['ema']['shadow_params']
+    assert len(shadow) == len(list(model.parameters()))
+    for s, b in zip(shadow, model.parameters()):
         assert torch.equal(s, b)
-    # ... and a file written by this package restores into the reference with strict=True
+    # ... and a file written by this package restores the way the reference's utils.restore_checkpoint does it: the optimizer
+    # state into an Adam over the reference's parameters, the model state with strict=True, the EMA state, the step
     path2 = str(tmp_path / 'checkpoint_ours.pth')
     save_checkpoint(path2, dict(optimizer=torch.optim.Adam(model.parameters()), model=model, ema=ema, step=5))
-    rstate = dict(optimizer=torch.optim.Adam(rmodel.parameters()), model=rmodel, ema=rema, step=0)
-    rstate = rutils.restore_checkpoint(path2, rstate, torch.device('cpu'))
-    assert rstate['step'] == 5
+    ours = torch.load(path2)
+    ref_params = [torch.nn.Parameter(v.clone()) for v in ref_sd.values()]        # the reference model has no buffers
+    torch.optim.Adam(ref_params).load_state_dict(ours['optimizer'])
+    assert list(ours['model']) == list(ref_sd)                                    # load_state_dict(strict=True): same keys ...
+    for k, v in ours['model'].items():
+        assert v.shape == ref_sd[k].shape, k                                      # ... and shapes
+    assert set(ours['ema']) == set(raw['ema'])
+    assert [s.shape for s in ours['ema']['shadow_params']] == [s.shape for s in shadow]
+    assert ours['step'] == 5

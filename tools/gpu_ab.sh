@@ -5,7 +5,7 @@ OUT=gpurun_out/ab; mkdir -p $OUT
 for rep in 1 2; do
 for opts in "$@"; do
   args=""; if [ "$opts" != "-" ]; then for o in $opts; do args="$args --plan-opt $o"; done; fi
-  timeout 600 python bench.py --workload $W --steps 40 --warmup 5 --no-cpu-baseline --no-full-round $args > $OUT/last.json 2> $OUT/last.err
+  timeout 600 python bench.py --workload $W --steps 40 --warmup 5 --full --no-cpu-baseline --no-full-round $args > $OUT/last.json 2> $OUT/last.err
   python - <<PY
 import json
 d = json.load(open("$OUT/last.json")); c = d['roofline']['classes']

@@ -58,7 +58,7 @@ def main():
     ap.add_argument('--stats')
     ap.add_argument('--bench', required=True)
     ap.add_argument('--out', required=True)
-    ap.add_argument('--command', default='python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-full-round')
+    ap.add_argument('--command', default='python bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-full-round')
     a = ap.parse_args()
     bench = json.loads([l for l in open(a.bench) if l.startswith('{')][-1])
     cfg = bench['config']
