@@ -160,8 +160,9 @@ class _DGTBase(nn.Module):
 
         # ---- runtime state (not part of state_dict) ----
         self._packed = None           # (version_key, blob_dev, woff_host ctypes array)
+        self._pack_gen = 0            # pack generation: +1 on every re-pack of the blob (the split tape and the plans' tapes key on it)
         self._plans = {}              # plan cache keyed by the mask storage (address, shape, version), see _plan
-        self._splits = {}             # sub-batch splits of n_streams > 1, keyed likewise
+        self._splits = {}             # sub-batch splits of n_streams > 1, keyed likewise (node and edge mask storage, k), see _split_of
         self.n_streams = 1            # > 1: sub-batches evaluated concurrently on that many HIP streams (_forward_split)
         self._cfg_struct = None
         self.register_load_state_dict_post_hook(_drop_packed_after_load)
@@ -173,7 +174,7 @@ class _DGTBase(nn.Module):
         # JODO_OPT_SPLIT_BF16).  nf 256 (pair update + node kernel) and nf 384 (pair update) unconditional models; ignored elsewhere.  The default path and every headline number
         # stay exact fp32.
         self.split_bf16 = False       # True: pair update + node kernel; 'attention': also the attention kernel (experiments: measured slower)
-        self._split_tape = None       # (weights key, device uint8 tensor): the split form's static weight tape
+        self._split_tape = None       # (pack generation, device uint8 tensor): the split form's static weight tape
 
     # -- C structs ---------------------------------------------------------------------------
     class _Cfg(ctypes.Structure):
@@ -200,6 +201,9 @@ class _DGTBase(nn.Module):
             # C-side packer (csrc/dgt_pack.cpp, jodo_dgt_pack_weights): the state_dict goes through the C ABI as named
             # fp32 tensors; tests/py_packing_model.py is an independent Python packer kept for tests (blob equality)
             blob_dev, woff_c, n_woff = capi.pack_weights(self._cfg(), self.state_dict(), device)
+            # a `.data` write re-packs under the SAME key (versions and addresses unchanged): what follows the blob — the split tape and
+            # the tape handed to each pinned plan — compares this generation, not the key
+            self._pack_gen += 1
             self._packed = (key, blob_dev, woff_c, n_woff)
             self._packed_fingerprint = self._fingerprint()
         return self._packed
@@ -214,6 +218,7 @@ class _DGTBase(nn.Module):
     def _recheck_weights(self):
         if self._packed is not None and self._fingerprint() != getattr(self, '_packed_fingerprint', None):
             self._packed = None
+            self._split_tape = None
 
     # -- plans ---------------------------------------------------------------------------------
     def _plan(self, node_mask, edge_mask, device, validate=True):
@@ -316,9 +321,8 @@ class _DGTBase(nn.Module):
         # plan first: building a plan for a new batch re-checks the weight fingerprint (`.data` updates such as the
         # reference's EMA copy_to / restore) and drops a stale blob BEFORE this call fetches it
         plan = self._plan(node_mask, edge_mask, dev)
-        wkey, blob, woff_c, n_woff = self._weights(dev)
-        if plan.get('split_tape') is not None and plan.get('split_key') != wkey:
-            self._hand_over_split(plan)                          # the weights changed under a pinned plan: the split tape follows the blob
+        _, blob, woff_c, n_woff = self._weights(dev)
+        self._follow_weights([plan])
         out_x = torch.empty_like(xh_)
         out_e = torch.empty_like(ex_)
         self._launch(plan, blob, woff_c, n_woff, xh_, ex_, cx_, cex_, nl_, ctx_, out_x, out_e)
@@ -424,10 +428,14 @@ class _DGTBase(nn.Module):
     # -- stream-interleaved evaluation -----------------------------------------------------------
     def _split_of(self, node_mask, edge_mask, k):
         """Contiguous split of the batch into k sub-batches of about equal pair work (sum n^2), cached per mask tensor:
-        [(lo, hi, node_mask[lo:hi], edge_mask rows of lo..hi)] — the sub-mask tensors are kept so that their plans stay cached."""
-        key = (id(node_mask), id(edge_mask), k)
+        [(lo, hi, node_mask[lo:hi], edge_mask rows of lo..hi)] — the sub-mask tensors are kept so that their plans stay cached.
+        Keyed like _plan, by the masks' storage address, shape, stride and device (the single-device DataParallel wrap hands over a
+        fresh view of the same masks on every call) and checked against their version counters; the entry keeps both masks alive,
+        so their storage cannot be recycled for other masks while it is cached."""
+        key = (node_mask.data_ptr(), tuple(node_mask.shape), tuple(node_mask.stride()), str(node_mask.device),
+               edge_mask.data_ptr(), tuple(edge_mask.shape), tuple(edge_mask.stride()), k)
         ent = self._splits.get(key)
-        if ent is not None and ent[0] is node_mask and ent[1] == node_mask._version and ent[3] is edge_mask and ent[4] == edge_mask._version:
+        if ent is not None and ent[1] == node_mask._version and ent[4] == edge_mask._version:
             return ent[2]
         B, N = node_mask.shape[0], node_mask.shape[1]
         n = node_mask.reshape(B, N).sum(1).round().long().cpu()                 # one sync per new batch
@@ -439,6 +447,7 @@ class _DGTBase(nn.Module):
         cuts.append(B)
         em = edge_mask.reshape(B, N * N, -1)
         parts = [(lo, hi, node_mask[lo:hi], em[lo:hi].reshape((hi - lo) * N * N, -1)) for lo, hi in zip(cuts[:-1], cuts[1:])]
+        self._splits.pop(key, None)
         if len(self._splits) >= 4:
             self._splits.pop(next(iter(self._splits)))
         self._splits[key] = (node_mask, node_mask._version, parts, edge_mask, edge_mask._version)
@@ -457,6 +466,7 @@ class _DGTBase(nn.Module):
         parts = self._split_of(node_mask, edge_mask, k)
         plans = [self._plan(nm, em, dev) for _, _, nm, em in parts]
         _, blob, woff_c, n_woff = self._weights(dev)
+        self._follow_weights(plans)
         out_x = torch.empty_like(xh_)
         out_e = torch.empty_like(ex_)
         if getattr(self, '_side_streams', None) is None or len(self._side_streams) < k - 1:
@@ -519,18 +529,26 @@ class _DGTBase(nn.Module):
                 capi.check(L.jodo_plan_set_option(plan['handle'], 13, 2 if self.split_bf16 == 'attention' else 1), 'jodo_plan_set_option')
 
     def _hand_over_split(self, plan):
-        """The split-bf16 weight tape of the CURRENT parameters -> this plan (also called by forward when the packed blob was rebuilt
-        under a pinned plan: an optimiser step or load_state_dict between two calls on the same masks)."""
+        """The split-bf16 weight tape of the CURRENT parameters -> this plan."""
         tape = self._split_weights(plan['ws'].device)
         capi.check(capi.lib().jodo_plan_set_split_weights(plan['handle'], capi.ptr(tape), ctypes.c_size_t(tape.numel())), 'jodo_plan_set_split_weights')
         plan['split_tape'] = tape                             # keeps the device copy alive as long as the plan may use it
         plan['split_key'] = self._split_tape[0]
 
+    def _follow_weights(self, plans):
+        """Called by every forward after it fetched the packed blob: a pinned split plan whose tape predates the blob's last re-pack
+        (an optimiser step, load_state_dict, a `.data` write caught by the fingerprint or invalidate_packed_weights() between two
+        calls on the same masks) gets the current tape, so that no kernel of the call reads other weights than the rest."""
+        for plan in plans:
+            if plan.get('split_tape') is not None and plan.get('split_key') != self._pack_gen:
+                self._hand_over_split(plan)
+
     def _split_weights(self, device):
-        """Device copy of the split-bf16 weight tape of the current parameters (re-packed when the packed blob is)."""
-        key = self._weights(device)[0]
-        if self._split_tape is None or self._split_tape[0] != key:
-            self._split_tape = (key, capi.pack_split_tape(self._cfg(), self.state_dict(), device))
+        """Device copy of the split-bf16 weight tape of the current parameters (re-packed when the packed blob is: same generation)."""
+        self._weights(device)
+        gen = self._pack_gen
+        if self._split_tape is None or self._split_tape[0] != gen:
+            self._split_tape = (gen, capi.pack_split_tape(self._cfg(), self.state_dict(), device))
         return self._split_tape[1]
 
     def unpin_paths(self):
@@ -573,8 +591,9 @@ class _DGTBase(nn.Module):
     def invalidate_packed_weights(self):
         """Drop the packed kernel weights; the next forward re-packs from the current parameters.  Needed after
         in-place updates that do not bump tensor versions (`param.data.copy_(...)`, e.g. the reference's
-        ExponentialMovingAverage.copy_to / restore, models/ema.py:44-66)."""
+        ExponentialMovingAverage.copy_to / restore, models/ema.py:44-66).  The split tape goes with it."""
         self._packed = None
+        self._split_tape = None
 
     def nan_guard_fired(self):
         """Lazy read of the device NaN-guard flag of the last call (the reference prints a warning and
