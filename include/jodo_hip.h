@@ -353,7 +353,9 @@ size_t jodo_train_workspace_bytes(const jodo_train* t);
  *            below), 0 never, 2 always (tests) */
 int jodo_train_set_option(jodo_train* t, int option, int value);
 /* tests: byte offset and element count of a kept activation inside the workspace; what 0 = hhat [Nn, D] (TransMixLayer's output,
- * layers.py:153), 1 = alpha [R, H] (softmax weights, layers.py:178) of block `layer` */
+ * layers.py:153), 1 = alpha [R, H] (softmax weights, layers.py:178) of block `layer`; the FFNs (mol_gnn.py:263-268): 2 = f1
+ * [Nn, r D] (ff_linear1), 3 = a1 [Nn, r D] (SiLU(f1) x dropout), 4 = f2 [Nn, D] (ff_linear2, before its dropout), 5 = f3 [R, r De]
+ * (ff_linear3), 6 = a3 [R, r De] (SiLU(f3) x dropout), 7 = f4 [R, De] (ff_linear4, before its dropout) */
 int jodo_train_debug_locate(const jodo_train* t, int what, int layer, size_t* byte_offset, size_t* count);
 int jodo_train_upload(jodo_train* t, void* desc_dev, void* stream);
 /* the host image jodo_train_upload copies (jodo_train_desc_bytes() bytes, owned by the handle): callers that stage it through pinned

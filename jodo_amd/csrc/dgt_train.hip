@@ -1034,7 +1034,8 @@ int jodo_train_set_option(jodo_train* t, int option, int value) {
     return JODO_OK;
 }
 // tests: where a kept activation lives in the workspace.  what 0 = hhat (attention output [Nn, D]), 1 = alpha (softmax weights
-// [R, H]) of block `layer`
+// [R, H]) of block `layer`; the FFNs: 2 = f1 (ff_linear1 output [Nn, r D]), 3 = a1 (SiLU(f1) x dropout), 4 = f2 (ff_linear2 output
+// [Nn, D], before its dropout), 5 = f3 ([R, r De]), 6 = a3 (SiLU(f3) x dropout), 7 = f4 ([R, De], before its dropout)
 int jodo_train_debug_locate(const jodo_train* t, int what, int layer, size_t* byte_offset, size_t* count) {
     if (!t || !byte_offset || !count) return jodo_set_error(JODO_ERR_ARG, "jodo_train_debug_locate: null argument");
     if (layer < 0 || layer >= t->L) return jodo_set_error(JODO_ERR_ARG, "jodo_train_debug_locate: layer %d of %d", layer, t->L);
@@ -1045,6 +1046,12 @@ int jodo_train_debug_locate(const jodo_train* t, int what, int layer, size_t* by
     size_t n = 0;
     if (what == 0) { ptr = b.blk[layer].hhat; n = (size_t)t->Nn * t->D; }
     else if (what == 1) { ptr = b.blk[layer].alpha; n = (size_t)t->R * t->H; }
+    else if (what == 2) { ptr = b.blk[layer].f1; n = (size_t)t->Nn * t->r * t->D; }
+    else if (what == 3) { ptr = b.blk[layer].a1; n = (size_t)t->Nn * t->r * t->D; }
+    else if (what == 4) { ptr = b.blk[layer].f2; n = (size_t)t->Nn * t->D; }
+    else if (what == 5) { ptr = b.blk[layer].f3; n = (size_t)t->R * t->r * t->De; }
+    else if (what == 6) { ptr = b.blk[layer].a3; n = (size_t)t->R * t->r * t->De; }
+    else if (what == 7) { ptr = b.blk[layer].f4; n = (size_t)t->R * t->De; }
     else return jodo_set_error(JODO_ERR_ARG, "jodo_train_debug_locate: unknown selector %d", what);
     *byte_offset = (size_t)(reinterpret_cast<const char*>(ptr) - reinterpret_cast<const char*>(256));
     *count = n;

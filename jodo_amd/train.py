@@ -163,7 +163,9 @@ class TrainEngine:
         return None
 
     def debug_fetch(self, what, layer):
-        """tests: a kept activation of the last forward (jodo_train_debug_locate: 0 = hhat [Nn, D], 1 = alpha [R, H] of block `layer`)."""
+        """tests: a kept activation of the last forward (jodo_train_debug_locate) of block `layer`: 0 = hhat [Nn, D], 1 = alpha [R, H],
+        2 = f1 [Nn, r D], 3 = a1 = SiLU(f1) x dropout, 4 = f2 [Nn, D], 5 = f3 [R, r De], 6 = a3 = SiLU(f3) x dropout, 7 = f4 [R, De]
+        (f2, f4 before their dropout); flat float32."""
         off, cnt = ctypes.c_size_t(), ctypes.c_size_t()
         self.L.jodo_train_debug_locate.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
         self._check(self.L.jodo_train_debug_locate(self.handle, int(what), int(layer), ctypes.byref(off), ctypes.byref(cnt)), 'jodo_train_debug_locate')

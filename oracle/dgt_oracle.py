@@ -120,7 +120,9 @@ def time_embedding(p, hp, noise_level, context=None):
 # faithful sparse formulation
 # ----------------------------------------------------------------------------------------------
 def forward_faithful(p, hp, xh, node_mask, edge_mask, edge_x, cond_x=None, cond_edge_x=None,
-                     noise_level=None, context=None):
+                     noise_level=None, context=None, drop=None):
+    """drop: None (eval mode) or the training-mode dropout multipliers in the per-molecule form of forward_dense, applied
+    where the block's nn.Dropout acts (mol_gnn.py:263-268); padding rows take 1."""
     bs, N, _ = xh.shape
     D, De, L = hp.nf, hp.de, hp.n_layers
     SH, SC, H, C = hp.sub_heads, hp.sub_ch, hp.n_heads, hp.head_ch
@@ -192,10 +194,15 @@ def forward_faithful(p, hp, xh, node_mask, edge_mask, edge_x, cond_x=None, cond_
         ehat = _lin(p, b + '.node2edge_lin', hhat[row] + hhat[col])
         hn = h_in + ng1 * hhat
         hn = (_ln(hn) * (1 + nc2) + ns2) * nmask
-        h = (hn + ng2 * _lin(p, b + '.ff_linear2', F.silu(_lin(p, b + '.ff_linear1', hn)))) * nmask
         en = e_in + eg1 * ehat
         en = _ln(en) * (1 + ec2) + es2
-        e = en + eg2 * _lin(p, b + '.ff_linear4', F.silu(_lin(p, b + '.ff_linear3', en)))
+        if drop is None:
+            h = (hn + ng2 * _lin(p, b + '.ff_linear2', F.silu(_lin(p, b + '.ff_linear1', hn)))) * nmask
+            e = en + eg2 * _lin(p, b + '.ff_linear4', F.silu(_lin(p, b + '.ff_linear3', en)))
+        else:
+            m = _sparse_drop(drop, l, bs, N, bidx, iidx, jidx, hn.dtype)
+            h = (hn + ng2 * (_lin(p, b + '.ff_linear2', F.silu(_lin(p, b + '.ff_linear1', hn)) * m['A1']) * m['F2'])) * nmask
+            e = en + eg2 * (_lin(p, b + '.ff_linear4', F.silu(_lin(p, b + '.ff_linear3', en)) * m['A3']) * m['F4'])
         # equivariant update: note (shift, scale) order, row-grouped aggregation
         u = _lin(p, b + '.equi_update.input_lin', torch.cat([h[row], h[col], e, G], dim=1))
         shsc = _lin(p, b + '.equi_update.time_mlp.1', edge_t)
@@ -229,6 +236,27 @@ def forward_faithful(p, hp, xh, node_mask, edge_mask, edge_x, cond_x=None, cond_
     return torch.cat([pm, atom_pred], dim=2), edge_final
 
 
+def _sparse_drop(drop, l, bs, N, bidx, iidx, jidx, dt):
+    """Block l's multipliers of forward_faithful's rows: node rows b N + a of the padded batch (padding 1), edge rows in
+    edge_index order, gathered from the per-molecule dense form."""
+    out = {}
+    for s_ in ('A1', 'F2'):
+        w = drop[0][l][s_].shape[-1]
+        full = torch.ones(bs, N, w, dtype=dt)
+        for b in range(bs):
+            m = torch.as_tensor(drop[b][l][s_])
+            full[b, :m.shape[0]] = m.to(dt)
+        out[s_] = full.reshape(bs * N, w)
+    for s_ in ('A3', 'F4'):
+        w = drop[0][l][s_].shape[-1]
+        full = torch.ones(bs, N, N, w, dtype=dt)
+        for b in range(bs):
+            m = torch.as_tensor(drop[b][l][s_])
+            full[b, :m.shape[0], :m.shape[1]] = m.to(dt)
+        out[s_] = full[bidx, iidx, jidx]
+    return out
+
+
 def _mlp3(p, name, x):
     x = F.silu(_lin(p, name + '.0', x))
     x = F.silu(_lin(p, name + '.2', x))
@@ -239,8 +267,13 @@ def _mlp3(p, name, x):
 # dense per-molecule formulation (what the kernels compute)
 # ----------------------------------------------------------------------------------------------
 def forward_dense(p, hp, xh, node_mask, edge_mask, edge_x, cond_x=None, cond_edge_x=None,
-                  noise_level=None, context=None, return_intermediates=False):
+                  noise_level=None, context=None, return_intermediates=False, drop=None):
     """Dense restatement; loops over molecules (kept simple: it is a checker, not a product).
+
+    drop: None (eval mode: dropout is the identity) or training-mode dropout multipliers, drop[b][l] = {'A1': [n, r D],
+    'F2': [n, D], 'A3': [n, n, r De], 'F4': [n, n, De]} (oracle/philox_ref.dropout_masks), applied where the block's
+    nn.Dropout acts (mol_gnn.py:263-268): after SiLU(ff_linear1), after ff_linear2 (before the gate), and the same two in
+    the edge FFN.
 
     Index convention inside one molecule: tensors are [a, c, ...] with a = row = source,
     c = column = target.  Softmax/aggregation run over a (dim 0); the position update sums over c.
@@ -327,10 +360,15 @@ def forward_dense(p, hp, xh, node_mask, edge_mask, edge_x, cond_x=None, cond_edg
             n2e = F.linear(hhat, p[bk + '.node2edge_lin.weight'])                  # per node
             ehat = n2e[:, None, :] + n2e[None, :, :] + p[bk + '.node2edge_lin.bias']
             hn = _ln(h + ng1 * hhat) * (1 + nc2) + ns2
-            h = hn + ng2 * _lin(p, bk + '.ff_linear2', F.silu(_lin(p, bk + '.ff_linear1', hn)))
             e_in = e
             en = _ln(e + eg1 * ehat) * (1 + ec2) + es2
-            e = en + eg2 * _lin(p, bk + '.ff_linear4', F.silu(_lin(p, bk + '.ff_linear3', en)))
+            if drop is None:
+                h = hn + ng2 * _lin(p, bk + '.ff_linear2', F.silu(_lin(p, bk + '.ff_linear1', hn)))
+                e = en + eg2 * _lin(p, bk + '.ff_linear4', F.silu(_lin(p, bk + '.ff_linear3', en)))
+            else:
+                m = {k_: torch.as_tensor(v_).to(dt) for k_, v_ in drop[b][l].items()}
+                h = hn + ng2 * (_lin(p, bk + '.ff_linear2', F.silu(_lin(p, bk + '.ff_linear1', hn)) * m['A1']) * m['F2'])
+                e = en + eg2 * (_lin(p, bk + '.ff_linear4', F.silu(_lin(p, bk + '.ff_linear3', en)) * m['A3']) * m['F4'])
             W = p[bk + '.equi_update.input_lin.weight']
             Wr, Wc, We, Wd = W[:, :D], W[:, D:2 * D], W[:, 2 * D:2 * D + De], W[:, 2 * D + De:]
             pre = (F.linear(h, Wr)[:, None, :] + F.linear(h, Wc)[None, :, :] + F.linear(e, We)

@@ -31,6 +31,9 @@ cond_DGT_concat with `jodo_amd.models.init_utils.deterministic_init_` (weights a
                                                (6 NFE) and order 1 (3 NFE)
   ckpt_ref_qm9.pth.xz                          a checkpoint file written by the reference's utils.save_checkpoint (QM9 model,
                                                EMA, Adam state, step), xz-compressed; patterned weights keep it small
+  train_drop_qm9.npz                           the QM9 model in train() mode with its dropout modules multiplying by the training
+                                               path's masks (oracle/philox_ref.dropout_masks): a no-grad self-conditioning call, a
+                                               grad-enabled call on its outputs, gradients of seeded output gradients
 
 While doing so it asserts the oracle restatement (oracle/dgt_oracle.py) against the reference:
 faithful == reference bit-for-bit, dense within 1e-5.
@@ -54,7 +57,7 @@ OUT = os.path.join(ROOT, 'tests', 'golden')
 HEAD_GAIN = 30.0      # scale the heads' last layers so that argmax / threshold decodes are not degenerate
 
 
-def build_reference_model(ref, cfg_name, seed, head_gain=1.0, nf=None, n_layers=None):
+def build_reference_model(ref, cfg_name, seed, head_gain=1.0, nf=None, n_layers=None, gain=1.0):
     cfg = reference_config(cfg_name)
     cfg.device = torch.device('cpu')
     if nf is not None:
@@ -62,7 +65,7 @@ def build_reference_model(ref, cfg_name, seed, head_gain=1.0, nf=None, n_layers=
     if n_layers is not None:
         cfg.model.n_layers = n_layers                             # BASELINE configs[2] as worded: "nf=256, 8 layers"
     model = ref.models.utils._MODELS[cfg.model.name](cfg).eval()
-    deterministic_init_(model, seed=seed)
+    deterministic_init_(model, seed=seed, gain=gain)
     if head_gain != 1.0:
         with torch.no_grad():
             for k in ('node_pred_mlp.4.weight', 'edge_type_mlp.4.weight', 'edge_exist_mlp.4.weight'):
@@ -533,6 +536,147 @@ def checkpoint_fixture(ref, fname, step=123):
     print(fname, 'ok;', len(raw), 'bytes raw,', os.path.getsize(os.path.join(OUT, fname)), 'compressed')
 
 
+def savez_stable(path, **arrays):
+    """np.savez_compressed with a fixed member timestamp: regenerating a fixture reproduces the file bit for bit."""
+    import zipfile
+    with zipfile.ZipFile(path, 'w', compression=zipfile.ZIP_DEFLATED) as zf:
+        for k, v in arrays.items():
+            info = zipfile.ZipInfo(k + '.npy', date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            with zf.open(info, 'w', force_zip64=True) as f:
+                np.lib.format.write_array(f, np.asanyarray(v), allow_pickle=False)
+
+
+class DropInjector(torch.nn.Module):
+    """Stands in for a block's nn.Dropout (mol_gnn.py:218) under model.train(): multiplies by the training path's masks.  The
+    block calls it four times per forward, in the order A1 (SiLU(ff_linear1)), F2 (ff_linear2), A3, F4 (mol_gnn.py:263-268);
+    each call's feature width is checked.  Node rows are b N + a of the padded batch (padding: 1); edge rows follow the
+    block's edge_index, which a forward pre-hook on the block hands over."""
+    ORDER = ('A1', 'F2', 'A3', 'F4')
+
+    def __init__(self, layer, widths):
+        super().__init__()
+        self.layer, self.widths = layer, widths
+        self.masks, self.edge_index, self.calls = None, None, 0
+
+    def forward(self, x):
+        site = self.ORDER[self.calls % 4]
+        self.calls += 1
+        assert x.shape[-1] == self.widths[site], (self.layer, site, tuple(x.shape))
+        return x * self.dense_rows(site, x.shape[0])
+
+    def dense_rows(self, site, rows):
+        masks, l = self.masks, self.layer
+        n_nodes = [m[l]['F2'].shape[0] for m in masks]
+        B, N = len(n_nodes), self.N
+        if site in ('A1', 'F2'):
+            full = torch.ones(B, N, self.widths[site])
+            for b, n in enumerate(n_nodes):
+                full[b, :n] = torch.from_numpy(masks[b][l][site])
+            assert rows == B * N
+            return full.reshape(B * N, -1)
+        row, col = self.edge_index
+        b, i, j = row // N, row % N, col % N
+        assert torch.equal(col // N, b) and rows == row.numel()
+        full = torch.ones(B, N, N, self.widths[site])
+        for bb, n in enumerate(n_nodes):
+            full[bb, :n, :n] = torch.from_numpy(masks[bb][l][site])
+        return full[b, i, j]
+
+
+def dropout_fixture(ref, fname, n_nodes=(5, 9, 7, 3), seed=43, gain=2.0, s1=0x2545F4914F6CDD1D, s2=0x9E3779B97F4A7C15 >> 2):
+    """Training-mode dropout of the reference, with the training path's masks: the QM9 model under model.train(), each block's
+    nn.Dropout replaced by a DropInjector (TransMixLayer's F.dropout(alpha, p = 0), layers.py:179, is left as it is).  A
+    no-grad self-conditioning call with masks of seed s1, a grad-enabled call on its outputs with seed s2, then backward of
+    seeded output gradients.  Recorded: inputs, seeds, p, both outputs, the output gradients and the gradients of every
+    block's FFN biases plus a few weights.  Both oracle forwards with the same masks are checked here too."""
+    from oracle import philox_ref as PR
+    cfg, model = build_reference_model(ref, 'vpsde_qm9_uncond_jodo', seed, gain=gain)     # gain: FFN terms large enough to see the masks
+    hp = O.Hyper.from_config(cfg)
+    p = float(cfg.model.dropout)
+    assert p > 0
+    model.train()
+    n_nodes = list(n_nodes)
+    B, N = len(n_nodes), max(n_nodes)
+    nm, em = masks(n_nodes)
+    D, De, r, L = hp.nf, hp.de, hp.mlp_ratio, hp.n_layers
+    widths = {'A1': r * D, 'F2': D, 'A3': r * De, 'F4': De}
+    inj, hooks = [], []
+    for l in range(L):
+        blk = model._modules['e_block_%d' % l]
+        assert isinstance(blk.dropout, torch.nn.Dropout) and blk.dropout.p == p
+        d = DropInjector(l, widths)
+        d.N = N
+        blk.dropout = d
+        inj.append(d)
+
+        def pre(m, args, d=d):
+            d.edge_index = args[3]                          # forward(pos, h, edge_attr, edge_index, ...)
+        hooks.append(blk.register_forward_pre_hook(pre))
+    g = torch.Generator().manual_seed(seed + 100)
+    xh = torch.randn(B, N, 3 + hp.in_node_dim, generator=g) * nm
+    xh[:, :, :3] = xh[:, :, :3] - xh[:, :, :3].sum(1, keepdim=True) / nm.sum(1, keepdim=True) * nm
+    ex = torch.randn(B, N, N, hp.edge_ch, generator=g)
+    ex = (torch.tril(ex.permute(0, 3, 1, 2), -1) + torch.tril(ex.permute(0, 3, 1, 2), -1).transpose(-1, -2)).permute(0, 2, 3, 1)
+    ex = ex * em.reshape(B, N, N, 1)
+    nl = torch.randn(B, generator=g) * 2.0
+    d_x = torch.randn(B, N, 3 + hp.in_node_dim, generator=g)
+    d_e = torch.randn(B, N, N, hp.edge_ch, generator=g)
+    m1 = PR.dropout_masks(s1, p, n_nodes, L, D, De, r)
+    m2 = PR.dropout_masks(s2, p, n_nodes, L, D, De, r)
+    kw = dict(edge_x=ex, noise_level=nl, context=None)
+
+    def run(ms, cx, cex):
+        for d in inj:
+            d.masks, d.calls = ms, 0
+        out = model(torch.ones(B), xh, nm, em, cond_x=cx, cond_edge_x=cex, **kw)
+        assert all(d.calls == 4 for d in inj)
+        return out
+
+    try:
+        with torch.no_grad():
+            r1 = run(m1, None, None)
+        model.zero_grad()
+        r2 = run(m2, r1[0], r1[1])
+        threads = torch.get_num_threads()
+        torch.set_num_threads(1)                            # the CPU backward's scatter sums are reordered by threads: keep the file reproducible
+        ((r2[0] * d_x).sum() + (r2[1] * d_e).sum()).backward()
+        torch.set_num_threads(threads)
+    finally:
+        for h_ in hooks:
+            h_.remove()
+    params = dict(model.named_parameters())
+    names = ['e_block_%d.ff_linear%d.bias' % (l, k) for l in range(L) for k in (1, 2, 3, 4)]
+    names += ['e_block_0.ff_linear3.weight', 'e_block_7.ff_linear4.weight', 'e_block_3.ff_linear2.weight', 'e_block_5.node2edge_lin.bias',
+              'e_block_6.attn_mpnn.lin_edge0.weight', 'e_block_2.equi_update.coord_norm.scale', 'node_emb.bias', 'edge_emb.bias',
+              'time_mlp.0.weights', 'edge_exist_mlp.4.weight', 'node_pred_mlp.4.weight']
+    assert len(set(names)) == len(names) and all(params[k].grad is not None for k in names)
+    # the oracle restatement with the same masks: faithful bit for bit, dense within 1e-5, dense autograd within 2e-4
+    sd = {k: v.detach().clone().requires_grad_(True) for k, v in model.state_dict().items()}
+    with torch.no_grad():
+        f1 = O.forward_faithful(sd, hp, xh, nm, em, ex, None, None, nl, None, drop=m1)
+        f2 = O.forward_faithful(sd, hp, xh, nm, em, ex, r1[0], r1[1], nl, None, drop=m2)
+    assert torch.equal(f1[0], r1[0]) and torch.equal(f1[1], r1[1]), "faithful oracle != reference (dropout, call 1)"
+    assert torch.equal(f2[0], r2[0].detach()) and torch.equal(f2[1], r2[1].detach()), "faithful oracle != reference (dropout, call 2)"
+    px, pe = O.forward_dense(sd, hp, xh, nm, em, ex, r1[0], r1[1], nl, None, drop=m2)
+    err = max((px - r2[0]).abs().max().item(), (pe - r2[1]).abs().max().item())
+    assert err < 1e-5, "dense oracle vs reference (dropout): %g" % err
+    ((px * d_x).sum() + (pe * d_e).sum()).backward()
+    for k in names:
+        a, b = sd[k].grad, params[k].grad
+        rel = (a - b).abs().max().item() / (b.abs().max().item() + 1e-12)
+        assert rel < 2e-4, "oracle gradient of %s (dropout): rel err %g" % (k, rel)
+    with torch.no_grad():                                   # the masks matter: eval mode gives another function
+        e2 = O.forward_dense(sd, hp, xh, nm, em, ex, r1[0], r1[1], nl, None)
+    assert (e2[0] - r2[0]).abs().max().item() > 0.1 and (e2[1] - r2[1]).abs().max().item() > 0.1
+    savez_stable(os.path.join(OUT, fname), cfg_name='vpsde_qm9_uncond_jodo', seed=seed, gain=np.float32(gain), n_nodes=np.array(n_nodes), p=np.float32(p),
+                 seed1=np.uint64(s1), seed2=np.uint64(s2), xh=xh.numpy(), edge_x=ex.numpy(), noise_level=nl.numpy(),
+                 out1_x=r1[0].numpy(), out1_e=r1[1].numpy(), out2_x=r2[0].detach().numpy(), out2_e=r2[1].detach().numpy(),
+                 d_out_x=d_x.numpy(), d_out_e=d_e.numpy(), grad_names=np.array(names),
+                 **{'grad_%d' % i: params[k].grad.numpy() for i, k in enumerate(names)})
+    print(fname, 'ok; dense err', err, 'bytes', os.path.getsize(os.path.join(OUT, fname)))
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     ref = load_reference()
@@ -561,6 +705,7 @@ def main():
         # BASELINE configs[0] at its own size (batch 64, 50 steps) through the reference's get_sampling_fn
         ('traj_qm9_cfg0.npz', lambda f: cfg0_fixture(ref, f)),
         ('ckpt_ref_qm9.pth.xz', lambda f: checkpoint_fixture(ref, f)),
+        ('train_drop_qm9.npz', lambda f: dropout_fixture(ref, f)),
     ]
     want = sys.argv[1:]
     for fname, job in jobs:

@@ -6,6 +6,9 @@ numbering of jodo_sampler_step_rng / jodo_dpm_update_rng): Philox4x32-10 as publ
 24-bit uniforms.  The reference draws its noise with torch.randn (models/utils.py:67-99); there is no reference
 counterpart of the generator itself, so it is pinned by the Random123 known-answer vectors
 (tests/test_host_logic.py::test_philox_known_answers) and the kernel is pinned against this file.
+
+Also the training path's dropout masks (csrc/train_common.h drop_mul, element numbering of dgt_train.hip): `drop_mul`,
+`dropout_masks`, fed to the oracle's `drop=` argument (tests/test_train_emul.py, tests/test_train_dropout_gpu.py).
 """
 import numpy as np
 
@@ -75,3 +78,51 @@ def edge_noise(seed, draw, n_nodes, N, ch):
     m = (a[None, :] < np.asarray(n_nodes)[:, None])
     em = (m[:, :, None] & m[:, None, :] & (a[:, None] != a[None, :])[None]).astype(np.float32)
     return (z * em[..., None]).astype(np.float32)
+
+
+# ---- training-path dropout masks (csrc/train_common.h drop_mul) ------------------------------------------------------------------
+DROP_SITES = {'A1': 1, 'F2': 2, 'A3': 3, 'F4': 4}      # after SiLU(ff_linear1), after ff_linear2, the same two of the edge FFN
+DROP_TAG = 0x4a4f444f
+
+
+def drop_site(layer, name):
+    return layer * 8 + DROP_SITES[name]
+
+
+def drop_mul(seed, site, p, count):
+    """float32 [count]: the multiplier of elements 0 .. count-1 of one site.  Element idx draws lane idx & 3 of
+    Philox4x32-10 at counter (idx >> 2, idx >> 34, site, 'JODO') under key (seed lo, seed hi); it is dropped when its 24-bit
+    uniform is below p, else scaled by the float32 1 / (1 - p); p = 0 gives exactly 1."""
+    p = np.float32(p)
+    if p <= 0:
+        return np.ones(count, np.float32)
+    quad = np.arange((count + 3) // 4, dtype=np.uint64)
+    ctr = np.stack([quad & MASK, quad >> np.uint64(32), np.full(quad.shape, site, np.uint64), np.full(quad.shape, DROP_TAG, np.uint64)],
+                   axis=-1).astype(np.uint32)
+    key = np.array([seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF], dtype=np.uint32)
+    u = philox4x32_10(ctr, key).reshape(-1)[:count]
+    uni = (u >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
+    keep = np.float32(1.0) / (np.float32(1.0) - p)
+    return np.where(uni < p, np.float32(0.0), keep).astype(np.float32)
+
+
+def dropout_masks(seed, p, n_nodes, n_layers, D, De, r):
+    """The multipliers of every dropout site, per molecule and block, in the shapes of the dense oracle
+    (dgt_oracle.forward_dense `drop=`): masks[b][l] = {'A1': [n, r D], 'F2': [n, D], 'A3': [n, n, r De], 'F4': [n, n, De]}.
+    Element numbering of the training path (dgt_train.hip jodo_train_create): node row node_off[b] + a, edge row
+    edge_off[b] + a n_b + c for the pair (a = source, c = target), element row * width + feature."""
+    n_nodes = [int(n) for n in n_nodes]
+    node_off = np.concatenate([[0], np.cumsum(n_nodes)])
+    edge_off = np.concatenate([[0], np.cumsum([n * n for n in n_nodes])])
+    Nn, R = int(node_off[-1]), int(edge_off[-1])
+    masks = [[None] * n_layers for _ in n_nodes]
+    for l in range(n_layers):
+        m = {'A1': drop_mul(seed, drop_site(l, 'A1'), p, Nn * r * D).reshape(Nn, r * D),
+             'F2': drop_mul(seed, drop_site(l, 'F2'), p, Nn * D).reshape(Nn, D),
+             'A3': drop_mul(seed, drop_site(l, 'A3'), p, R * r * De).reshape(R, r * De),
+             'F4': drop_mul(seed, drop_site(l, 'F4'), p, R * De).reshape(R, De)}
+        for b, n in enumerate(n_nodes):
+            masks[b][l] = {'A1': m['A1'][node_off[b]:node_off[b] + n], 'F2': m['F2'][node_off[b]:node_off[b] + n],
+                           'A3': m['A3'][edge_off[b]:edge_off[b] + n * n].reshape(n, n, r * De),
+                           'F4': m['F4'][edge_off[b]:edge_off[b] + n * n].reshape(n, n, De)}
+    return masks

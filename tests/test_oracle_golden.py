@@ -232,3 +232,68 @@ def test_cond_sampling_eval_fn_reproduces_the_reference():
     # the classifier's edge list: fully connected with self-loops, batch offsets, row-major (cond_gen/utils.py:15-38)
     r, c = full_edge_index(3, 2, 'cpu')
     assert r.tolist() == [0, 0, 0, 1, 1, 1, 2, 2, 2, 3, 3, 3, 4, 4, 4, 5, 5, 5] and c.tolist() == [0, 1, 2] * 3 + [3, 4, 5] * 3
+
+
+def _drop_fixture_model():
+    from oracle import philox_ref as PR
+    fx = load_fixture('train_drop_qm9.npz')
+    cfg = make_config(str(fx['cfg_name']))
+    model = make_model(cfg, int(fx['seed']), gain=float(fx['gain']))
+    hp = O.Hyper.from_config(cfg)
+    n_nodes = fx['n_nodes'].tolist()
+    p = float(fx['p'])
+    assert p == np.float32(cfg.model.dropout)
+    ms = [PR.dropout_masks(int(fx['seed%d' % i]), p, n_nodes, hp.n_layers, hp.nf, hp.de, hp.mlp_ratio) for i in (1, 2)]
+    return fx, cfg, model, hp, n_nodes, ms
+
+
+def test_masked_oracle_reproduces_the_reference_in_train_mode():
+    """tests/golden/train_drop_qm9.npz: the reference's QM9 model under model.train() with its dropout modules multiplying by the
+    training path's masks.  Both oracle forwards with the restated masks reproduce its two calls (faithful bit for bit, dense within
+    1e-5), and autograd through the dense oracle its recorded gradients (2e-4 relative) — every block's FFN biases among them."""
+    fx, cfg, model, hp, n_nodes, (m1, m2) = _drop_fixture_model()
+    sd = {k: v.detach().clone().requires_grad_(True) for k, v in model.state_dict().items()}
+    nm, em = masks(n_nodes)
+    t = lambda k: torch.from_numpy(fx[k])
+    with torch.no_grad():
+        f1 = O.forward_faithful(sd, hp, t('xh'), nm, em, t('edge_x'), None, None, t('noise_level'), None, drop=m1)
+        f2 = O.forward_faithful(sd, hp, t('xh'), nm, em, t('edge_x'), t('out1_x'), t('out1_e'), t('noise_level'), None, drop=m2)
+        d1 = O.forward_dense(sd, hp, t('xh'), nm, em, t('edge_x'), None, None, t('noise_level'), None, drop=m1)
+    assert torch.equal(f1[0], t('out1_x')) and torch.equal(f1[1], t('out1_e'))
+    assert torch.equal(f2[0], t('out2_x')) and torch.equal(f2[1], t('out2_e'))
+    assert (d1[0] - t('out1_x')).abs().max() < 1e-5 and (d1[1] - t('out1_e')).abs().max() < 1e-5
+    px, pe = O.forward_dense(sd, hp, t('xh'), nm, em, t('edge_x'), t('out1_x'), t('out1_e'), t('noise_level'), None, drop=m2)
+    assert (px.detach() - t('out2_x')).abs().max() < 1e-5 and (pe.detach() - t('out2_e')).abs().max() < 1e-5
+    ((px * t('d_out_x')).sum() + (pe * t('d_out_e')).sum()).backward()
+    names = fx['grad_names'].tolist()
+    assert all('e_block_%d.ff_linear%d.bias' % (l, k) in names for l in range(hp.n_layers) for k in (1, 2, 3, 4))
+    for i, k in enumerate(names):
+        want = t('grad_%d' % i)
+        rel = (sd[k].grad - want).abs().max().item() / (want.abs().max().item() + 1e-12)
+        assert rel < 2e-4, "%s: %g" % (k, rel)
+    # the fixture sees the masks: the same call with the other seed's masks, or without dropout, is far from it
+    with torch.no_grad():
+        for other in (m1, None):
+            o = O.forward_dense(sd, hp, t('xh'), nm, em, t('edge_x'), t('out1_x'), t('out1_e'), t('noise_level'), None, drop=other)
+            assert (o[0] - t('out2_x')).abs().max() > 0.1
+
+
+def test_oracle_drop_none_and_all_ones_masks_leave_the_forward_unchanged():
+    """drop=None is the eval-mode oracle of before; masks of ones (p = 0) give the same bits through the dropout branch."""
+    from oracle import philox_ref as PR
+    fx = load_fixture('fwd_qm9.npz')
+    cfg = make_config(str(fx['cfg_name']), n_layers=4)
+    sd = state_dict_cpu(make_model(cfg, int(fx['seed'])))
+    hp = O.Hyper.from_config(cfg)
+    n_nodes = fx['n_nodes'].tolist()
+    nm, em = masks(n_nodes)
+    t = lambda k: torch.from_numpy(fx[k])
+    ones = PR.dropout_masks(123, 0.0, n_nodes, hp.n_layers, hp.nf, hp.de, hp.mlp_ratio)
+    with torch.no_grad():
+        for fn in (O.forward_faithful, O.forward_dense):
+            for cx, cex in ((None, None), (t('out1_x'), t('out1_e'))):
+                a = fn(sd, hp, t('xh'), nm, em, t('edge_x'), cx, cex, t('noise_level'), None)
+                b = fn(sd, hp, t('xh'), nm, em, t('edge_x'), cx, cex, t('noise_level'), None, drop=None)
+                c = fn(sd, hp, t('xh'), nm, em, t('edge_x'), cx, cex, t('noise_level'), None, drop=ones)
+                assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+                assert torch.equal(a[0], c[0]) and torch.equal(a[1], c[1])

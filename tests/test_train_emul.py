@@ -146,3 +146,138 @@ def test_dropout_masks_are_shared_by_forward_and_backward(emul):
     fd = (plus - minus) / (2 * eps)
     an = float(sum((gq.double() * v.double()).sum() for gq, v in zip(grads, vs)))
     assert abs(fd - an) <= 2e-2 * max(abs(an), abs(fd), 1e-6), (fd, an)
+
+
+# ---- dropout on: the kernels against the float64 oracle with the restated masks (oracle/philox_ref.dropout_masks) ----------------
+DROP_SEED = (0x5DEECE66D << 20) | 0x1234567           # >= 2^32: the key's high word matters
+
+
+def drop_masks_for(hp, n_nodes, p, seed):
+    from oracle import philox_ref as PR
+    return PR.dropout_masks(seed, p, n_nodes, hp.n_layers, hp.nf, hp.de, hp.mlp_ratio)
+
+
+def oracle_grads_masked(model, hp, xh, nm, em, ex, cx, cex, nl, ctx, d_out_x, d_out_e, drop, dtype=torch.float64):
+    sd = {k: v.detach().to(dtype).clone().requires_grad_(True) for k, v in model.state_dict().items()}
+    c = lambda t: None if t is None else t.to(dtype)
+    px, pe = O.forward_dense(sd, hp, c(xh), c(nm), c(em), c(ex), c(cx), c(cex), c(nl), c(ctx), drop=drop)
+    ((px * d_out_x.to(dtype)).sum() + (pe * d_out_e.to(dtype)).sum()).backward()
+    return px.detach(), pe.detach(), {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in sd.items()}
+
+
+@pytest.mark.parametrize("cfg_name,n_nodes,over,selfcond", [
+    ('vpsde_qm9_uncond_jodo', [4, 1, 2, 6], dict(nf=128, n_layers=2), False),
+    ('vpsde_qm9_uncond_jodo', [5, 3, 7], dict(nf=128, n_layers=2), True),
+    ('vpsde_qm9_cond_jodo', [3, 5], dict(nf=128, n_layers=2), True),
+    ('vpsde_qm9_cond_jodo', [6, 2, 4], dict(nf=128, n_layers=2), False),
+])
+def test_dropout_on_matches_autograd_through_the_masked_oracle(emul, cfg_name, n_nodes, over, selfcond):
+    """Training-mode dropout (p = 0.1, a seed above 2^32) through the emulation build against float64 autograd through the oracle
+    with the restated masks: the outputs and every parameter's gradient.  Pins the site numbering, the row numbering of nodes and
+    edge pairs, the scale, and that nothing else (the attention weights) is dropped."""
+    cfg = make_config(cfg_name, **over)
+    model = make_model(cfg, 3, gain=1.5, coord_scale=0.05)
+    hp = O.Hyper.from_config(cfg)
+    xh, ex, nl, ctx, nm, em = random_inputs(hp, n_nodes, seed=5)
+    g = torch.Generator().manual_seed(9)
+    cx = cex = None
+    if selfcond:
+        cx = torch.randn(xh.shape, generator=g) * nm
+        cex = torch.randn(ex.shape, generator=g)
+        cex = (cex + cex.transpose(1, 2)) * em.reshape(ex.shape[0], ex.shape[1], ex.shape[1], 1)
+    d_x = torch.randn(xh.shape, generator=g)
+    d_e = torch.randn(ex.shape, generator=g)
+    p = 0.1
+    drop = drop_masks_for(hp, n_nodes, p, DROP_SEED)
+    eng, names = engine_for(emul, model, n_nodes)
+    params = [v.detach().float().contiguous() for v in model.state_dict().values()]
+    out_x, out_e = eng.forward(params, xh, ex, cx, cex, nl, ctx, p, DROP_SEED)
+    px, pe, want = oracle_grads_masked(model, hp, xh, nm, em, ex, cx, cex, nl, ctx, d_x, d_e, drop)
+    assert (out_x.double() - px).abs().max() < 2e-5 and (out_e.double() - pe).abs().max() < 2e-5
+    with torch.no_grad():                                       # the masks matter at this size: eval mode is far away
+        ev = O.forward_dense({k: v.double() for k, v in model.state_dict().items()}, hp, xh.double(), nm.double(), em.double(), ex.double(),
+                             None if cx is None else cx.double(), None if cex is None else cex.double(), nl.double(),
+                             None if ctx is None else ctx.double())
+    assert (ev[0] - px).abs().max() > 1e-3
+    grads = eng.backward(params, nl, d_x, d_e, p, DROP_SEED)
+    compare_all(names, grads, want, 3e-4)
+
+
+def test_dropout_kernel_activations_follow_the_restated_masks(emul):
+    """The kept FFN activations of the emulation build (jodo_train_debug_locate 2 - 7): a1 and a3 are zero exactly where the
+    restatement drops, and elsewhere SiLU(f) x 1 / (1 - p) to a few ulps; first and last block, p 0.1 and 0.5, a seed above 2^32."""
+    from oracle import philox_ref as PR
+    cfg = make_config('vpsde_qm9_uncond_jodo', nf=128, n_layers=3)
+    model = make_model(cfg, 4, gain=1.5, coord_scale=0.05)
+    hp = O.Hyper.from_config(cfg)
+    n_nodes = [5, 1, 8, 3]
+    xh, ex, nl, ctx, nm, em = random_inputs(hp, n_nodes, seed=8)
+    eng, names = engine_for(emul, model, n_nodes)
+    params = [v.detach().float().contiguous() for v in model.state_dict().values()]
+    for p, seed in ((0.1, DROP_SEED), (0.5, 7)):
+        eng.forward(params, xh, ex, None, None, nl, None, p, seed)
+        for l in (0, hp.n_layers - 1):
+            check_ffn_masks(eng, hp, n_nodes, p, seed, l, PR)
+
+
+_MASKS = {}
+
+
+def check_ffn_masks(eng, hp, n_nodes, p, seed, l, PR):
+    """a1 / a3 of block l against the restated masks of sites A1 / A3 (shared with tests/test_train_dropout_gpu.py)."""
+    Nn, R = sum(n_nodes), sum(n * n for n in n_nodes)
+    r, D, De = hp.mlp_ratio, hp.nf, hp.de
+    scale = float(torch.tensor(1.0, dtype=torch.float32) / (torch.tensor(1.0, dtype=torch.float32) - torch.tensor(p, dtype=torch.float32)))
+    for f_sel, a_sel, site, count in ((2, 3, 'A1', Nn * r * D), (5, 6, 'A3', R * r * De)):
+        f, a = eng.debug_fetch(f_sel, l).cpu().double(), eng.debug_fetch(a_sel, l).cpu().double()
+        assert f.numel() == count and a.numel() == count
+        key = (seed, PR.drop_site(l, site), p, count)
+        if key not in _MASKS:
+            _MASKS[key] = torch.from_numpy(PR.drop_mul(*key))
+        m = _MASKS[key]
+        dropped = m == 0
+        frac = float(dropped.double().mean())
+        assert abs(frac - p) < 5 * (p * (1 - p) / count) ** 0.5 + 1e-12, (l, site, frac)
+        want = torch.where(dropped, 0.0, (f * torch.sigmoid(f)) * scale)
+        # dropped: exactly 0; kept: SiLU(f) / (1 - p) to a few ulps (0 only where SiLU(f) is)
+        bad = (a - want).abs() > 4 * 2.0 ** -23 * want.abs()
+        if bool(bad.any()):
+            i = bad.nonzero()[:8, 0].tolist()
+            w = count // (Nn if site == 'A1' else R)
+            raise AssertionError("block %d site %s (p %g, seed %d): %d of %d elements differ; first (row, feature, f, a, restated multiplier): %s"
+                                 % (l, site, p, seed, int(bad.sum()), count, [(j // w, j % w, float(f[j]), float(a[j]), float(m[j])) for j in i]))
+
+
+# ---- host properties of the mask restatement ------------------------------------------------------------------------------------
+def test_dropout_restatement_host_properties():
+    """p = 0 is exactly 1; the keep rate of every site of every block lies within 5 sigma of 1 - p on the config's training batch
+    (128 QM9 molecules); seeds that differ only in their high 32 bits give different masks; the multiplier is the float32 1 / (1 - p)."""
+    import numpy as np
+    from jodo_amd.models import load_dataset_info, get_node_dist
+    from oracle import philox_ref as PR
+    assert np.array_equal(PR.drop_mul(DROP_SEED, 9, 0.0, 1001), np.ones(1001, np.float32))
+    z = PR.dropout_masks(DROP_SEED, 0.0, [3, 2], 2, 16, 4, 2)
+    assert all(np.array_equal(v, np.ones_like(v)) for mol in z for blk in mol for v in blk.values())
+    cfg = make_config('vpsde_qm9_uncond_jodo')
+    hp = O.Hyper.from_config(cfg)
+    torch.manual_seed(5)
+    n_nodes = get_node_dist(load_dataset_info('qm9_with_h')).sample(int(cfg.training.batch_size)).tolist()
+    Nn, R = sum(n_nodes), sum(n * n for n in n_nodes)
+    assert R > 30000
+    p = 0.1
+    widths = {'A1': (Nn, hp.mlp_ratio * hp.nf), 'F2': (Nn, hp.nf), 'A3': (R, hp.mlp_ratio * hp.de), 'F4': (R, hp.de)}
+    keep = np.float32(1) / (np.float32(1) - np.float32(p))
+    for l in range(hp.n_layers):
+        for site, (rows, w) in widths.items():
+            m = PR.drop_mul(DROP_SEED, PR.drop_site(l, site), p, rows * w)
+            assert set(np.unique(m).tolist()) == {0.0, float(keep)}
+            kept = float((m != 0).mean())
+            assert abs(kept - (1 - p)) < 5 * (p * (1 - p) / m.size) ** 0.5, (l, site, kept)
+    lo = DROP_SEED & 0xFFFFFFFF
+    a = PR.drop_mul(lo | (1 << 32), PR.drop_site(0, 'A1'), p, 4096)
+    b = PR.drop_mul(lo | (2 << 32), PR.drop_site(0, 'A1'), p, 4096)
+    c = PR.drop_mul(lo, PR.drop_site(0, 'A1'), p, 4096)
+    assert not np.array_equal(a, b) and not np.array_equal(a, c) and not np.array_equal(b, c)
+    # sites and layers are distinct streams
+    assert not np.array_equal(PR.drop_mul(7, PR.drop_site(0, 'F2'), p, 4096), PR.drop_mul(7, PR.drop_site(0, 'F4'), p, 4096))
+    assert not np.array_equal(PR.drop_mul(7, PR.drop_site(0, 'A1'), p, 4096), PR.drop_mul(7, PR.drop_site(1, 'A1'), p, 4096))
