@@ -72,22 +72,13 @@ struct AttnT {
     static constexpr int PHB = WQK_ ? 1 : ((VAR_ == 0 || SPLIT) ? 1 : (VAR_ == 2 ? D_ / 32 : 4));   // message blocks per hand-over phase
     static constexpr int NQB = WQK_ ? 14 : 8;                      // 32-row blocks of q / k / lin_edge0
     static constexpr int KQE = D_ / 32;                            // weight quads per output block for K = De
-#ifndef JODO_X_ATT_PG384                                           // experiment builds (tools/gpu_attn384_ab.sh): -DJODO_X_ATT_...
-#define JODO_X_ATT_PG384 4
-#endif
-#ifndef JODO_X_ATT_PREF384
-#define JODO_X_ATT_PREF384 0
-#endif
-#ifndef JODO_X_ATT_LDSS384
-#define JODO_X_ATT_LDSS384 1
-#endif
-    static constexpr int PG = (D_ % 256 == 0) ? 8 : (D_ == 384 ? JODO_X_ATT_PG384 : 4);   // quads in flight (must divide KQE)
+    static constexpr int PG = (D_ % 256 == 0) ? 8 : 4;             // quads in flight (must divide KQE)
     static constexpr bool PH = (D_ / 16 == 16) && !(D_ > 256);     // C = 16: a half-lane's registers belong to heads 2b + half only, so it
     static constexpr int NS = PH ? 8 : 16;                         // tracks 8 heads (slot k = head 2k + half) instead of all 16
-    static constexpr bool PREF = (!(D_ > 256) || JODO_X_ATT_PREF384 != 0) && !SPLIT;   // request the next source's edge row one iteration ahead (D/8 registers; not in the split form: its operands' split images need them)
-    static constexpr bool QK2 = false;   // q / k rows two blocks ahead in two register sets: measured SLOWER on MI355X (QM9 B = 2500: attention
-                                         // 3.91 -> 4.00 ms/step, 455 -> 490 registers) — the block's wait is issue, not row latency; kept as a switch
-    static constexpr bool LDSS = D_ > 256 && JODO_X_ATT_LDSS384 != 0;   // running softmax state in LDS (registers are short at nf = 384:
+    static constexpr bool PREF = !(D_ > 256) && !SPLIT;            // request the next source's edge row one iteration ahead (D/8 registers; not in the split form: its operands' split images need them)
+    // (Tried and dropped: q / k rows two blocks ahead in two register sets — SLOWER on MI355X, QM9 B = 2500: attention 3.91 -> 4.00 ms/step,
+    // 455 -> 490 registers; the block's wait is issue, not row latency.)
+    static constexpr bool LDSS = D_ > 256;                         // running softmax state in LDS (registers are short at nf = 384:
                                                                    // D/2 accumulators + D/8 inputs per lane; LDS is free, no resident weights)
     // the share of one launch: head slots [SL0, SL0 + NSL) (PH: slot k = head 2k + half = message block k), score blocks [SB0, SB1) of
     // lin_edge0 besides its tail block, learned heads [G0, G1) in the tail block; everything unless SPLIT
@@ -212,7 +203,7 @@ __device__ __forceinline__ void attn_edge_input(const KArgs& A, AttnW<X>& w, con
 // scores of one pair for both directions from T0 = tanh(lin_edge0 x): S1 = edge (j -> i), S2 = edge (i -> j); all 16
 // heads in every lane (heads 0, 1 = adjacency heads from the edge flags f1 / f2, 2.. = learned)
 // first q / k rows of a pair (block 0): requested by the caller ahead of the edge-input projections where registers allow
-// q / k rows of a pair, one register set per block in flight (X::QK2: two alternating sets, [0] even blocks, [1] odd)
+// q / k rows of a pair: one register set, the block in flight
 struct QKRows { float qi[16], ki[16], qj[16], kj[16]; };
 template <bool BOTH>
 __device__ __forceinline__ void attn_rows(const BRow& qi, const BRow& ki, const BRow& qj, const BRow& kj, int b, QKRows& r) {
@@ -223,15 +214,14 @@ __device__ __forceinline__ void attn_rows(const BRow& qi, const BRow& ki, const 
 template <typename X, bool BOTH>
 __device__ __forceinline__ void attn_scores(AttnW<X>& w, const float (&x)[X::HE], const BRow& qi, const BRow& ki, const BRow& qj,
                                             const BRow& kj, int half, int f1, int f2, float (&S1)[16], float (&S2)[16],
-                                            QKRows (&rows)[X::QK2 ? 2 : 1], const Split8* xs = nullptr) {
-    // rows[b & 1] (QK2) / rows[0] holds block b on entry to iteration b: blocks 0 (and 1) were requested by the caller
+                                            QKRows& R, const Split8* xs = nullptr) {
+    // R holds block b on entry to iteration b: block 0 was requested by the caller
     float m1[X::WQK ? 1 : 7], m2[X::WQK ? 1 : 7];       // blocks reduced per head / per head pair
     S1[0] = (f1 & 1) ? 1.f : -1e10f; S1[1] = (f1 & 2) ? 1.f : -1e10f;           // extra heads, 0 -> -1e10 (layers.py:170-174)
     S2[0] = (f2 & 1) ? 1.f : -1e10f; S2[1] = (f2 & 2) ? 1.f : -1e10f;
 #pragma unroll
     for (int b = X::SB0; b < X::SB1; ++b) {
         float a1[16], a2[16];
-        QKRows& R = rows[X::QK2 ? (b & 1) : 0];
 #pragma unroll
         for (int s = 0; s < 16; s += 2) {
             const f32x2 p1 = pk2(R.qi[s], R.qi[s + 1]) * pk2(R.kj[s], R.kj[s + 1]);
@@ -239,10 +229,9 @@ __device__ __forceinline__ void attn_scores(AttnW<X>& w, const float (&x)[X::HE]
             if (BOTH) { const f32x2 p2 = pk2(R.qj[s], R.qj[s + 1]) * pk2(R.ki[s], R.ki[s + 1]); a2[s] = p2.x; a2[s + 1] = p2.y; }
             else { a2[s] = 0.f; a2[s + 1] = 0.f; }
         }
-        auto next_rows = [&]() {                       // the set just consumed takes the block two (one) ahead
-            constexpr int AHEAD = X::QK2 ? 2 : 1;
+        auto next_rows = [&]() {                       // the set just consumed takes the next block
             if constexpr (X::SPLIT) attn_rows<BOTH>(qi, ki, qj, kj, b + 1 < X::SB1 ? b + 1 : X::NQB - 1, R);   // after its share: the tail block
-            else if (b + AHEAD < X::NQB) attn_rows<BOTH>(qi, ki, qj, kj, b + AHEAD, R);
+            else if (b + 1 < X::NQB) attn_rows<BOTH>(qi, ki, qj, kj, b + 1, R);
         };
         if constexpr (X::LDS_L0) pipeline_fence();
         const unsigned cur = w.oL0 + (unsigned)(b * X::KQE) * 1024;
@@ -280,7 +269,6 @@ __device__ __forceinline__ void attn_scores(AttnW<X>& w, const float (&x)[X::HE]
 #pragma unroll
         for (int g = X::G0; g < X::G1; ++g) {
             const float tt = tanh_f(acc[g]);
-            const QKRows& R = rows[X::QK2 ? ((X::NQB - 1) & 1) : 0];
             tl1[g] = tt * R.qi[g] * R.kj[g];
             tl2[g] = BOTH ? tt * R.qj[g] * R.ki[g] : 0.f;
         }
@@ -409,8 +397,8 @@ __device__ __forceinline__ void attn_item(const KArgs& A, const float4* wl, floa
         // the first q / k rows of the pair travel behind the edge-input projections (8k cycles) where registers allow
         const BRow qi = brow(A.q, X::NQB, L.v, half), ki = brow(A.k, X::NQB, L.v, half);
         const BRow qj = brow(A.q, X::NQB, u, half), kj = brow(A.k, X::NQB, u, half);
-        QKRows rows[X::QK2 ? 2 : 1];
-        if constexpr (PREF) attn_rows<PAIR>(qi, ki, qj, kj, X::SB0, rows[0]);
+        QKRows rows;
+        if constexpr (PREF) attn_rows<PAIR>(qi, ki, qj, kj, X::SB0, rows);
         attn_edge_input<X>(A, w, e, dx * dx + dy * dy + dz * dz, gscale, gshift, mrow, half, x);
         Split8 xs[X::SPLIT ? 4 : 1];                    // SPLIT: et as split operands, for the 16 projection blocks of scores and messages
         if constexpr (X::SPLIT) {
@@ -422,9 +410,8 @@ __device__ __forceinline__ void attn_item(const KArgs& A, const float4* wl, floa
             cur = source(t + 1 < t1 ? t + 1 : t);      // next source: its row, position and flags are requested now
             request();
         } else {
-            attn_rows<PAIR>(qi, ki, qj, kj, X::SB0, rows[0]);
+            attn_rows<PAIR>(qi, ki, qj, kj, X::SB0, rows);
         }
-        if constexpr (X::QK2) attn_rows<PAIR>(qi, ki, qj, kj, 1, rows[1]);   // second set: requested behind the edge-input projections
         // ---- scores ----
         float Sa[X::NS], R[X::LDSS ? 1 : X::NS];           // scores of the own source / of the handed-over source per head slot
         {
@@ -614,11 +601,8 @@ __device__ __forceinline__ void attn_item(const KArgs& A, const float4* wl, floa
 // (ai_dir: every lane visits all its sources, no hand-over), so that symmetric inputs need one launch whatever the sizes.
 // PAIR = false: the directed launch (ad_* items), runs when the inputs are asymmetric (and for ad_big items: molecules larger than
 // a group when the pair launch does not carry them, i.e. fixed-chunk plans)
-#ifndef JODO_X_ATT_SPLIT_OCC
-#define JODO_X_ATT_SPLIT_OCC(VAR) 1
-#endif
 template <int D, bool WQK, bool PAIR, int VAR = 0>
-__global__ __launch_bounds__(ATT_WAVES * 64, JODO_X_ATT_SPLIT_OCC(VAR)) void k_edge_attn(KArgs A) {
+__global__ __launch_bounds__(ATT_WAVES * 64, 1) void k_edge_attn(KArgs A) {
     using X = AttnT<D, WQK, VAR>;
     const bool asym = A.flags[FLAG_ASYM] != 0;
     if (PAIR ? asym : !(asym || A.pd.ad_big[blockIdx.x])) return;

@@ -234,11 +234,8 @@ struct ArgsC {
     float *xh, *rs, *u, *c0pre, *c0a, *inv;
 };
 
-#ifndef JODO_X_CHAINC_OCC                                              // experiment builds: waves per SIMD the compiler must leave room for
-#define JODO_X_CHAINC_OCC 1
-#endif
 template <int D>
-__global__ __launch_bounds__(64, JODO_X_CHAINC_OCC) void k_chain_c(ArgsC A) {
+__global__ __launch_bounds__(64, 1) void k_chain_c(ArgsC A) {
     using X = FD<D>;
     const int lane = threadIdx.x & 63, j = lane & 31, half = lane >> 5;
     const long r = (long)blockIdx.x * 32 + j;

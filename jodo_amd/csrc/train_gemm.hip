@@ -292,9 +292,6 @@ static void launch(hipStream_t s, int tA, int tB, dim3 grid, int M, int N, int K
 
 static bool gemm_fast(int tA, int tB, int M, int N, int K, int vecA, int vecB) {
     const bool kc = !tA || tB;                               // some operand is k-contiguous
-#ifdef JODO_X_GEMM_NO_RAGGED                                  // experiment builds: the round-4 rule (whole K tiles only)
-    if (K % TK) return false;
-#endif
     return vecA && vecB && K >= 4 && (!kc || (K % 4) == 0) && (tA ? (M % 4) == 0 && M >= 4 : M >= 1) && (tB ? N >= 1 : (N % 4) == 0 && N >= 4);
 }
 static FILE* shape_log() {
