@@ -206,7 +206,13 @@ enum jodo_plan_option {
                                    * last bits; the default and every headline number stay exact fp32.  Ignored when a precondition fails.
                                    * 2 (experiments): also the fused attention kernel (k_edge_attn variants 4 + 5: two launches that share every
                                    * item by heads; nf 256 tuned set, plans without molecules above an attention group) — parity-tested, measured
-                                   * 15 % SLOWER than the fp32 kernel on MI355X (513 against 447 us per block at QM9 B = 2500), DESIGN.md 4i */
+                                   * 15 % SLOWER than the fp32 kernel on MI355X (513 against 447 us per block at QM9 B = 2500), DESIGN.md 4i.
+                                   * CONDITIONAL models (cond_ch > 0, nf 256): >= 1 runs the UN-FOLDED pair update in the split form
+                                   * (k_edge_update_sym_split_cond, csrc/dgt_kernels_split_cond.h; per-molecule modulation rows, so nothing folds
+                                   * or rotates and per-molecule noise levels are legal input).  Preconditions: the conditional tape handed over
+                                   * (jodo_dgt_pack_split_cond_host -> jodo_plan_set_split_weights), JODO_OPT_PIN_SYMMETRIC = 1,
+                                   * JODO_OPT_PIN_UNIFORM_T = 2, one circulant offset per pair item; node and attention kernels stay exact fp32,
+                                   * so 2 means the same as 1.  Ignored when a precondition fails. */
     JODO_OPT_COUNT
 };
 int jodo_plan_set_option(jodo_plan* plan, int option, int value);
@@ -423,6 +429,13 @@ int jodo_debug_mfma_valu(int iters, int nv, int nt, int waves_per_simd, float* s
 int jodo_dgt_split_size(const jodo_cfg* cfg, size_t* total_bytes, size_t* pair_block_bytes, size_t* node_block_bytes, size_t* attn_block_bytes);
 int jodo_dgt_pack_split_host(const jodo_cfg* cfg, const jodo_tensor* tensors, int n_tensors, void* host, size_t cap_bytes);
 int jodo_plan_set_split_weights(jodo_plan* plan, const void* tape_dev, size_t bytes);
+/* The CONDITIONAL model's tape (cond_ch > 0, nf 256; k_edge_update_sym_split_cond, csrc/dgt_kernels_split_cond.h): a pair tape only — per
+ *   block the edge FFN and the readout as above, then input_lin's [e ; G] columns (8 output blocks x 8 K16 steps) and coord_mlp.0
+ *   (8 x 16): every weight of the un-folded pair update is static, so nothing comes from the workspace.  228 steps of 3 KiB per block at
+ *   mlp_ratio 2, 260 at 4; layout of the buffer: L pair tapes.  JODO_ERR_UNSUPPORTED unless nf = 256 and cond_ch > 0 (jodo_dgt_split_size /
+ *   jodo_dgt_pack_split_host keep refusing conditional configurations).  jodo_plan_set_split_weights takes this tape for a conditional plan. */
+int jodo_dgt_split_cond_size(const jodo_cfg* cfg, size_t* total_bytes, size_t* pair_block_bytes);
+int jodo_dgt_pack_split_cond_host(const jodo_cfg* cfg, const jodo_tensor* tensors, int n_tensors, void* host, size_t cap_bytes);
 
 /* ---- gate experiments of the opt-in split-bf16 (three-term, fp32-equivalent) MFMA form (csrc/dgt_split.{h,hip}; no reference
  * counterpart; measurement helpers, never on the data path) ----

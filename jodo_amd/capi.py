@@ -95,7 +95,8 @@ def pack_weights(cfg_struct, state_dict, device=None):
 
 def pack_split_tape(cfg_struct, state_dict, device=None):
     """The static weight tape of the OPT-IN split-bf16 pair update (jodo_dgt_pack_split_host; JODO_OPT_SPLIT_BF16): a uint8 tensor
-    (CPU, or uploaded to `device`).  Raises JodoHipError for configurations the split form is not built for (nf != 256, conditional)."""
+    (CPU, or uploaded to `device`).  Raises JodoHipError for configurations this tape is not built for (nf not 256 / 384; conditional
+    models have a tape of their own, pack_split_cond_tape)."""
     import numpy as np
     import torch
     L = lib()
@@ -112,4 +113,26 @@ def pack_split_tape(cfg_struct, state_dict, device=None):
     tape = torch.empty(total.value, dtype=torch.uint8)
     check(L.jodo_dgt_pack_split_host(ctypes.byref(cfg_struct), arr, len(keep), ctypes.c_void_p(tape.data_ptr()), ctypes.c_size_t(total.value)),
           'jodo_dgt_pack_split_host')
+    return tape if device is None else tape.to(device)
+
+
+def pack_split_cond_tape(cfg_struct, state_dict, device=None):
+    """The conditional model's tape of the OPT-IN split-bf16 pair update (jodo_dgt_pack_split_cond_host; cond_DGT_concat at nf 256 under
+    JODO_OPT_SPLIT_BF16): per block the edge FFN, the readout, input_lin's [e ; G] columns and coord_mlp.0 in the un-folded kernel's
+    consumption order, a uint8 tensor (CPU, or uploaded to `device`).  Raises JodoHipError for unconditional models and nf != 256."""
+    import numpy as np
+    import torch
+    L = lib()
+    keep, arr = [], (JodoTensor * len(state_dict))()
+    for i, (k, v) in enumerate(state_dict.items()):
+        t = np.ascontiguousarray(v.detach().float().cpu().numpy())
+        shp = (ctypes.c_int64 * max(t.ndim, 1))(*t.shape)
+        name = k.encode()
+        keep.append((t, shp, name))
+        arr[i] = JodoTensor(name, t.ctypes.data_as(ctypes.c_void_p), shp, t.ndim)
+    total, per_block = ctypes.c_size_t(), ctypes.c_size_t()
+    check(L.jodo_dgt_split_cond_size(ctypes.byref(cfg_struct), ctypes.byref(total), ctypes.byref(per_block)), 'jodo_dgt_split_cond_size')
+    tape = torch.empty(total.value, dtype=torch.uint8)
+    check(L.jodo_dgt_pack_split_cond_host(ctypes.byref(cfg_struct), arr, len(keep), ctypes.c_void_p(tape.data_ptr()), ctypes.c_size_t(total.value)),
+          'jodo_dgt_pack_split_cond_host')
     return tape if device is None else tape.to(device)

@@ -2,6 +2,7 @@
 #include "dgt_kernels_attn.h"
 #include "dgt_kernels_wide.h"
 #include "dgt_kernels_split.h"
+#include "dgt_kernels_split_cond.h"
 #include "dgt_launch.h"
 
 using namespace jd;
@@ -47,7 +48,18 @@ int launch_update_sym(jodo_plan* p, hipStream_t st, KArgs& A) {
     A.item0 = 0; A.dir_split = 0;
     // JODO_OPT_PIN_UNIFORM_T: 1 = every call shares one modulation row (only the folded variant is launched), 2 = never
     const bool run_plain = p->opt[JODO_OPT_PIN_UNIFORM_T] != 1, run_fold = p->opt[JODO_OPT_PIN_UNIFORM_T] != 2 && d.cond_ch == 0;
-    if (run_plain && n1 > 0) {
+    // opt-in split-bf16 form of the un-folded update (conditional model; jodo_dgt_forward checked the preconditions — both pins among them —
+    // and set A.split_cond / A.wsplit): ONE launch over all items, four per workgroup, instead of the full rounds + the four-wave remainder
+    bool split_cond_ran = false;
+    if constexpr (D == 256) {
+        if (run_plain && !run_fold && A.split_cond && A.wsplit && n1 > 0) {
+            const int wgs = (p->n_pitems + 31) / 32 * 8;
+            if (d.r == 2) hipLaunchKernelGGL((split::k_edge_update_sym_split_cond<D, 2>), dim3(wgs), dim3(split::SPLIT_WAVES * 64), 0, st, A);
+            else hipLaunchKernelGGL((split::k_edge_update_sym_split_cond<D, 4>), dim3(wgs), dim3(split::SPLIT_WAVES * 64), 0, st, A);
+            split_cond_ran = true;
+        }
+    }
+    if (run_plain && n1 > 0 && !split_cond_ran) {
         if constexpr (D == 256) { if (d.r == 2) launch_sym_variant<D, 2, false, false>(st, A, n1, zw); else launch_sym_variant<D, 4, false, false>(st, A, n1, zw); }
         else { if (d.r == 2) LAUNCH((wide::k_edge_update_sym<D, 2>), n1, 64, A); else LAUNCH((wide::k_edge_update_sym<D, 4>), n1, 64, A); }
     }

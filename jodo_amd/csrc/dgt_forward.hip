@@ -54,7 +54,7 @@ void fill_ws(KArgs& A, const jodo_plan* p, void* ws) {
     A.ehid = ws_ptr<float>(ws, w.ehid); A.epred = ws_ptr<float>(ws, w.epred);
     A.e_out = ws_ptr<float>(ws, w.e2);
     A.dposE = ws_ptr<float>(ws, w.dposE); A.gramE = ws_ptr<float>(ws, w.gramE);
-    A.wsplit = nullptr; A.wsplit_node = nullptr; A.wsplit_attn = nullptr; A.mfold_s = nullptr; A.ffold_s = nullptr;      // the opt-in split-bf16 kernels: decided per forward (jodo_dgt_forward)
+    A.wsplit = nullptr; A.wsplit_node = nullptr; A.wsplit_attn = nullptr; A.mfold_s = nullptr; A.ffold_s = nullptr; A.split_cond = 0;      // the opt-in split-bf16 kernels: decided per forward (jodo_dgt_forward)
 }
 
 int rowgemm(hipStream_t st, const float* X, int64_t ldx, float* Y, int64_t ldy, const float* Wp, const float* bias,
@@ -309,6 +309,10 @@ int forward_blocks(jodo_plan* p, hipStream_t st, KArgs& A, const int64_t* woff, 
             A.wsplit = reinterpret_cast<const unsigned short*>(base + (size_t)l * pair_block);
             if (node_block > 0) A.wsplit_node = reinterpret_cast<const unsigned short*>(base + (size_t)d.L * pair_block + (size_t)l * node_block);
             if (attn_block > 0 && p->opt[JODO_OPT_SPLIT_BF16] == 2) A.wsplit_attn = reinterpret_cast<const unsigned short*>(base + (size_t)d.L * (pair_block + node_block) + (size_t)l * attn_block);
+        } else if (A.split_cond) {                 // conditional model: a pair tape only (node and attention kernels stay exact)
+            size_t total = 0, pair_block = 0;
+            (void)jodo_dgt_split_cond_size(&p->cfg, &total, &pair_block);
+            A.wsplit = reinterpret_cast<const unsigned short*>(static_cast<const char*>(p->split_w) + (size_t)l * pair_block);
         }
         A.pos_in = posbuf[cur]; A.pos_out = posbuf[cur ^ 1];
         {
@@ -459,6 +463,14 @@ extern "C" int jodo_dgt_forward(jodo_plan* p, const void* desc_dev, const float*
         if (jodo_dgt_split_size(&p->cfg, &total, &per_block, &node_block, &attn_block) == JODO_OK && total == p->split_bytes)
             A.mfold_s = ws_ptr<unsigned short>(workspace, p->ws.mfold_s);
         if (A.mfold_s && node_block > 0) A.ffold_s = ws_ptr<unsigned short>(workspace, p->ws.ffold_s);   // tuned nf 256 set: k_node_ab_split
+    }
+    // The conditional model (per-molecule modulation rows: nothing folds, nothing rotates): the un-folded pair update in the split form,
+    // k_edge_update_sym_split_cond.  nf 256, symmetric inputs pinned, the shared-row pin set to "never" (2), one circulant offset per
+    // item, the conditional tape handed over; per-molecule noise levels are legal input.  Option value 2 means the same as 1 here.
+    if (p->opt[JODO_OPT_SPLIT_BF16] >= 1 && p->split_w && d.D == 256 && d.cond_ch > 0 && !p->force_directed && p->n_pitems > 0 && p->pitems_single &&
+        p->opt[JODO_OPT_PIN_SYMMETRIC] == 1 && p->opt[JODO_OPT_PIN_UNIFORM_T] == 2) {
+        size_t total = 0, per_block = 0;
+        if (jodo_dgt_split_cond_size(&p->cfg, &total, &per_block) == JODO_OK && total == p->split_bytes) A.split_cond = 1;
     }
     float* posbuf[2] = {ws_ptr<float>(workspace, p->ws.pos0), ws_ptr<float>(workspace, p->ws.pos1)};
     A.pos_in = posbuf[0]; A.pos_out = posbuf[1];

@@ -43,6 +43,8 @@ struct KArgs {
     const unsigned short* wsplit_node;    // the same for the node kernel of the tuned nf 256 set (k_node_post_split), NULL = off
     unsigned short* mfold_s;
     unsigned short* ffold_s;              // split image of ffold (the rotated per-node factor F of every block): k_node_ab_split
+    int split_cond;                       // 1: conditional model, the un-folded split pair update runs this forward (k_edge_update_sym_split_cond;
+                                          // wsplit = the current block's tape, no workspace image, node and attention kernels exact)
     int* flags;
     unsigned long long* dbgt;             // debug: per-phase cycle sums (builds with -DJODO_PHASE_TIMING only)
     // API tensors

@@ -699,3 +699,84 @@ extern "C" int jodo_dgt_pack_split_host(const jodo_cfg* cfg, const jodo_tensor* 
     std::memcpy(host, tape.data(), tape.size() * sizeof(uint16_t));
     return JODO_OK;
 }
+
+// ---- the CONDITIONAL model's pair tape (cond_DGT_concat, nf 256; csrc/dgt_kernels_split_cond.h) ----
+// Per-molecule modulation rows: nothing folds and nothing rotates, so every weight of the un-folded pair update is static and a block is
+// ONE tape, in the order k_edge_update_sym_split_cond consumes it:
+//   for every hidden chunk c of 64:  ff_linear3 output blocks 2c, 2c + 1 (De / 16 steps each), then ff_linear4 output blocks
+//                                    0 .. De / 32 - 1, their steps 4c .. 4c + 3                      (as the unconditional tape)
+//   the readout edge_l (De / 16 steps)
+//   input_lin's [e ; G] columns: output blocks 0 .. D / 32 - 1, 2 De / 16 steps each                 (S = W_in [e ; G])
+//   coord_mlp.0: output blocks 0 .. D / 32 - 1, D / 16 steps each                                    (Z = W0 (S (1 + sc)))
+// 228 steps per block at mlp_ratio 2, 260 at 4 (both multiples of the kernel's four-step chunk).  No node or attention tape: those kernels
+// stay exact fp32 for the conditional model.
+static int split_cond_tape_steps(const DgtDims& d) {
+    const int NCH = d.r * d.De / 64, NSE = d.De / 16, NE = d.De / 32, ND = d.D / 32;
+    return NCH * (2 * NSE + NE * 4) + NSE + ND * (2 * d.De / 16) + ND * (d.D / 16);
+}
+static int split_cond_check(const DgtDims& d) {
+    if (d.D != 256 || d.cond_ch <= 0)
+        return jodo_set_error(JODO_ERR_UNSUPPORTED, "split-bf16 form, conditional tape: built for nf = 256 conditional models (got nf %d, cond_ch %d)", d.D, d.cond_ch);
+    return JODO_OK;
+}
+extern "C" int jodo_dgt_split_cond_size(const jodo_cfg* cfg, size_t* total_bytes, size_t* pair_block_bytes) {
+    if (!cfg || !total_bytes || !pair_block_bytes) return jodo_set_error(JODO_ERR_ARG, "split_cond_size: null argument");
+    DgtDims d;
+    int rc = dgt_dims_from_cfg(cfg, &d);
+    if (rc != JODO_OK) return rc;
+    if ((rc = split_cond_check(d)) != JODO_OK) return rc;
+    *pair_block_bytes = (size_t)split_cond_tape_steps(d) * 3072;
+    *total_bytes = *pair_block_bytes * d.L;
+    return JODO_OK;
+}
+extern "C" int jodo_dgt_pack_split_cond_host(const jodo_cfg* cfg, const jodo_tensor* tensors, int n_tensors, void* host, size_t cap_bytes) {
+    if (!cfg || !tensors || !host) return jodo_set_error(JODO_ERR_ARG, "pack_split_cond: null argument");
+    DgtDims d;
+    int rc = dgt_dims_from_cfg(cfg, &d);
+    if (rc != JODO_OK) return rc;
+    if ((rc = split_cond_check(d)) != JODO_OK) return rc;
+    const int D = d.D, De = d.De, L = d.L, r = d.r, ce = (2 * De) / L, KIN = 2 * D + 2 * De;
+    Lookup lk;
+    for (int i = 0; i < n_tensors; ++i) {
+        if (!tensors[i].name || !tensors[i].data) return jodo_set_error(JODO_ERR_ARG, "pack_split_cond: tensor %d has a null field", i);
+        std::string nm(tensors[i].name);
+        if (nm.rfind("module.", 0) == 0) nm = nm.substr(7);
+        lk.m[nm] = &tensors[i];
+    }
+    const int NCH = r * De / 64, NSE = De / 16, NE = De / 32, ND = D / 32, NS4 = r * De / 16, NSZ = 2 * De / 16, NSD = D / 16;
+    constexpr size_t STEP = 3 * 64 * 8;                 // uint16 per (block, step)
+    const size_t per_block = (size_t)split_cond_tape_steps(d) * STEP;
+    if (per_block * L * sizeof(uint16_t) > cap_bytes) return jodo_set_error(JODO_ERR_ARG, "pack_split_cond: buffer of %zu bytes, need %zu", cap_bytes, per_block * L * sizeof(uint16_t));
+    std::vector<uint16_t> tape;
+    tape.reserve(per_block * L);
+    auto slice = [&](const std::vector<uint16_t>& p, int ns, int blk, int s0, int s1) {      // steps [s0, s1) of output block blk
+        const uint16_t* src = p.data() + ((size_t)blk * ns + s0) * STEP;
+        tape.insert(tape.end(), src, src + (size_t)(s1 - s0) * STEP);
+    };
+    for (int l = 0; l < L; ++l) {
+        const std::string b = "e_block_" + std::to_string(l);
+        const float* w3 = lk.get(b + ".ff_linear3.weight", (int64_t)r * De * De);
+        const float* w4 = lk.get(b + ".ff_linear4.weight", (int64_t)De * r * De);
+        const float* wro = lk.get("edge_" + std::to_string(l) + ".weight", (int64_t)ce * De);
+        const float* win = lk.get(b + ".equi_update.input_lin.weight", (int64_t)D * KIN);
+        const float* w0 = lk.get(b + ".equi_update.coord_mlp.0.weight", (int64_t)D * D);
+        if (!w3 || !w4 || !wro || !win || !w0) return jodo_set_error(JODO_ERR_ARG, "pack_split_cond: missing or mis-sized tensor '%s'", lk.missing.c_str());
+        const std::vector<uint16_t> p3 = pack_proj_split(w3, De, nat_in(De), nat_out(r * De));
+        const std::vector<uint16_t> p4 = pack_proj_split(w4, (int64_t)r * De, nat_in(r * De), nat_out(De));
+        const std::vector<uint16_t> pro = pack_proj_split(wro, De, nat_in(De), nat_out(32, ce));
+        // input_lin [D, 2D + De + De] = h_row | h_col | e | G: the [e ; G] columns, as the f32 packing of JB_INE_W takes them
+        const std::vector<uint16_t> pin = pack_proj_split(win, KIN, cat(nat_in(De, 2 * D), nat_in(De, 2 * D + De)), nat_out(D));
+        const std::vector<uint16_t> p0 = pack_proj_split(w0, D, nat_in(D), nat_out(D));
+        for (int c = 0; c < NCH; ++c) {
+            slice(p3, NSE, 2 * c, 0, NSE);
+            slice(p3, NSE, 2 * c + 1, 0, NSE);
+            for (int ob = 0; ob < NE; ++ob) slice(p4, NS4, ob, 4 * c, 4 * c + 4);
+        }
+        slice(pro, NSE, 0, 0, NSE);
+        for (int blk = 0; blk < ND; ++blk) slice(pin, NSZ, blk, 0, NSZ);
+        for (int blk = 0; blk < ND; ++blk) slice(p0, NSD, blk, 0, NSD);
+    }
+    if (tape.size() != per_block * L) return jodo_set_error(JODO_ERR_ARG, "pack_split_cond: internal tape size");
+    std::memcpy(host, tape.data(), tape.size() * sizeof(uint16_t));
+    return JODO_OK;
+}

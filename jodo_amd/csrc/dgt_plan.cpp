@@ -628,7 +628,9 @@ extern "C" int jodo_plan_set_split_weights(jodo_plan* p, const void* tape_dev, s
     if (!p) return jodo_set_error(JODO_ERR_ARG, "null plan");
     if (tape_dev) {
         size_t total = 0, per_block = 0, node_block = 0, attn_block = 0;
-        const int rc = jodo_dgt_split_size(&p->cfg, &total, &per_block, &node_block, &attn_block);
+        // (a conditional plan takes the conditional tape: jodo_dgt_pack_split_cond_host)
+        const int rc = p->dims.cond_ch > 0 ? jodo_dgt_split_cond_size(&p->cfg, &total, &per_block)
+                                           : jodo_dgt_split_size(&p->cfg, &total, &per_block, &node_block, &attn_block);
         if (rc != JODO_OK) return rc;
         if (bytes != total) return jodo_set_error(JODO_ERR_ARG, "set_split_weights: %zu bytes, this configuration's tape has %zu", bytes, total);
     }

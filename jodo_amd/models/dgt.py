@@ -169,10 +169,11 @@ class _DGTBase(nn.Module):
         self.last_flags = None        # device int32[8] of the last call (NaN guard etc.)
         self.warn_nan = True
         # OPT-IN (default off): under pinned paths (pin_paths: what the samplers do after a round's first self-conditioned evaluation)
-        # the folded pair update runs its projections in the split-bf16 form — three bf16 terms per operand, six bf16 MFMAs per K = 16
+        # the pair update runs its projections in the split-bf16 form — three bf16 terms per operand, six bf16 MFMAs per K = 16
         # step, fp32 accumulation: fp32-equivalent arithmetic, not bit-identical to the default (csrc/dgt_kernels_split.h,
-        # JODO_OPT_SPLIT_BF16).  nf 256 (pair update + node kernel) and nf 384 (pair update) unconditional models; ignored elsewhere.  The default path and every headline number
-        # stay exact fp32.
+        # JODO_OPT_SPLIT_BF16).  Unconditional models: nf 256 (folded pair update + node kernel) and nf 384 (folded pair update) under a
+        # shared noise level.  The conditional model at nf 256: the un-folded pair update (csrc/dgt_kernels_split_cond.h; per-molecule
+        # noise levels allowed).  Ignored elsewhere (nf 128, asymmetric inputs).  The default path and every headline number stay exact fp32.
         self.split_bf16 = False       # True: pair update + node kernel; 'attention': also the attention kernel (experiments: measured slower)
         self._split_tape = None       # (pack generation, device uint8 tensor): the split form's static weight tape
 
@@ -524,7 +525,9 @@ class _DGTBase(nn.Module):
             capi.check(L.jodo_plan_set_option(plan['handle'], 4, 2 if f[4] else 1), 'jodo_plan_set_option')
             capi.check(L.jodo_plan_set_option(plan['handle'], 5, 1 if f[2] else 2), 'jodo_plan_set_option')
             plan['pinned'] = True
-            if self.split_bf16 and self.dims.D in (256, 384) and not self.conditional and not f[4] and f[2]:
+            # unconditional: the folded kernels (need the shared modulation row, f[2]); conditional: the un-folded kernel (nf 256, any rows)
+            fits = (self.dims.D == 256) if self.conditional else (self.dims.D in (256, 384) and f[2])
+            if self.split_bf16 and fits and not f[4]:
                 self._hand_over_split(plan)
                 capi.check(L.jodo_plan_set_option(plan['handle'], 13, 2 if self.split_bf16 == 'attention' else 1), 'jodo_plan_set_option')
 
@@ -548,7 +551,8 @@ class _DGTBase(nn.Module):
         self._weights(device)
         gen = self._pack_gen
         if self._split_tape is None or self._split_tape[0] != gen:
-            self._split_tape = (gen, capi.pack_split_tape(self._cfg(), self.state_dict(), device))
+            pack = capi.pack_split_cond_tape if self.conditional else capi.pack_split_tape
+            self._split_tape = (gen, pack(self._cfg(), self.state_dict(), device))
         return self._split_tape[1]
 
     def unpin_paths(self):
