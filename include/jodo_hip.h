@@ -403,6 +403,58 @@ int jodo_gradnorm_clip(const float* norm_dev, double* state_dev, double max_grad
  *   check synchronises the host with the device (the last synchronisation of a training step). */
 int jodo_kabsch_rotations(int B, const float* A_dev, float* R_dev, void* stream);
 
+/* ---- the 2-D model: DGT_concat_2D (models/mol_gnn.py:797-946, blocks :325-407, TransMixLayer with ONE adjacency head) -------------
+ * No positions, no batch-global operation.  Supported: nf 256, 16 heads of which 1 adjacency head (15 learned heads of 17 channels),
+ * mlp_ratio 2, n_layers 8, time_dim 4 nf, in_node_dim <= 16, edge_ch in {2, 3}; anything else -> JODO_ERR_UNSUPPORTED.
+ * The state_dict (235 tensors) is packed by name like the 3-D one (a leading "module." is accepted; a missing or mis-sized tensor is
+ * JODO_ERR_ARG with its name in jodo_last_error()).  Slot tables below: offsets in floats into the packed blob.
+ *   "tiled" weights: [out block of 32][K chunk of 64][8 quads][64 lanes][4] in MFMA A-operand order, see csrc/dgt2d_pack.cpp. */
+typedef struct {
+    int32_t nf, n_layers, n_heads, n_extra, mlp_ratio, in_node_dim, edge_ch;
+    float edge_quan_th;
+} jodo_cfg2d;
+enum jodo2d_wslot_global {
+    J2_TIME_FREQ = 0, J2_TIME_W1, J2_TIME_B1, J2_TIME_W3, J2_TIME_B3, J2_MOD_W, J2_MOD_B,
+    J2_NODE_EMB_W, J2_NODE_EMB_B, J2_EDGE_EMB_W, J2_EDGE_EMB_B,
+    J2_NH1_W, J2_NH1_B, J2_NH2_W, J2_NH2_B, J2_NH3_W, J2_NH3_B,
+    J2_EH1_W, J2_EH1_B, J2_EH2_W, J2_EH2_B, J2_EH3_W, J2_EH3_B,
+    J2_GLOBAL_COUNT
+};
+enum jodo2d_wslot_block {
+    J2B_QKV_W = 0, J2B_QKV_B, J2B_LE_W, J2B_N2E_W, J2B_N2E_B, J2B_FF1_W, J2B_FF1_B, J2B_FF2_W, J2B_FF2_B,
+    J2B_FF3_W, J2B_FF3_B, J2B_FF4_W, J2B_FF4_B, J2B_NRO_W, J2B_NRO_B, J2B_ERO_W, J2B_ERO_B,
+    J2B_BLOCK_COUNT
+};
+/* JODO_OK, or JODO_ERR_UNSUPPORTED naming the setting outside the supported set */
+int jodo_dgt2d_check_cfg(const jodo_cfg2d* cfg);
+int jodo_dgt2d_packed_size(const jodo_cfg2d* cfg, size_t* n_floats, int* n_woff);
+int jodo_dgt2d_pack_weights_host(const jodo_cfg2d* cfg, const jodo_tensor* tensors, int n_tensors, float* packed_host,
+                                 size_t cap_floats, int64_t* woff_out, int n_woff);
+/* Batch layout: B molecules with n_nodes[b] atoms (prefix masks, diagonal excluded), padded width N <= 64 of the dense tensors.
+ * jodo_dgt2d_layout: sizes for the caller's buffers — out[0] = int32 words of the descriptor, out[1] = workspace bytes,
+ * out[2] = real atoms Nn, out[3] = rows of the edge state (sum n^2), out[4] / out[5] = byte offsets of h [Nn, nf] and of the edge
+ * state [rows, nf / 4] in the workspace (tests read them after a forward that stopped after `max_blocks` blocks; row of (b, r, c) =
+ * eoff_b + r n_b + c, with only r < c rows live when the inputs were symmetric), out[6] = unordered pairs, out[7] = reserved.
+ * jodo_dgt2d_fill_desc writes the descriptor into HOST memory; the caller copies it to the device. */
+int jodo_dgt2d_layout(const jodo_cfg2d* cfg, int B, int N, const int32_t* n_nodes_host, int64_t* out8);
+int jodo_dgt2d_fill_desc(const jodo_cfg2d* cfg, int B, int N, const int32_t* n_nodes_host, int32_t* desc_host, int64_t n_words);
+/* One evaluation.  xh [B,N,nd], edge_x [B,N,N,ch], cond_x / cond_edge_x both given or both NULL (first step: all-ones adjacency
+ * head), noise_level [B] -> out_xh [B,N,nd], out_edge [B,N,N,ch], written fully (zeros on padding and the diagonal).
+ * flags_dev int32[8]: [0] = 1 when edge_x and cond_edge_x are symmetric (one pair-update / head evaluation per unordered pair),
+ * 0 -> directed fallback; [1] = 1 when all noise levels are equal (one shared modulation row).  force_directed != 0: always the
+ * directed fallback (tests).  max_blocks < 0: all blocks. */
+int jodo_dgt2d_forward(const jodo_cfg2d* cfg, int B, int N, const int32_t* n_nodes_host, const void* desc_dev, const float* packed_w,
+                       const int64_t* woff, int n_woff, const float* xh, const float* edge_x, const float* cond_x,
+                       const float* cond_edge_x, const float* noise_level, float* out_xh, float* out_edge, int32_t* flags_dev,
+                       void* workspace, int force_directed, int max_blocks, void* stream);
+/* Ancestral update of the 2-D sampler (sampling.py:637-658) for a node tensor WITHOUT position channels, replayed-draw form:
+ * x_mean = cx x + cp pred, x_next = x_mean + sigma eps_node masked to the real atoms (all node channels are plain masked noise);
+ * the edge tensors likewise with eps_edge [B,N,N,ch] read from its strict lower triangle for both orientations of a pair (the
+ * triangle sample_symmetric_edge_feature_noise mirrors), masked to real pairs.  All outputs are written fully. */
+int jodo_sampler_step_2d(int B, int N, int node_feats, int edge_ch, const int32_t* n_nodes_dev, float cx, float cp, float sigma,
+                         const float* x, const float* edge_x, const float* pred, const float* edge_pred, const float* eps_node,
+                         const float* eps_edge, float* x_next, float* edge_next, float* x_mean, float* edge_mean, void* stream);
+
 const char* jodo_last_error(void);
 
 /* measurement helper (synchronises, default stream): fp32 MFMA throughput of the box in TFLOP/s from a

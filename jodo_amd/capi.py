@@ -93,6 +93,28 @@ def pack_weights(cfg_struct, state_dict, device=None):
     return blob, woff, n_woff.value
 
 
+def pack_weights_2d(cfg_struct, state_dict, device=None):
+    """The 2-D model's state_dict -> (blob, woff ctypes int64 array, n_woff) through jodo_dgt2d_pack_weights_host; device=None keeps
+    the blob on the CPU, otherwise it is copied to `device`."""
+    import numpy as np
+    import torch
+    L = lib()
+    keep, arr = [], (JodoTensor * len(state_dict))()
+    for i, (k, v) in enumerate(state_dict.items()):
+        t = np.ascontiguousarray(v.detach().float().cpu().numpy())
+        shp = (ctypes.c_int64 * max(t.ndim, 1))(*t.shape)
+        name = k.encode()
+        keep.append((t, shp, name))
+        arr[i] = JodoTensor(name, t.ctypes.data_as(ctypes.c_void_p), shp, t.ndim)
+    n_floats, n_woff = ctypes.c_size_t(), ctypes.c_int()
+    check(L.jodo_dgt2d_packed_size(ctypes.byref(cfg_struct), ctypes.byref(n_floats), ctypes.byref(n_woff)), 'jodo_dgt2d_packed_size')
+    woff = (ctypes.c_int64 * n_woff.value)()
+    blob = torch.empty(n_floats.value, dtype=torch.float32)
+    check(L.jodo_dgt2d_pack_weights_host(ctypes.byref(cfg_struct), arr, len(keep), ctypes.c_void_p(blob.data_ptr()),
+                                         ctypes.c_size_t(n_floats.value), woff, n_woff.value), 'jodo_dgt2d_pack_weights_host')
+    return (blob if device is None else blob.to(device)), woff, n_woff.value
+
+
 def pack_split_tape(cfg_struct, state_dict, device=None):
     """The static weight tape of the OPT-IN split-bf16 pair update (jodo_dgt_pack_split_host; JODO_OPT_SPLIT_BF16): a uint8 tensor
     (CPU, or uploaded to `device`).  Raises JodoHipError for configurations this tape is not built for (nf not 256 / 384; conditional

@@ -1,0 +1,702 @@
+// jodo_dgt2d_forward: one evaluation of the 2-D score network DGT_concat_2D (include/jodo_hip.h), and the 2-D sampler update.
+//
+// Layout.  Real atoms are compact: node row = noff_b + i.  The edge state lives in memory between blocks as rows of De = 64 floats,
+// row(b, r, c) = eoff_b + r n_b + c (n_b^2 rows per molecule).  With symmetric inputs (device flag 0) only the rows r < c are live:
+// embedding, pair update, readout and heads run once per unordered pair, and the attention kernel reads row (min, max).  With
+// asymmetric inputs every ordered pair is its own row (directed fallback, twice the pair work).
+//
+// Per block:  k2d_ln_mod (LN1 + modulate) -> k2d_gemm (q | k | v) -> k2d_attn -> k2d_gemm (node2edge) -> k2d_ln_mod (residual, LN2,
+// modulate) -> k2d_gemm x 2 (node FFN) -> k2d_gemm (node readout) -> k2d_pair (edge residual, LN, FFN, readout).
+// Every projection is exact fp32 on v_mfma_f32_32x32x2_f32 in the strip model of dgt_device.h (32 items per wave, weights as A operand,
+// packed by csrc/dgt2d_pack.cpp).  The two per-edge kernels are persistent: a workgroup of four waves copies the block's weights
+// (128 KiB lin_edge0 | lin_edge1; 72 KiB edge FFN + readout) into LDS once and its waves then walk over the items.
+#include "dgt_device.h"
+#include "jodo_hip_internal.h"
+#include "../../include/jodo_hip.h"
+
+using namespace jd;
+
+extern "C" int jodo_dgt2d_check_cfg(const jodo_cfg2d* cfg);
+
+namespace {
+
+constexpr int D2 = 256, DE = 64, T2 = 1024, L2 = 8, MODB = 6 * D2 + 6 * DE, MODW = L2 * MODB, EHW = DE + L2 * 16, NHW = D2 + L2 * 64;
+
+#define L2D(kern, grid, block, ...)                                               \
+    do {                                                                          \
+        auto kf_ = kern;                                                          \
+        hipLaunchKernelGGL(kf_, dim3(grid), dim3(block), 0, st, __VA_ARGS__);     \
+        int rc_ = jodo_check_launch(#kern);                                       \
+        if (rc_ != JODO_OK) return rc_;                                           \
+    } while (0)
+
+struct Lay {                     // sizes and workspace offsets (in floats)
+    int B, N, Nn, P;
+    int64_t R;
+    size_t hid1, tembs, mods, h, hm, qkv, hn, u, f1, ahid, nh1, nh2, nh3, e, ehid, total;
+    int off_n, off_noff, off_eoff, off_node, off_pair, words;
+};
+
+int make_lay(int B, int N, const int32_t* n, Lay* o) {
+    if (B <= 0 || N <= 0 || !n) return jodo_set_error(JODO_ERR_ARG, "dgt2d: bad batch");
+    if (N > 64) return jodo_set_error(JODO_ERR_UNSUPPORTED, "dgt2d: padded width %d above 64", N);
+    if (B >= (1 << 19)) return jodo_set_error(JODO_ERR_UNSUPPORTED, "dgt2d: batch %d too large", B);
+    int64_t Nn = 0, R = 0, P = 0;
+    for (int b = 0; b < B; ++b) {
+        if (n[b] < 1 || n[b] > N) return jodo_set_error(JODO_ERR_ARG, "dgt2d: n_nodes[%d]=%d outside [1,%d]", b, n[b], N);
+        Nn += n[b]; R += (int64_t)n[b] * n[b]; P += (int64_t)n[b] * (n[b] - 1) / 2;
+    }
+    if (R >= ((int64_t)1 << 30) / 48) return jodo_set_error(JODO_ERR_UNSUPPORTED, "dgt2d: batch too large (%lld edge rows)", (long long)R);
+    o->B = B; o->N = N; o->Nn = (int)Nn; o->P = (int)P; o->R = R;
+    const size_t Bp = (size_t)(B + 63) / 64 * 64, Np = (size_t)(Nn + 63) / 64 * 64, Rp = (size_t)(R + 63) / 64 * 64;
+    size_t at = 0;
+    auto take = [&](size_t cnt) { size_t a = at; at += (cnt + 63) / 64 * 64; return a; };
+    o->hid1 = take(Bp * T2); o->tembs = take(Bp * T2); o->mods = take(Bp * MODW);
+    o->h = take(Np * D2); o->hm = take(Np * D2); o->qkv = take(Np * 3 * D2); o->hn = take(Np * D2); o->u = take(Np * DE);
+    o->f1 = take(Np * 2 * D2); o->ahid = take(Np * NHW); o->nh1 = take(Np * D2); o->nh2 = take(Np * (D2 / 2)); o->nh3 = take(Np * 32);
+    o->e = take(Rp * DE); o->ehid = take(Rp * EHW);
+    o->total = at;
+    o->off_n = 0; o->off_noff = B; o->off_eoff = 2 * B; o->off_node = 3 * B; o->off_pair = 3 * B + (int)Nn;
+    o->words = 3 * B + (int)Nn + (int)P + 1;
+    return JODO_OK;
+}
+
+struct K2 {                      // kernel arguments
+    const int *mol_n, *mol_noff, *mol_eoff, *node_b, *pair;
+    int B, N, Nn, P, nd, ch, layer;
+    float th;
+    const float* W;
+    const int32_t* flags;        // [0] symmetric inputs, [1] shared noise level
+    const float *xh, *edge_x, *cond_x, *cond_edge_x, *noise;
+    float *out_xh, *out_edge;
+    float *hid1, *tembs, *mods, *h, *hm, *qkv, *hn, *u, *f1, *ahid, *nh1, *nh2, *nh3, *e, *ehid;
+    int64_t wg[J2_GLOBAL_COUNT], wb[J2B_BLOCK_COUNT];
+};
+
+__device__ __forceinline__ float half_max(float v) {          // over the 32 lanes of a half
+#pragma unroll
+    for (int m = 1; m < 32; m <<= 1) v = fmaxf(v, __shfl_xor(v, m));
+    return v;
+}
+__device__ __forceinline__ float half_sum(float v) {
+#pragma unroll
+    for (int m = 1; m < 32; m <<= 1) v += __shfl_xor(v, m);
+    return v;
+}
+
+// Sum of 16 per-lane values over the 32 lanes of a half, transposed: lane j ends with the total of value j % 16 (31 exchanges
+// instead of 80: after the first full exchange every step halves the values a lane still carries).
+__device__ __forceinline__ float half_sum16(const float (&v)[16], int j) {
+    float a[16];
+#pragma unroll
+    for (int s = 0; s < 16; ++s) a[s] = v[s] + __shfl_xor(v[s], 16);
+    float b8[8], b4[4], b2[2];
+    const bool u8 = (j & 8) != 0, u4 = (j & 4) != 0, u2 = (j & 2) != 0, u1 = (j & 1) != 0;
+#pragma unroll
+    for (int s = 0; s < 8; ++s) b8[s] = (u8 ? a[s + 8] : a[s]) + __shfl_xor(u8 ? a[s] : a[s + 8], 8);
+#pragma unroll
+    for (int s = 0; s < 4; ++s) b4[s] = (u4 ? b8[s + 4] : b8[s]) + __shfl_xor(u4 ? b8[s] : b8[s + 4], 4);
+#pragma unroll
+    for (int s = 0; s < 2; ++s) b2[s] = (u2 ? b4[s + 2] : b4[s]) + __shfl_xor(u2 ? b4[s] : b4[s + 2], 2);
+    return (u1 ? b2[1] : b2[0]) + __shfl_xor(u1 ? b2[0] : b2[1], 1);
+}
+
+// ---- prologue ------------------------------------------------------------------------------------------------------------------
+__global__ void k2d_flags_init(int32_t* flags, int force_directed) {
+    if (threadIdx.x == 0) { flags[0] = force_directed ? 0 : 1; flags[1] = 1; }
+}
+__global__ void k2d_flags(K2 A, int32_t* flags) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx < (size_t)A.B && A.noise[idx] != A.noise[0]) flags[1] = 0;
+    const size_t tot = (size_t)A.B * A.N * A.N;
+    if (idx >= tot) return;
+    const int c = (int)(idx % A.N), r = (int)((idx / A.N) % A.N), b = (int)(idx / ((size_t)A.N * A.N));
+    const int n = A.mol_n[b];
+    if (!(r < c && c < n)) return;
+    const size_t t = (((size_t)b * A.N + c) * A.N + r) * A.ch;
+    bool same = true;
+    for (int k = 0; k < A.ch; ++k) {
+        same = same && A.edge_x[idx * A.ch + k] == A.edge_x[t + k];
+        if (A.cond_edge_x) same = same && A.cond_edge_x[idx * A.ch + k] == A.cond_edge_x[t + k];
+    }
+    if (!same) flags[0] = 0;
+}
+
+// time_mlp.0 / .1: [x, sin, cos] (17) -> Linear -> GELU(erf)
+__global__ __launch_bounds__(256) void k2d_time1(K2 A) {
+    const int b = blockIdx.x;
+    if (A.flags[1] && b > 0) return;
+    __shared__ float ft[17];
+    if (threadIdx.x < 8) {
+        const float x = A.noise[b];
+        const float fr = x * A.W[A.wg[J2_TIME_FREQ] + threadIdx.x] * 2.f * 3.14159265358979323846f;
+        ft[1 + threadIdx.x] = sinf(fr);
+        ft[9 + threadIdx.x] = cosf(fr);
+        if (threadIdx.x == 0) ft[0] = x;
+    }
+    __syncthreads();
+    const float* W1 = A.W + A.wg[J2_TIME_W1];
+    const float* b1 = A.W + A.wg[J2_TIME_B1];
+    for (int j = threadIdx.x; j < T2; j += 256) {
+        float s = b1[j];
+#pragma unroll
+        for (int k = 0; k < 17; ++k) s = fmaf(W1[j * 17 + k], ft[k], s);
+        A.hid1[(size_t)b * T2 + j] = 0.5f * s * (1.f + erff(s * 0.70710678118654752f));
+    }
+}
+
+// ---- row GEMM: Y[rows, 32 NB] = epi(X[rows, 64 nk] W^T + bias) ----------------------------------------------------------------------
+struct Gemm2 {
+    const float* X; int ldx; float* Y; int ldy; const float* W; const float* bias; int rows, nk, NB, act;    // act 1: SiLU
+    const float* R; int ldr; const float* gate; int gate_ld; const int* node_b; const int32_t* flags; int uni_rows;
+};
+template <int NOB, int MT>
+__global__ __launch_bounds__(64) void k2d_gemm(Gemm2 G) {
+    const int lane = threadIdx.x, j = lane & 31, h = lane >> 5;
+    const int strip = blockIdx.x, ob0 = blockIdx.y * NOB;
+    if (G.uni_rows && G.flags[1] && strip > 0) return;
+    f32x16 acc[NOB][MT];
+    int row[MT];
+    const float* xr[MT];
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+        row[m] = (strip * MT + m) * 32 + j;
+        xr[m] = G.X + (size_t)min(row[m], G.rows - 1) * G.ldx;
+#pragma unroll
+        for (int o = 0; o < NOB; ++o) acc[o][m] = zero16();
+    }
+    for (int kc = 0; kc < G.nk; ++kc) {
+        float act[MT][32];
+#pragma unroll
+        for (int m = 0; m < MT; ++m) load_nat<2>(xr[m] + kc * 64, h, act[m]);
+#pragma unroll
+        for (int o = 0; o < NOB; ++o) {
+            if (ob0 + o >= G.NB) continue;
+            const float4* w = reinterpret_cast<const float4*>(G.W) + ((size_t)(ob0 + o) * G.nk + kc) * 512 + lane;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const float4 a = w[q * 64];
+#pragma unroll
+                for (int m = 0; m < MT; ++m) {
+                    acc[o][m] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, act[m][4 * q + 0], acc[o][m], 0, 0, 0);
+                    acc[o][m] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, act[m][4 * q + 1], acc[o][m], 0, 0, 0);
+                    acc[o][m] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, act[m][4 * q + 2], acc[o][m], 0, 0, 0);
+                    acc[o][m] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, act[m][4 * q + 3], acc[o][m], 0, 0, 0);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+        if (row[m] >= G.rows) continue;
+        int mrow = 0;
+        if (G.R && !G.flags[1]) mrow = G.node_b[row[m]] >> 8;
+#pragma unroll
+        for (int o = 0; o < NOB; ++o) {
+            if (ob0 + o >= G.NB) continue;
+            const int col0 = (ob0 + o) * 32 + 16 * h;
+            float v[16], bb[16];
+            if (G.bias) load16(G.bias + col0, bb);
+#pragma unroll
+            for (int s = 0; s < 16; ++s) {
+                v[s] = acc[o][m][s] + (G.bias ? bb[s] : 0.f);
+                if (G.act == 1) v[s] = silu_f(v[s]);
+            }
+            if (G.R) {
+                float rr[16], gg[16];
+                load16(G.R + (size_t)row[m] * G.ldr + col0, rr);
+                load16(G.gate + (size_t)mrow * G.gate_ld + col0, gg);
+#pragma unroll
+                for (int s = 0; s < 16; ++s) v[s] = fmaf(gg[s], v[s], rr[s]);
+            }
+            store16(G.Y + (size_t)row[m] * G.ldy + col0, v);
+        }
+    }
+}
+
+// ---- embeddings ------------------------------------------------------------------------------------------------------------------
+__global__ void k2d_embed_nodes(K2 A) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= A.Nn * D2) return;
+    const int node = idx >> 8, f = idx & 255;
+    const int nb = A.node_b[node], b = nb >> 8, i = nb & 255;
+    const float* w = A.W + A.wg[J2_NODE_EMB_W] + (size_t)f * 2 * A.nd;
+    const float* x = A.xh + ((size_t)b * A.N + i) * A.nd;
+    float s = A.W[A.wg[J2_NODE_EMB_B] + f];
+    for (int k = 0; k < A.nd; ++k) s = fmaf(w[k], x[k], s);
+    if (A.cond_x) {
+        const float* cx = A.cond_x + ((size_t)b * A.N + i) * A.nd;
+        for (int k = 0; k < A.nd; ++k) s = fmaf(w[A.nd + k], cx[k], s);
+    }
+    A.h[(size_t)node * D2 + f] = s;
+    A.ahid[(size_t)node * NHW + f] = s;
+}
+
+// item < P: pair (r, c) with r < c; item >= P: its mirror (c, r) (directed fallback only)
+__device__ __forceinline__ void item_rc(const K2& A, int item, int& b, int& r, int& c) {
+    const int pr = A.pair[item < A.P ? item : item - A.P];
+    b = pr >> 12;
+    r = (pr >> 6) & 63;
+    c = pr & 63;
+    if (item >= A.P) { const int t = r; r = c; c = t; }
+}
+
+__global__ void k2d_embed_edges(K2 A) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int item = (int)(idx >> 6), f = (int)(idx & 63);
+    if (item >= (A.flags[0] ? A.P : 2 * A.P)) return;
+    int b, r, c;
+    item_rc(A, item, b, r, c);
+    const int n = A.mol_n[b];
+    const size_t row = (size_t)A.mol_eoff[b] + (size_t)r * n + c;
+    const size_t in = (((size_t)b * A.N + r) * A.N + c) * A.ch;
+    const float* w = A.W + A.wg[J2_EDGE_EMB_W] + (size_t)f * 2 * A.ch;
+    float s = A.W[A.wg[J2_EDGE_EMB_B] + f];
+    for (int k = 0; k < A.ch; ++k) s = fmaf(w[k], A.edge_x[in + k], s);
+    if (A.cond_edge_x)
+        for (int k = 0; k < A.ch; ++k) s = fmaf(w[A.ch + k], A.cond_edge_x[in + k], s);
+    A.e[row * DE + f] = s;
+    A.ehid[row * EHW + f] = s;
+}
+
+// ---- node LayerNorm + modulate: Y = LN(X + gate R) (1 + scale) + shift; one wave per node row -------------------------------------
+__global__ __launch_bounds__(256) void k2d_ln_mod(K2 A, const float* X, const float* R, float* Y, int gate_off, int shift_off, int scale_off) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= A.Nn) return;
+    const int mrow = A.flags[1] ? 0 : (A.node_b[row] >> 8);
+    const float* md = A.mods + (size_t)mrow * MODW + (size_t)A.layer * MODB;
+    float4 v = reinterpret_cast<const float4*>(X + (size_t)row * D2)[lane];
+    if (R) {
+        const float4 r = reinterpret_cast<const float4*>(R + (size_t)row * D2)[lane];
+        const float4 g = reinterpret_cast<const float4*>(md + gate_off)[lane];
+        v.x = fmaf(g.x, r.x, v.x); v.y = fmaf(g.y, r.y, v.y); v.z = fmaf(g.z, r.z, v.z); v.w = fmaf(g.w, r.w, v.w);
+    }
+    float s = (v.x + v.y) + (v.z + v.w);
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) s += __shfl_xor(s, m);
+    const float mean = s * (1.f / D2);
+    v.x -= mean; v.y -= mean; v.z -= mean; v.w -= mean;
+    float q = (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) q += __shfl_xor(q, m);
+    const float rstd = 1.f / sqrtf(q * (1.f / D2) + 1e-6f);
+    const float4 sh = reinterpret_cast<const float4*>(md + shift_off)[lane], sc = reinterpret_cast<const float4*>(md + scale_off)[lane];
+    float4 y;
+    y.x = fmaf(v.x * rstd, 1.f + sc.x, sh.x); y.y = fmaf(v.y * rstd, 1.f + sc.y, sh.y);
+    y.z = fmaf(v.z * rstd, 1.f + sc.z, sh.z); y.w = fmaf(v.w * rstd, 1.f + sc.w, sh.w);
+    reinterpret_cast<float4*>(Y + (size_t)row * D2)[lane] = y;
+}
+
+// one 32-row output block from LDS-resident tiles: acc += W_tile act (tile = 8 quads x 64 lanes of float4)
+__device__ __forceinline__ f32x16 mfma_lds(const float4* tile, int lane, const float* act, f32x16 acc) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const float4 a = tile[q * 64 + lane];
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, act[4 * q + 0], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, act[4 * q + 1], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, act[4 * q + 2], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, act[4 * q + 3], acc, 0, 0, 0);
+    }
+    return acc;
+}
+
+// ---- 2-D attention: one wave per target atom, sources in chunks of 32 (one per lane pair), running softmax ---------------------------
+// Lane (j, h): source r0 + j, half h.  Scores: half 0 holds attention heads 0 (adjacency) .. 7, half 1 heads 8 .. 15; the value /
+// lin_edge1 channels of block ob on half h are those of head 8 h + ob (row maps of csrc/dgt2d_pack.cpp).
+__global__ __launch_bounds__(256, 1) void k2d_attn(K2 A) {
+    __shared__ float4 wl[16 * 512];
+    {
+        const float4* src = reinterpret_cast<const float4*>(A.W + A.wb[J2B_LE_W]);
+        for (int i = threadIdx.x; i < 16 * 512; i += 256) wl[i] = src[i];
+    }
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
+    const int sym = A.flags[0], uni = A.flags[1];
+    for (int t = blockIdx.x * 4 + wave; t < A.Nn; t += gridDim.x * 4) {
+        const int nb = A.node_b[t], b = nb >> 8, c = nb & 255;
+        const int n = A.mol_n[b], noff = A.mol_noff[b];
+        const size_t eoff = (size_t)A.mol_eoff[b];
+        float* out_row = A.hn + (size_t)t * D2;
+        if (n == 1) {                                        // no sources: the block's attention output is zero
+            reinterpret_cast<float4*>(out_row)[lane] = make_float4(0.f, 0.f, 0.f, 0.f);
+            continue;
+        }
+        const float* md = A.mods + (size_t)(uni ? 0 : b) * MODW + (size_t)A.layer * MODB + 6 * D2;
+        const float* qrow = A.qkv + (size_t)t * 3 * D2 + h * 128;
+        float mx[8], den[8], out[8];             // out[ob]: channel j % 16 of attention head 8 h + ob
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { mx[i] = -INFINITY; den[i] = 0.f; }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) out[i] = 0.f;
+        for (int r0 = 0; r0 < n; r0 += 32) {
+            const int r = r0 + j;
+            const bool valid = r < n && r != c;
+            const int rs = valid ? r : (c == 0 ? 1 : 0);     // a live row for masked lanes (their weight is zero)
+            const size_t row = sym ? eoff + (size_t)min(rs, c) * n + max(rs, c) : eoff + (size_t)rs * n + c;
+            float et[32];
+            load_nat<2>(A.e + row * DE, h, et);
+            layer_norm<32>(et);
+            modulate<2>(et, md, md + DE, h);
+            const float* krow = A.qkv + (size_t)(noff + rs) * 3 * D2 + D2 + h * 128;
+            const float* qr = launder(qrow);                 // (re-read per chunk instead of 128 hoisted registers)
+            float seg[7], tail = 0.f;
+#pragma unroll
+            for (int g = 0; g < 7; ++g) seg[g] = 0.f;
+#pragma unroll
+            for (int ob = 0; ob < 8; ++ob) {
+                const f32x16 acc = mfma_lds(wl + ob * 512, lane, et, zero16());
+                float tt[16], kk[16], qq[16];
+                tanh16(acc, tt);
+                load16(krow + ob * 16, kk);
+                load16(qr + ob * 16, qq);
+#pragma unroll
+                for (int s = 0; s < 16; ++s) {
+                    const int slot = ob * 16 + s;
+                    const float p = qq[s] * kk[s] * tt[s];
+                    if (slot < 119) seg[slot / 17] += p; else tail += p;
+                }
+                pipeline_fence();                            // keeps the next block's loads from being hoisted above this block (registers)
+            }
+            tail = pair_sum(tail);
+            float S[8];
+            if (h == 0) {
+                float adj = 1.f;
+                if (A.cond_edge_x) adj = A.cond_edge_x[(((size_t)b * A.N + rs) * A.N + c) * A.ch] >= A.th ? 1.f : -1e10f;
+                S[0] = adj;
+            } else {
+                S[0] = tail * 0.25f;
+            }
+#pragma unroll
+            for (int g = 0; g < 7; ++g) S[1 + g] = seg[g] * 0.25f;
+            float wgt[8], fsc[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const float si = valid ? S[i] : -INFINITY;
+                const float mnew = fmaxf(mx[i], half_max(si));
+                const float muse = mnew == -INFINITY ? 0.f : mnew;
+                wgt[i] = valid ? fast_exp(si - muse) : 0.f;
+                fsc[i] = fast_exp(mx[i] - muse);
+                den[i] = den[i] * fsc[i] + half_sum(wgt[i]);
+                mx[i] = mnew;
+            }
+            const float* vrow = A.qkv + (size_t)(noff + rs) * 3 * D2 + 2 * D2 + h * 128;
+#pragma unroll
+            for (int ob = 0; ob < 8; ++ob) {
+                const f32x16 acc = mfma_lds(wl + (8 + ob) * 512, lane, et, zero16());
+                float tt[16], vv[16];
+                tanh16(acc, tt);
+                load16(vrow + ob * 16, vv);
+#pragma unroll
+                for (int s = 0; s < 16; ++s) tt[s] = wgt[ob] * vv[s] * tt[s];
+                out[ob] = fmaf(out[ob], fsc[ob], half_sum16(tt, j));
+                pipeline_fence();
+            }
+        }
+        if (j < 16) {
+#pragma unroll
+            for (int ob = 0; ob < 8; ++ob) out_row[(8 * h + ob) * 16 + j] = den[ob] > 0.f ? out[ob] / den[ob] : 0.f;
+        }
+    }
+}
+
+// per-lane modulation vector in natural-half order (lanes of a strip may belong to different molecules)
+__device__ __forceinline__ void lane_vec(const float* p, int h, float (&x)[32]) { load_nat<2>(p, h, x); }
+
+// ---- 2-D pair update: e1 = e + gate_msa (W_n2e (hn_r + hn_c) + b); e2 = modulate(LN(e1)); e' = e2 + gate_mlp FFN(e2); readout ------
+__global__ __launch_bounds__(256, 1) void k2d_pair(K2 A) {
+    __shared__ float4 wl[9 * 512];                           // ff_linear3 (4 tiles) | ff_linear4 (2 x 2 tiles) | readout (1 tile)
+    {
+        const float4* s3 = reinterpret_cast<const float4*>(A.W + A.wb[J2B_FF3_W]);
+        const float4* s4 = reinterpret_cast<const float4*>(A.W + A.wb[J2B_FF4_W]);
+        const float4* sr = reinterpret_cast<const float4*>(A.W + A.wb[J2B_ERO_W]);
+        for (int i = threadIdx.x; i < 4 * 512; i += 256) { wl[i] = s3[i]; wl[4 * 512 + i] = s4[i]; }
+        for (int i = threadIdx.x; i < 512; i += 256) wl[8 * 512 + i] = sr[i];
+    }
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
+    const int uni = A.flags[1];
+    const int items = A.flags[0] ? A.P : 2 * A.P;
+    const float* b2e = A.W + A.wb[J2B_N2E_B];
+    const float* b3 = A.W + A.wb[J2B_FF3_B];
+    const float* b4 = A.W + A.wb[J2B_FF4_B];
+    const float* bro = A.W + A.wb[J2B_ERO_B];
+    for (int strip = blockIdx.x * 4 + wave; strip * 32 < items; strip += gridDim.x * 4) {
+        const int item = strip * 32 + j;
+        const bool live = item < items;
+        int b, r, c;
+        item_rc(A, live ? item : items - 1, b, r, c);
+        const int n = A.mol_n[b], noff = A.mol_noff[b];
+        const size_t row = (size_t)A.mol_eoff[b] + (size_t)r * n + c;
+        const float* md = A.mods + (size_t)(uni ? 0 : b) * MODW + (size_t)A.layer * MODB + 6 * D2;
+        float e[32];
+        load_nat<2>(A.e + row * DE, h, e);
+        {
+            float ur[32], uc[32], g[32], bb[32];
+            load_nat<2>(A.u + (size_t)(noff + r) * DE, h, ur);
+            load_nat<2>(A.u + (size_t)(noff + c) * DE, h, uc);
+            lane_vec(md + 2 * DE, h, g);
+            lane_vec(b2e, h, bb);
+#pragma unroll
+            for (int i = 0; i < 32; ++i) e[i] = fmaf(g[i], (ur[i] + uc[i]) + bb[i], e[i]);
+        }
+        layer_norm<32>(e);
+        {
+            float sh[32], sc[32];
+            lane_vec(md + 3 * DE, h, sh);
+            lane_vec(md + 4 * DE, h, sc);
+#pragma unroll
+            for (int i = 0; i < 32; ++i) e[i] = fmaf(e[i], 1.f + sc[i], sh[i]);
+        }
+        float hid[64];
+#pragma unroll
+        for (int ob = 0; ob < 4; ++ob) {
+            const f32x16 acc = mfma_lds(wl + ob * 512, lane, e, zero16());
+            float bb[16], o16[16];
+            load16(b3 + ob * 32 + 16 * h, bb);
+            silu_bias16(acc, bb, o16);
+#pragma unroll
+            for (int s = 0; s < 16; ++s) hid[ob * 16 + s] = o16[s];
+            pipeline_fence();
+        }
+        float gm[32];
+        lane_vec(md + 5 * DE, h, gm);
+#pragma unroll
+        for (int ob = 0; ob < 2; ++ob) {
+            f32x16 acc = mfma_lds(wl + (4 + ob * 2) * 512, lane, hid, zero16());
+            acc = mfma_lds(wl + (5 + ob * 2) * 512, lane, hid + 32, acc);
+            float bb[16];
+            load16(b4 + ob * 32 + 16 * h, bb);
+#pragma unroll
+            for (int s = 0; s < 16; ++s) e[ob * 16 + s] = fmaf(gm[ob * 16 + s], acc[s] + bb[s], e[ob * 16 + s]);
+        }
+        const f32x16 racc = mfma_lds(wl + 8 * 512, lane, e, zero16());
+        if (live) {
+            store_nat<2>(A.e + row * DE, h, e);
+            if (h == 0) {
+                float bb[16], o16[16];
+                load16(bro, bb);
+#pragma unroll
+                for (int s = 0; s < 16; ++s) o16[s] = racc[s] + bb[s];
+                store16(A.ehid + row * EHW + DE + 16 * A.layer, o16);
+            }
+        }
+    }
+}
+
+// ---- edge heads: exist / type MLPs on [e0 | 8 readouts] (192), one evaluation per unordered pair (two when directed), 0.5 (E + E^T) --
+__global__ __launch_bounds__(64) void k2d_edge_head(K2 A) {
+    const int lane = threadIdx.x, j = lane & 31, h = lane >> 5;
+    const int item = blockIdx.x * 32 + j;
+    const bool live = item < A.P;
+    const int sym = A.flags[0];
+    int b, r, c;
+    item_rc(A, live ? item : A.P - 1, b, r, c);
+    const int n = A.mol_n[b];
+    const size_t eoff = (size_t)A.mol_eoff[b];
+    const float4* w1 = reinterpret_cast<const float4*>(A.W + A.wg[J2_EH1_W]);
+    const float4* w2 = reinterpret_cast<const float4*>(A.W + A.wg[J2_EH2_W]);
+    const float* b1 = A.W + A.wg[J2_EH1_B];
+    const float* b2 = A.W + A.wg[J2_EH2_B];
+    const float* w3 = A.W + A.wg[J2_EH3_W];
+    const float* b3 = A.W + A.wg[J2_EH3_B];
+    float res[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int dir = 0; dir < (sym ? 1 : 2); ++dir) {
+        const size_t row = dir == 0 ? eoff + (size_t)r * n + c : eoff + (size_t)c * n + r;
+        f32x16 a1[4];
+#pragma unroll
+        for (int ob = 0; ob < 4; ++ob) a1[ob] = zero16();
+#pragma unroll
+        for (int kc = 0; kc < 3; ++kc) {
+            float x[32];
+            load_nat<2>(A.ehid + row * EHW + kc * 64, h, x);
+#pragma unroll
+            for (int ob = 0; ob < 4; ++ob) {
+                a1[ob] = mfma_block<8>(w1 + (size_t)(ob * 3 + kc) * 512 + lane, x, a1[ob]);
+                pipeline_fence();
+            }
+        }
+        float h1[64];
+#pragma unroll
+        for (int ob = 0; ob < 4; ++ob) {
+            float bb[16], o16[16];
+            load16(b1 + ob * 32 + 16 * h, bb);
+            silu_bias16(a1[ob], bb, o16);
+#pragma unroll
+            for (int s = 0; s < 16; ++s) h1[ob * 16 + s] = o16[s];
+        }
+#pragma unroll
+        for (int mlp = 0; mlp < 2; ++mlp) {                  // 0 = edge_exist_mlp, 1 = edge_type_mlp
+            const f32x16 acc = mfma_block<8>(w2 + (size_t)mlp * 512 + lane, *reinterpret_cast<const float(*)[32]>(h1 + mlp * 32), zero16());
+            float bb[16], h2[16];
+            load16(b2 + mlp * 32 + 16 * h, bb);
+            silu_bias16(acc, bb, h2);
+            const int k0 = mlp == 0 ? 0 : 1, k1 = mlp == 0 ? 1 : A.ch;
+            for (int k = k0; k < k1; ++k) {
+                float wv[16], s = 0.f;
+                load16(w3 + k * 32 + 16 * h, wv);
+#pragma unroll
+                for (int i = 0; i < 16; ++i) s = fmaf(wv[i], h2[i], s);
+                res[k] += pair_sum(s) + b3[k];
+            }
+        }
+    }
+    if (live && h == 0) {
+        float* o1 = A.out_edge + (((size_t)b * A.N + r) * A.N + c) * A.ch;
+        float* o2 = A.out_edge + (((size_t)b * A.N + c) * A.N + r) * A.ch;
+        for (int k = 0; k < A.ch; ++k) {
+            const float v = sym ? res[k] : 0.5f * res[k];
+            o1[k] = v;
+            o2[k] = v;
+        }
+    }
+}
+
+__global__ void k2d_finalize_nodes(K2 A) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= A.Nn * A.nd) return;
+    const int node = idx / A.nd, k = idx % A.nd;
+    const int nb = A.node_b[node], b = nb >> 8, i = nb & 255;
+    A.out_xh[((size_t)b * A.N + i) * A.nd + k] = A.nh3[(size_t)node * 32 + k];
+}
+
+// ---- the 2-D sampler's ancestral update -------------------------------------------------------------------------------------------
+__global__ void k2d_sampler_step(int B, int N, int nd, int ch, const int32_t* n_nodes, float cx, float cp, float sigma, const float* x,
+                                 const float* ex, const float* pred, const float* epred, const float* eps, const float* eeps, float* x_next,
+                                 float* e_next, float* x_mean, float* e_mean) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t n_node = (size_t)B * N * nd, n_edge = (size_t)B * N * N * ch;
+    if (idx < n_node) {
+        const int i = (int)((idx / nd) % N), b = (int)(idx / ((size_t)nd * N));
+        const float m = cx * x[idx] + cp * pred[idx];
+        x_mean[idx] = m;
+        x_next[idx] = m + (i < n_nodes[b] ? sigma * eps[idx] : 0.f);
+    } else if (idx < n_node + n_edge) {
+        const size_t q = idx - n_node;
+        const int k = (int)(q % ch), c = (int)((q / ch) % N), r = (int)((q / ((size_t)ch * N)) % N), b = (int)(q / ((size_t)ch * N * N));
+        const float m = cx * ex[q] + cp * epred[q];
+        e_mean[q] = m;
+        const int n = n_nodes[b];
+        // the noise of pair {r, c} is the entry of the strict lower triangle (row max, column min), as the reference mirrors it
+        const size_t src = (((size_t)b * N + max(r, c)) * N + min(r, c)) * ch + k;
+        e_next[q] = m + ((r != c && r < n && c < n) ? sigma * eeps[src] : 0.f);
+    }
+}
+
+int gemm(hipStream_t st, const float* X, int ldx, float* Y, int ldy, const float* W, const float* bias, int rows, int K, int NB, int act,
+         const K2& A, const float* R = nullptr, int ldr = 0, const float* gate = nullptr, bool uni_rows = false) {
+    if (K % 64) return jodo_set_error(JODO_ERR_ARG, "dgt2d gemm: K=%d not a multiple of 64", K);
+    Gemm2 G{X, ldx, Y, ldy, W, bias, rows, K / 64, NB, act, R, ldr, gate, MODW, A.node_b, A.flags, uni_rows ? 1 : 0};
+    if (uni_rows) { L2D((k2d_gemm<1, 1>), dim3((rows + 31) / 32, NB), 64, G); }
+    else { L2D((k2d_gemm<4, 2>), dim3((rows + 63) / 64, (NB + 3) / 4), 64, G); }
+    return JODO_OK;
+}
+
+}  // namespace
+
+extern "C" int jodo_dgt2d_layout(const jodo_cfg2d* cfg, int B, int N, const int32_t* n_nodes, int64_t* out8) {
+    if (!out8) return jodo_set_error(JODO_ERR_ARG, "dgt2d_layout: null argument");
+    if (int rc = jodo_dgt2d_check_cfg(cfg)) return rc;
+    Lay l;
+    if (int rc = make_lay(B, N, n_nodes, &l)) return rc;
+    out8[0] = l.words; out8[1] = (int64_t)(l.total * sizeof(float)); out8[2] = l.Nn; out8[3] = l.R;
+    out8[4] = (int64_t)(l.h * sizeof(float)); out8[5] = (int64_t)(l.e * sizeof(float)); out8[6] = l.P; out8[7] = 0;
+    return JODO_OK;
+}
+
+extern "C" int jodo_dgt2d_fill_desc(const jodo_cfg2d* cfg, int B, int N, const int32_t* n_nodes, int32_t* desc, int64_t n_words) {
+    if (!desc) return jodo_set_error(JODO_ERR_ARG, "dgt2d_fill_desc: null argument");
+    if (int rc = jodo_dgt2d_check_cfg(cfg)) return rc;
+    Lay l;
+    if (int rc = make_lay(B, N, n_nodes, &l)) return rc;
+    if (n_words < l.words) return jodo_set_error(JODO_ERR_ARG, "dgt2d_fill_desc: %lld words, need %d", (long long)n_words, l.words);
+    int noff = 0, eoff = 0, node = 0, pair = 0;
+    for (int b = 0; b < B; ++b) {
+        const int n = n_nodes[b];
+        desc[l.off_n + b] = n; desc[l.off_noff + b] = noff; desc[l.off_eoff + b] = eoff;
+        for (int i = 0; i < n; ++i) desc[l.off_node + node++] = (b << 8) | i;
+        for (int r = 0; r < n; ++r)
+            for (int c = r + 1; c < n; ++c) desc[l.off_pair + pair++] = (b << 12) | (r << 6) | c;
+        noff += n; eoff += n * n;
+    }
+    desc[l.off_pair + pair] = 0;
+    return JODO_OK;
+}
+
+extern "C" int jodo_dgt2d_forward(const jodo_cfg2d* cfg, int B, int N, const int32_t* n_nodes, const void* desc_dev, const float* packed_w,
+                                  const int64_t* woff, int n_woff, const float* xh, const float* edge_x, const float* cond_x,
+                                  const float* cond_edge_x, const float* noise_level, float* out_xh, float* out_edge, int32_t* flags_dev,
+                                  void* workspace, int force_directed, int max_blocks, void* stream) {
+    if (!desc_dev || !packed_w || !woff || !xh || !edge_x || !noise_level || !out_xh || !out_edge || !flags_dev || !workspace)
+        return jodo_set_error(JODO_ERR_ARG, "dgt2d_forward: null argument");
+    if (int rc = jodo_dgt2d_check_cfg(cfg)) return rc;
+    if ((cond_x == nullptr) != (cond_edge_x == nullptr))
+        return jodo_set_error(JODO_ERR_ARG, "dgt2d_forward: cond_x and cond_edge_x must both be given or both NULL");
+    if (n_woff != J2_GLOBAL_COUNT + cfg->n_layers * J2B_BLOCK_COUNT)
+        return jodo_set_error(JODO_ERR_ARG, "dgt2d_forward: weight table has %d slots, expected %d", n_woff, J2_GLOBAL_COUNT + cfg->n_layers * J2B_BLOCK_COUNT);
+    Lay l;
+    if (int rc = make_lay(B, N, n_nodes, &l)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const int* dsc = static_cast<const int*>(desc_dev);
+    float* ws = static_cast<float*>(workspace);
+    K2 A;
+    A.mol_n = dsc + l.off_n; A.mol_noff = dsc + l.off_noff; A.mol_eoff = dsc + l.off_eoff; A.node_b = dsc + l.off_node; A.pair = dsc + l.off_pair;
+    A.B = B; A.N = N; A.Nn = l.Nn; A.P = l.P; A.nd = cfg->in_node_dim; A.ch = cfg->edge_ch; A.layer = 0; A.th = cfg->edge_quan_th;
+    A.W = packed_w; A.flags = flags_dev;
+    A.xh = xh; A.edge_x = edge_x; A.cond_x = cond_x; A.cond_edge_x = cond_edge_x; A.noise = noise_level; A.out_xh = out_xh; A.out_edge = out_edge;
+    A.hid1 = ws + l.hid1; A.tembs = ws + l.tembs; A.mods = ws + l.mods; A.h = ws + l.h; A.hm = ws + l.hm; A.qkv = ws + l.qkv; A.hn = ws + l.hn;
+    A.u = ws + l.u; A.f1 = ws + l.f1; A.ahid = ws + l.ahid; A.nh1 = ws + l.nh1; A.nh2 = ws + l.nh2; A.nh3 = ws + l.nh3; A.e = ws + l.e; A.ehid = ws + l.ehid;
+    for (int i = 0; i < J2_GLOBAL_COUNT; ++i) A.wg[i] = woff[i];
+    for (int i = 0; i < J2B_BLOCK_COUNT; ++i) A.wb[i] = 0;
+    const float* W = packed_w;
+    const size_t n_out_x = (size_t)B * N * A.nd, n_out_e = (size_t)B * N * N * A.ch;
+    if (hipMemsetAsync(out_xh, 0, n_out_x * sizeof(float), st) != hipSuccess || hipMemsetAsync(out_edge, 0, n_out_e * sizeof(float), st) != hipSuccess)
+        return jodo_set_error(JODO_ERR_LAUNCH, "dgt2d_forward: clearing the outputs failed");
+
+    // ---- flags, time embedding, modulation rows ----
+    L2D(k2d_flags_init, 1, 64, flags_dev, force_directed);
+    L2D(k2d_flags, (unsigned)(((size_t)B * N * N + 255) / 256), 256, A, flags_dev);
+    L2D(k2d_time1, B, 256, A);
+    int rc;
+    if ((rc = gemm(st, A.hid1, T2, A.tembs, T2, W + A.wg[J2_TIME_W3], W + A.wg[J2_TIME_B3], B, T2, T2 / 32, 1, A, nullptr, 0, nullptr, true))) return rc;
+    if ((rc = gemm(st, A.tembs, T2, A.mods, MODW, W + A.wg[J2_MOD_W], W + A.wg[J2_MOD_B], B, T2, MODW / 32, 0, A, nullptr, 0, nullptr, true))) return rc;
+    // ---- embeddings ----
+    L2D(k2d_embed_nodes, (l.Nn * D2 + 255) / 256, 256, A);
+    if (l.P > 0) L2D(k2d_embed_edges, (unsigned)(((size_t)2 * l.P * 64 + 255) / 256), 256, A);
+    // ---- blocks ----
+    const int nblocks = (max_blocks >= 0 && max_blocks < cfg->n_layers) ? max_blocks : cfg->n_layers;
+    const int persist = 256;                                 // one workgroup of four waves per compute unit
+    for (int lyr = 0; lyr < nblocks; ++lyr) {
+        A.layer = lyr;
+        for (int i = 0; i < J2B_BLOCK_COUNT; ++i) A.wb[i] = woff[J2_GLOBAL_COUNT + lyr * J2B_BLOCK_COUNT + i];
+        const float* gate_mlp = A.mods + (size_t)lyr * MODB + 5 * D2;
+        L2D(k2d_ln_mod, (l.Nn + 3) / 4, 256, A, A.h, (const float*)nullptr, A.hm, 0, 0, D2);
+        if ((rc = gemm(st, A.hm, D2, A.qkv, 3 * D2, W + A.wb[J2B_QKV_W], W + A.wb[J2B_QKV_B], l.Nn, D2, 24, 0, A))) return rc;
+        L2D(k2d_attn, persist, 256, A);
+        if ((rc = gemm(st, A.hn, D2, A.u, DE, W + A.wb[J2B_N2E_W], nullptr, l.Nn, D2, 2, 0, A))) return rc;
+        L2D(k2d_ln_mod, (l.Nn + 3) / 4, 256, A, A.h, (const float*)A.hn, A.hm, 2 * D2, 3 * D2, 4 * D2);
+        if ((rc = gemm(st, A.hm, D2, A.f1, 2 * D2, W + A.wb[J2B_FF1_W], W + A.wb[J2B_FF1_B], l.Nn, D2, 16, 1, A))) return rc;
+        if ((rc = gemm(st, A.f1, 2 * D2, A.h, D2, W + A.wb[J2B_FF2_W], W + A.wb[J2B_FF2_B], l.Nn, 2 * D2, 8, 0, A, A.hm, D2, gate_mlp))) return rc;
+        if ((rc = gemm(st, A.h, D2, A.ahid + D2 + 64 * lyr, NHW, W + A.wb[J2B_NRO_W], W + A.wb[J2B_NRO_B], l.Nn, D2, 2, 0, A))) return rc;
+        if (l.P > 0) L2D(k2d_pair, 2 * persist, 256, A);
+    }
+    // ---- heads ----
+    if ((rc = gemm(st, A.ahid, NHW, A.nh1, D2, W + A.wg[J2_NH1_W], W + A.wg[J2_NH1_B], l.Nn, NHW, 8, 1, A))) return rc;
+    if ((rc = gemm(st, A.nh1, D2, A.nh2, D2 / 2, W + A.wg[J2_NH2_W], W + A.wg[J2_NH2_B], l.Nn, D2, 4, 1, A))) return rc;
+    if ((rc = gemm(st, A.nh2, D2 / 2, A.nh3, 32, W + A.wg[J2_NH3_W], W + A.wg[J2_NH3_B], l.Nn, D2 / 2, 1, 0, A))) return rc;
+    L2D(k2d_finalize_nodes, (l.Nn * A.nd + 255) / 256, 256, A);
+    if (l.P > 0) L2D(k2d_edge_head, (l.P + 31) / 32, 64, A);
+    return JODO_OK;
+}
+
+extern "C" int jodo_sampler_step_2d(int B, int N, int node_feats, int edge_ch, const int32_t* n_nodes_dev, float cx, float cp, float sigma,
+                                    const float* x, const float* edge_x, const float* pred, const float* edge_pred, const float* eps_node,
+                                    const float* eps_edge, float* x_next, float* edge_next, float* x_mean, float* edge_mean, void* stream) {
+    if (B <= 0 || N <= 0 || node_feats <= 0 || edge_ch <= 0 || !n_nodes_dev || !x || !edge_x || !pred || !edge_pred || !eps_node || !eps_edge ||
+        !x_next || !edge_next || !x_mean || !edge_mean)
+        return jodo_set_error(JODO_ERR_ARG, "sampler_step_2d: bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    const size_t tot = (size_t)B * N * node_feats + (size_t)B * N * N * edge_ch;
+    L2D(k2d_sampler_step, (unsigned)((tot + 255) / 256), 256, B, N, node_feats, edge_ch, n_nodes_dev, cx, cp, sigma, x, edge_x, pred, edge_pred,
+        eps_node, eps_edge, x_next, edge_next, x_mean, edge_mean);
+    return JODO_OK;
+}

@@ -112,6 +112,26 @@ def sampler_step(bufs, n_nodes_dev, c_x, c_pred, sigma, x, edge_x, pred, edge_pr
     return xn, en, bufs.x_mean, bufs.e_mean
 
 
+def sampler_step_2d(n_nodes_dev, c_x, c_pred, sigma, x, edge_x, pred, edge_pred, eps_node, eps_edge):
+    """The 2-D sampler's ancestral update as one kernel (jodo_sampler_step_2d): no position channels, node noise masked to the
+    real atoms, edge noise [B,N,N,ch] read from its strict lower triangle for both orientations of a pair.
+    Returns (x_next, edge_next, x_mean, edge_mean), freshly allocated."""
+    x, edge_x, pred, edge_pred = _f32c(x, 'x'), _f32c(edge_x, 'edge_x'), _f32c(pred, 'pred'), _f32c(edge_pred, 'edge_pred')
+    eps_node, eps_edge = _f32c(eps_node, 'eps_node'), _f32c(eps_edge, 'eps_edge')
+    B, N, nd = x.shape
+    ch = edge_x.shape[-1]
+    if edge_x.shape != (B, N, N, ch) or eps_edge.shape != edge_x.shape or eps_node.shape != x.shape or pred.shape != x.shape \
+            or edge_pred.shape != edge_x.shape:
+        raise ValueError("sampler_step_2d: shape mismatch")
+    new = lambda t: torch.empty(t.shape, dtype=torch.float32, device=t.device)
+    x_next, e_next, x_mean, e_mean = new(x), new(edge_x), new(x), new(edge_x)
+    capi.check(capi.lib().jodo_sampler_step_2d(B, N, nd, ch, capi.ptr(n_nodes_dev), ctypes.c_float(c_x), ctypes.c_float(c_pred),
+                                               ctypes.c_float(sigma), capi.ptr(x), capi.ptr(edge_x), capi.ptr(pred), capi.ptr(edge_pred),
+                                               capi.ptr(eps_node), capi.ptr(eps_edge), capi.ptr(x_next), capi.ptr(e_next), capi.ptr(x_mean),
+                                               capi.ptr(e_mean), capi.current_stream_ptr()), 'jodo_sampler_step_2d')
+    return x_next, e_next, x_mean, e_mean
+
+
 def decode(config, xh, edge_x, n_nodes_dev):
     """post_process + inverse scaling on the device.  Returns compact device tensors
     (pos f32 [B,N,3], atom_type u8 [B,N], fc i8 [B,N], edge_type u8 [B,N,N])."""

@@ -1,0 +1,207 @@
+"""MI355X-native score network for 2-D graphs, registered under the reference's name 'DGT_concat_2D'
+(reference: models/mol_gnn.py:797-946; the ZINC250k and MOSES experiments).
+
+Same constructor argument, parameter names / shapes / registration order (state_dict keys, EMA order, `strict=True` loading) and
+the same call as the reference class:
+    model(t, xh, node_mask, edge_mask, context=None, edge_x=..., cond_x=..., cond_edge_x=..., noise_level=...)
+        -> (atom_pred [B,N,nd], edge_pred [B,N,N,ch])
+The arithmetic runs in libjodo_hip.so (csrc/dgt2d_forward.hip, `jodo_dgt2d_forward`) on the current HIP stream: the weights are
+packed once (csrc/dgt2d_pack.cpp), a descriptor and a workspace are built per batch of atom counts.  Inference only: there is no
+CPU or eager fallback, no training path and no split-bf16 form for this model — those raise.
+"""
+import ctypes
+
+import numpy as np
+import torch
+from torch import nn
+
+from .. import capi
+from . import utils
+from .dgt import _SinusoidParams, _mlp3, _time_seq, _AttnParams, _drop_packed_after_load
+
+# (key, the one supported value) — the settings of configs/vpsde_zinc_2d_jodo.py and vpsde_moses_2d_jodo.py
+_SUPPORTED_2D = (('nf', 256), ('n_heads', 16), ('n_extra_heads', 1), ('mlp_ratio', 2), ('n_layers', 8), ('cond_time', True),
+                 ('pred_data', True), ('softmax_inf', True), ('trans_name', 'TransMixLayer'))
+
+
+class _Block2DParams(nn.Module):
+    """EquivariantMixBlock_2D (mol_gnn.py:325-362): parameters only, reference registration order."""
+
+    def __init__(self, node_dim, edge_dim, time_dim, n_extra, n_heads, mlp_ratio):
+        super().__init__()
+        self.node2edge_lin = nn.Linear(node_dim, edge_dim)
+        self.attn_mpnn = _AttnParams(node_dim, node_dim // n_heads, n_extra, n_heads, edge_dim)
+        self.ff_linear1 = nn.Linear(node_dim, node_dim * mlp_ratio)
+        self.ff_linear2 = nn.Linear(node_dim * mlp_ratio, node_dim)
+        self.ff_linear3 = nn.Linear(edge_dim, edge_dim * mlp_ratio)
+        self.ff_linear4 = nn.Linear(edge_dim * mlp_ratio, edge_dim)
+        self.node_time_mlp = _time_seq(time_dim, node_dim * 6)
+        self.edge_time_mlp = _time_seq(time_dim, edge_dim * 6)
+
+
+class _Cfg2D(ctypes.Structure):                 # jodo_cfg2d (include/jodo_hip.h)
+    _fields_ = [('nf', ctypes.c_int32), ('n_layers', ctypes.c_int32), ('n_heads', ctypes.c_int32), ('n_extra', ctypes.c_int32),
+                ('mlp_ratio', ctypes.c_int32), ('in_node_dim', ctypes.c_int32), ('edge_ch', ctypes.c_int32),
+                ('edge_quan_th', ctypes.c_float)]
+
+
+@utils.register_model(name='DGT_concat_2D')
+class DGT_concat_2D(nn.Module):
+    """Diffusion Graph Transformer with self-conditioning for 2-D graphs (HIP)."""
+
+    def __init__(self, config):
+        super().__init__()
+        m = config.model
+        for key, want in _SUPPORTED_2D:
+            got = getattr(m, key, want if key == 'trans_name' else None)
+            if got != want:
+                raise NotImplementedError("config.model.%s=%r: the 2-D HIP path implements %r only (the ZINC250k / MOSES configs' setting)"
+                                          % (key, got, want))
+        if hasattr(m, 'time_dim') and m.time_dim != 4 * m.nf:
+            raise NotImplementedError("config.model.time_dim=%r: the 2-D HIP path implements 4 * nf = %d only" % (m.time_dim, 4 * m.nf))
+        in_node_dim = config.data.atom_types + int(m.include_fc_charge)
+        if not 1 <= in_node_dim <= 16:
+            raise NotImplementedError("config.data.atom_types + include_fc_charge = %d: the 2-D HIP path takes 1..16 node channels" % in_node_dim)
+        if m.edge_ch not in (2, 3):
+            raise NotImplementedError("config.model.edge_ch=%r: the 2-D HIP path implements 2 and 3" % (m.edge_ch,))
+        D, De, L, T = m.nf, m.nf // 4, m.n_layers, 4 * m.nf
+        self.in_node_dim, self.edge_ch = in_node_dim, int(m.edge_ch)
+        self.edge_th = float(m.edge_quan_th)
+        self.n_layers = L
+        self.pred_data = m.pred_data
+        self.cond_time = m.cond_time
+        self.dropout_p = m.dropout               # identity at inference; kept for config parity
+        self._cfg_struct = _Cfg2D(D, L, m.n_heads, m.n_extra_heads, m.mlp_ratio, in_node_dim, self.edge_ch, self.edge_th)
+
+        # ---- parameter tree, reference construction / registration order (mol_gnn.py:823-866) ----
+        self.node_emb = nn.Linear(in_node_dim * 2, D)
+        self.edge_emb = nn.Linear(m.edge_ch * 2, De)
+        cat_node, cat_edge = (D * 2) // L, (De * 2) // L
+        for i in range(L):
+            self.add_module("e_block_%d" % i, _Block2DParams(D, De, T, m.n_extra_heads, m.n_heads, m.mlp_ratio))
+            self.add_module("node_%d" % i, nn.Linear(D, cat_node))
+            self.add_module("edge_%d" % i, nn.Linear(De, cat_edge))
+        self.node_pred_mlp = _mlp3(cat_node * L + D, D, D // 2, in_node_dim)
+        self.edge_type_mlp = _mlp3(cat_edge * L + De, De, De // 2, m.edge_ch - 1)
+        self.edge_exist_mlp = _mlp3(cat_edge * L + De, De, De // 2, 1)
+        self.time_mlp = nn.Sequential(_SinusoidParams(16), nn.Linear(17, T), nn.GELU(), nn.Linear(T, T))
+
+        # ---- runtime state (not part of state_dict) ----
+        self._packed = None           # (version key, device blob, woff ctypes array, n_woff)
+        self._plans = {}              # per batch of atom counts: descriptor + workspace, keyed by the mask storage (see _plan)
+        self.split_bf16 = False       # the 3-D models' opt-in form; not built for this model (forward raises when set)
+        self.force_directed = False   # tests: always the directed fallback
+        self.max_blocks = -1          # tests: stop after this many blocks (the workspace then holds h and e of that block)
+        self.last_flags = None
+        self.register_load_state_dict_post_hook(_drop_packed_after_load)
+
+    # -- weights (same invalidation rules as _DGTBase._weights) ------------------------------------
+    def _weights(self, device):
+        key = (str(device),) + tuple(p._version for p in self.parameters()) + tuple(p.data_ptr() for p in self.parameters())
+        if self._packed is None or self._packed[0] != key:
+            blob, woff_c, n_woff = capi.pack_weights_2d(self._cfg_struct, self.state_dict(), device)
+            self._packed = (key, blob, woff_c, n_woff)
+            self._packed_fingerprint = self._fingerprint()
+        return self._packed
+
+    def _fingerprint(self):
+        ps = [p.detach() for p in self.parameters()]
+        norms = torch._foreach_norm(ps)
+        w = torch.arange(1, len(norms) + 1, device=norms[0].device, dtype=torch.float64)
+        return float((torch.stack([n.double() for n in norms]) * (1.0 + 1e-3 * w)).sum().item())
+
+    def _recheck_weights(self):
+        if self._packed is not None and self._fingerprint() != getattr(self, '_packed_fingerprint', None):
+            self._packed = None
+
+    def invalidate_packed_weights(self):
+        """Drop the packed kernel weights; the next forward re-packs from the current parameters (needed after in-place `.data`
+        updates that bump no tensor version, e.g. the reference's ExponentialMovingAverage.copy_to / restore)."""
+        self._packed = None
+
+    # -- per-batch descriptor and workspace -----------------------------------------------------------
+    def _plan(self, node_mask, edge_mask, device, validate=True):
+        # keyed by the mask's storage (address, shape, stride, device) + version counter like _DGTBase._plan: the single-device
+        # DataParallel wrap hands over a fresh view of the same mask on every call
+        key = (node_mask.data_ptr(), tuple(node_mask.shape), tuple(node_mask.stride()), str(node_mask.device))
+        plan = self._plans.get(key)
+        if plan is not None and plan['mask_version'] == node_mask._version:
+            return plan
+        self._recheck_weights()                          # new batch (= new sampling round): catch `.data` weight updates
+        B, N = node_mask.shape[0], node_mask.shape[1]
+        nm = node_mask.reshape(B, N)
+        n_nodes = nm.sum(1).round().to(torch.int32)
+        if validate:
+            prefix = (torch.arange(N, device=nm.device).unsqueeze(0) < n_nodes.unsqueeze(1)).to(nm.dtype)
+            if not torch.equal(prefix, nm):
+                raise ValueError("node_mask must be a prefix mask (real atoms first), as the samplers build it")
+            em = edge_mask.reshape(B, N, N)
+            want = prefix.unsqueeze(1) * prefix.unsqueeze(2) * (~torch.eye(N, dtype=torch.bool, device=nm.device))
+            if not torch.equal(want.to(em.dtype), em):
+                raise ValueError("edge_mask must be node_mask x node_mask with the diagonal removed")
+        n_host = np.ascontiguousarray(n_nodes.cpu().numpy(), dtype=np.int32)     # one sync per new batch
+        L = capi.lib()
+        lay = (ctypes.c_int64 * 8)()
+        n_ptr = n_host.ctypes.data_as(ctypes.c_void_p)
+        capi.check(L.jodo_dgt2d_layout(ctypes.byref(self._cfg_struct), B, N, n_ptr, lay), 'jodo_dgt2d_layout')
+        desc_host = torch.empty(int(lay[0]), dtype=torch.int32)
+        capi.check(L.jodo_dgt2d_fill_desc(ctypes.byref(self._cfg_struct), B, N, n_ptr, ctypes.c_void_p(desc_host.data_ptr()),
+                                          ctypes.c_int64(int(lay[0]))), 'jodo_dgt2d_fill_desc')
+        plan = dict(desc=desc_host.to(device), ws=torch.zeros(int(lay[1]), dtype=torch.uint8, device=device), n_nodes=n_host, B=B, N=N,
+                    Nn=int(lay[2]), rows=int(lay[3]), h_off=int(lay[4]), e_off=int(lay[5]), pairs=int(lay[6]), mask=node_mask,
+                    mask_version=node_mask._version, flags=torch.zeros(8, dtype=torch.int32, device=device))
+        self._plans.pop(key, None)
+        if len(self._plans) >= 8:                        # bounded cache
+            self._plans.pop(next(iter(self._plans)))
+        self._plans[key] = plan
+        return plan
+
+    def _replicate_for_data_parallel(self):
+        raise RuntimeError(
+            "jodo_amd %s cannot be replicated by torch.nn.DataParallel over several devices: its descriptors, workspace and packed "
+            "weights belong to one device.  DataParallel(model, device_ids=[one device]) is supported." % type(self).__name__)
+
+    # -- forward -------------------------------------------------------------------------------
+    def forward(self, t, xh, node_mask, edge_mask, context=None, *args, **kwargs):
+        edge_x, cond_x, cond_edge_x = kwargs['edge_x'], kwargs.get('cond_x'), kwargs.get('cond_edge_x')
+        noise_level = kwargs['noise_level']
+        if not xh.is_cuda:
+            raise RuntimeError("jodo_amd DGT_concat_2D runs on an MI355X only (got a %s tensor); there is no CPU fallback — "
+                               "use tests/oracle2d.py for CPU checks" % xh.device)
+        if self.split_bf16:
+            raise NotImplementedError("split_bf16 is not implemented for DGT_concat_2D (exact fp32 only)")
+        if torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters()) or
+                                        any(t_ is not None and t_.requires_grad for t_ in (xh, edge_x, cond_x, cond_edge_x, noise_level))):
+            raise NotImplementedError("DGT_concat_2D is inference only: call it under torch.no_grad() (training / backward for the 2-D "
+                                      "model is not implemented)")
+        if (cond_x is None) != (cond_edge_x is None):
+            raise ValueError("cond_x and cond_edge_x must both be given or both be None")
+        B, N, dims = xh.shape
+        if dims != self.in_node_dim or edge_x.shape != (B, N, N, self.edge_ch):
+            raise ValueError("shape mismatch: xh %s edge_x %s" % (tuple(xh.shape), tuple(edge_x.shape)))
+        dev = xh.device
+        f32 = lambda x: None if x is None else x.detach().to(torch.float32).contiguous()
+        xh_, ex_, cx_, cex_, nl_ = f32(xh), f32(edge_x), f32(cond_x), f32(cond_edge_x), f32(noise_level)
+        plan = self._plan(node_mask, edge_mask, dev)     # first: a new batch re-checks the weight fingerprint
+        _, blob, woff_c, n_woff = self._weights(dev)
+        out_x = torch.empty_like(xh_)
+        out_e = torch.empty_like(ex_)
+        capi.check(capi.lib().jodo_dgt2d_forward(
+            ctypes.byref(self._cfg_struct), B, N, plan['n_nodes'].ctypes.data_as(ctypes.c_void_p), capi.ptr(plan['desc']), capi.ptr(blob),
+            woff_c, n_woff, capi.ptr(xh_), capi.ptr(ex_), capi.ptr(cx_), capi.ptr(cex_), capi.ptr(nl_), capi.ptr(out_x), capi.ptr(out_e),
+            capi.ptr(plan['flags']), capi.ptr(plan['ws']), int(bool(self.force_directed)), int(self.max_blocks),
+            capi.current_stream_ptr()), 'jodo_dgt2d_forward')
+        self.last_flags = plan['flags']
+        self._last_plan = plan
+        return out_x, out_e
+
+    # -- tests: the state inside the workspace after the last call ------------------------------------
+    def debug_state(self):
+        """(h [Nn, nf], e [sum n^2, nf / 4]) of the last call as the kernels left them: h compact over real atoms; e row
+        eoff_b + r n_b + c, with only the rows r < c live when the inputs were symmetric (flags[0])."""
+        p = self._last_plan
+        D = self._cfg_struct.nf
+        ws = p['ws']
+        h = ws[p['h_off']:p['h_off'] + p['Nn'] * D * 4].view(torch.float32).reshape(p['Nn'], D)
+        e = ws[p['e_off']:p['e_off'] + p['rows'] * (D // 4) * 4].view(torch.float32).reshape(p['rows'], D // 4)
+        return h.clone(), e.clone()

@@ -13,7 +13,11 @@ Additions that do not change the reference behaviour:
     round's batch (jodo_amd/dist.py gathers the results) — replaces nn.DataParallel;
   * masks are built vectorised rather than with a Python loop over the batch (:195-196);
   * `hip_graph=True` on `get_sampling_fn`: the ancestral loop replays one captured HIP graph per step.
-The 2-D-only sampler (`AncestralSampler_2D`) is out of scope.
+
+The 2-D experiments (`config.only_2D`, model DGT_concat_2D): `AncestralSampler_2D` (:599-660), `post_process_2D` (:100-141),
+`mol_process_2D` (:35-50) and the 2-D sampling function of `get_sampling_fn` (:234-276), with the reference's RNG use.  The
+additions above are not built for the 2-D path: `shard=`, `hip_graph=True`, `device_noise=True` and `method='fast'` raise
+NotImplementedError there; `cpu_noise=True` (2-D only) makes every draw on the CPU generator in the reference's shapes and order.
 """
 import random
 
@@ -23,7 +27,7 @@ from torch.nn import functional as F
 
 from .mix_dpm_solver import DPM_Solver_hybrid
 from .models.utils import (assert_mean_zero_with_mask, model_hook, sample_combined_position_feature_noise,
-                           sample_symmetric_edge_feature_noise)
+                           sample_gaussian_with_mask, sample_symmetric_edge_feature_noise)
 from .utils import expand_dims, get_self_cond_fn
 
 
@@ -86,6 +90,51 @@ def post_process(xh, atom_types, include_charge, node_mask, inverse_scaler, edge
     return pos, h_cat, h_int, h_edge
 
 
+def mol_process_2D(one_hot, formal_charges, n_nodes, edge_types=None):
+    """Batch tensors -> list of per-molecule CPU tuples (None, atom_type[n], edge_type[n,n], fc[n]) — sampling.py:35-50.
+    One device->host copy per tensor instead of one per molecule."""
+    atom_type_all = one_hot.argmax(2).cpu()
+    edge_all = edge_types.detach().cpu()
+    fc_all = formal_charges.detach().cpu()
+    mols = []
+    for i in range(one_hot.shape[0]):
+        n = int(n_nodes[i])
+        fc = fc_all[i, :n, 0].long() if fc_all.shape[-1] != 0 else fc_all[i][:n]
+        mols.append((None, atom_type_all[i, :n], edge_all[i, :n, :n], fc))
+    return mols
+
+
+def post_process_2D(xh, atom_types, include_charge, node_mask, inverse_scaler, edge_x=None, edge_mask=None,
+                    compress_edge=False):
+    """Split xh [B,N,atom_types(+1)] (no positions), undo normalisation, discretise — sampling.py:100-141; the same decisions as
+    post_process.  Returns (one_hot, charge, bond type)."""
+    if include_charge:
+        h_int, h_cat = xh[:, :, -1:], xh[:, :, :-1]
+    else:
+        h_int, h_cat = torch.zeros(0).to(xh.device), xh[:, :, :]
+    assert h_cat.shape[-1] == atom_types
+    assert edge_x is not None
+    _, h_cat, h_int, h_edge = inverse_scaler(None, h_cat, h_int, node_mask, edge_x, edge_mask)
+    h_cat = F.one_hot(torch.argmax(h_cat, dim=2), atom_types) * node_mask
+    h_int = torch.round(h_int).long() * node_mask
+    if compress_edge:
+        exist = (h_edge[..., 0] >= 0.5).to(h_edge.dtype)
+        o = h_edge[..., 1] * 3.
+        order = torch.zeros_like(o)
+        order[o >= 0.5] = 1.
+        order[o >= 1.5] = 2.
+        order[o >= 2.5] = 3.
+        order = exist * order
+        if h_edge.size(-1) == 3:
+            arom = exist * (h_edge[..., 2] >= 0.5).to(h_edge.dtype)
+            order[torch.bitwise_and(arom > 0., order == 0.)] = 4.
+        h_edge = order
+    else:
+        any_on = torch.sum(h_edge > 0.5, dim=-1) != 0
+        h_edge = any_on * (torch.argmax(h_edge, dim=-1) + 1.0)
+    return h_cat, h_int, h_edge
+
+
 def build_masks(n_nodes, max_n_nodes, device):
     """node_mask [B,N,1], edge_mask [B*N*N,1] (prefix masks, diagonal removed) — sampling.py:193-201."""
     n = torch.as_tensor(n_nodes, dtype=torch.long)
@@ -132,7 +181,7 @@ class _ParityNoise:
 
 def get_sampling_fn(config, noise_scheduler, nodes_dist, batch_size, n_samples, inverse_scaler, eps=1e-3,
                     prop_dist=None, shard=None, return_raw=False, fused_decode=True, hip_graph=False,
-                    shard_mode='perf', shard_assign='contiguous', seed=None, device_noise=None):
+                    shard_mode='perf', shard_assign='contiguous', seed=None, device_noise=None, cpu_noise=False):
     """sampling.py:148-232.  Without `shard` this is the reference's procedure, RNG use included.
 
     shard=(rank, world) — one process per GPU (replaces nn.DataParallel).  Seeding contract: every rank passes the SAME
@@ -164,8 +213,13 @@ def get_sampling_fn(config, noise_scheduler, nodes_dist, batch_size, n_samples, 
     pred_edge = config.pred_edge
     edge_nf = config.model.edge_ch
     compress_edge = config.data.compress_edge
-    if config.only_2D or not pred_edge:
-        raise NotImplementedError("only the 3-D + edge (vpsde_edge) sampling path is in scope")
+    if not pred_edge:
+        raise NotImplementedError("only the edge-predicting sampling paths (3-D + edge, 2-D) are in scope")
+    if config.only_2D:
+        return _get_sampling_fn_2d(config, noise_scheduler, nodes_dist, batch_size, n_samples, inverse_scaler, eps, shard=shard,
+                                   return_raw=return_raw, hip_graph=hip_graph, device_noise=device_noise, cpu_noise=cpu_noise)
+    if cpu_noise:
+        raise ValueError("cpu_noise is an option of the 2-D sampling function; the 3-D path replays CPU draws with shard_mode='parity'")
     if shard_mode not in ('perf', 'parity') or shard_assign not in ('contiguous', 'lpt'):
         raise ValueError("shard_mode in {'perf','parity'}, shard_assign in {'contiguous','lpt'}")
     if shard is not None and not (0 <= shard[0] < shard[1]):
@@ -304,6 +358,64 @@ def get_sampling_fn(config, noise_scheduler, nodes_dist, batch_size, n_samples, 
     sampling_fn.last_indices = None
     sampling_fn.last_decoded = decoded_rounds
     return sampling_fn
+
+
+def _get_sampling_fn_2d(config, noise_scheduler, nodes_dist, batch_size, n_samples, inverse_scaler, eps, shard=None, return_raw=False,
+                        hip_graph=False, device_noise=None, cpu_noise=False):
+    """sampling.py:234-276 (`sampling_fn_2D`): atom counts for all rounds first, then per round z = sample_gaussian_with_mask,
+    symmetric edge noise, AncestralSampler_2D, post_process_2D, mol_process_2D; `random.shuffle` at the end.  cpu_noise: every draw
+    is made by the CPU generator (reference shapes and order) and copied to the device, so that a seeded run reproduces the CPU
+    reference's noise stream on the GPU (tests)."""
+    for name, val in (('shard', shard is not None), ('hip_graph', bool(hip_graph)), ('device_noise', bool(device_noise))):
+        if val:
+            raise NotImplementedError("%s is not implemented for the 2-D sampling path (config.only_2D)" % name)
+    if config.sampling.method == 'fast':
+        raise NotImplementedError("sampling.method='fast' (DPM-solver) is not implemented for the 2-D sampling path")
+    if config.sampling.method != 'ancestral':
+        raise ValueError('Invalid sampling method!')
+    device = config.device
+    atom_types = config.data.atom_types
+    include_fc = config.model.include_fc_charge
+    node_nf = atom_types + int(include_fc)
+    edge_nf = config.model.edge_ch
+    compress_edge = config.data.compress_edge
+    rounds = int(np.ceil(n_samples / batch_size))
+    time_steps = torch.linspace(noise_scheduler.T, eps, config.sampling.steps)      # host scalars, as in the 3-D path
+    sampler = AncestralSampler_2D(noise_scheduler, time_steps, config.model.pred_data, config.model.self_cond)
+
+    def sampling_fn_2D(model):
+        model.eval()
+        mols = []
+        with torch.no_grad():
+            n_nodes_all = nodes_dist.sample(rounds * batch_size)
+            for r in range(rounds):
+                n_nodes = n_nodes_all[r * batch_size:(r + 1) * batch_size]
+                max_n = int(max(n_nodes))
+                node_mask, edge_mask = build_masks(n_nodes, max_n, device)
+                if cpu_noise:
+                    nm_c, em_c = build_masks(n_nodes, max_n, 'cpu')
+                    z = sample_gaussian_with_mask((batch_size, max_n, node_nf), 'cpu', nm_c).to(device)
+                    edge_z = sample_symmetric_edge_feature_noise(batch_size, max_n, edge_nf, em_c).to(device)
+                    sampler.noise_fn = lambda i, kind, like: (
+                        sample_gaussian_with_mask(tuple(like.shape), 'cpu', nm_c) if kind == 'node'
+                        else sample_symmetric_edge_feature_noise(like.shape[0], like.shape[1], like.shape[-1], em_c)).to(like.device)
+                else:
+                    z = sample_gaussian_with_mask((batch_size, max_n, node_nf), device, node_mask)
+                    edge_z = sample_symmetric_edge_feature_noise(batch_size, max_n, edge_nf, edge_mask)
+                try:
+                    x_node, x_edge = sampler.sampling(model, z, node_mask, edge_mask, edge_z, None)
+                finally:
+                    sampler.noise_fn = None
+                one_hot, fc, edge_types = post_process_2D(x_node, atom_types, include_fc, node_mask, inverse_scaler, x_edge,
+                                                          edge_mask, compress_edge)
+                mols += mol_process_2D(one_hot, fc, n_nodes, edge_types)
+                print('Generate {}, Total {}.'.format(len(mols), n_samples))
+        if return_raw:
+            return mols
+        random.shuffle(mols)
+        return mols[:n_samples]
+
+    return sampling_fn_2D
 
 
 def full_edge_index(n_nodes, batch_size, device):
@@ -524,4 +636,72 @@ class AncestralSampler:
             if unpin is not None:
                 unpin()
         assert_mean_zero_with_mask(st['x_mean'][:, :, :3], node_mask)
+        return st['x_mean'], st['edge_x_mean']
+
+
+class AncestralSampler_2D:
+    """Ancestral sampler without 3-D positions (sampling.py:599-660): every node channel gets plain masked Gaussian noise, the edge
+    noise is symmetric; returns the noise-free mean of the last step.  `noise_fn(step, kind, like)` replays recorded draws
+    ('node' / 'edge', in the reference's draw order).  On GPU tensors with a data-predicting model the update runs as one HIP
+    kernel (jodo_sampler_step_2d) fed with the same draws."""
+
+    def __init__(self, noise_scheduler, time_steps, model_pred_data, self_cond=False, noise_fn=None, fused=True):
+        self.noise_scheduler = noise_scheduler
+        self.t_array = time_steps
+        self.s_array = torch.cat([time_steps[1:], torch.zeros(1, device=time_steps.device)])
+        self.model_pred_data = model_pred_data
+        self.self_cond = self_cond
+        self.noise_fn = noise_fn
+        self.fused = fused
+
+    def init_state(self, z_T, edge_z_T):
+        return dict(x=z_T, edge_x=edge_z_T, cond_x=None, cond_edge_x=None, x_mean=None, edge_x_mean=None)
+
+    def _noise(self, i, x, edge_x, node_mask, edge_mask):
+        """(node noise, edge noise) of step i — RNG order of the reference: node first, then edge."""
+        if self.noise_fn is not None:
+            return self.noise_fn(i, 'node', x), self.noise_fn(i, 'edge', edge_x)
+        return (sample_gaussian_with_mask(x.size(), x.device, node_mask),
+                sample_symmetric_edge_feature_noise(x.shape[0], edge_x.shape[1], edge_x.shape[-1], edge_mask))
+
+    def step(self, model, i, st, node_mask, edge_mask, context=None):
+        ns = self.noise_scheduler
+        x, edge_x = st['x'], st['edge_x']
+        bs = x.shape[0]
+        t, s = self.t_array[i], self.s_array[i]
+        c_x, c_pred, sigma, alpha_t, sigma_t, a_ts, var_ts = posterior_coefficients(ns, t, s)
+        vec_t = torch.ones(bs, device=x.device) * t
+        noise_level = torch.ones(bs, device=x.device) * torch.log(alpha_t ** 2 / sigma_t ** 2)
+        if self.self_cond:
+            assert self.model_pred_data
+            pred_t, edge_pred_t = model(vec_t, x, node_mask, edge_mask, edge_x=edge_x, noise_level=noise_level,
+                                        cond_x=st['cond_x'], cond_edge_x=st['cond_edge_x'], context=context)
+            st['cond_x'], st['cond_edge_x'] = pred_t, edge_pred_t
+        else:
+            pred_t, edge_pred_t = model(vec_t, x, node_mask, edge_mask, edge_x=edge_x, noise_level=noise_level, context=context)
+        if self.fused and x.is_cuda and self.model_pred_data:
+            from . import fused
+            if st.get('_n_nodes') is None:
+                st['_n_nodes'] = fused.n_nodes_from_mask(node_mask)
+            eps_n, eps_e = self._noise(i, x, edge_x, node_mask, edge_mask)
+            st['x'], st['edge_x'], st['x_mean'], st['edge_x_mean'] = fused.sampler_step_2d(
+                st['_n_nodes'], float(c_x), float(c_pred), float(sigma), x, edge_x, pred_t, edge_pred_t, eps_n, eps_e)
+            return st
+        if self.model_pred_data:
+            x_mean = c_x * x + c_pred * pred_t
+            edge_x_mean = c_x * edge_x + c_pred * edge_pred_t
+        else:
+            k = var_ts / a_ts / sigma_t
+            x_mean = x / a_ts - k * pred_t
+            edge_x_mean = edge_x / a_ts - k * edge_pred_t
+        eps_n, eps_e = self._noise(i, x_mean, edge_x_mean, node_mask, edge_mask)
+        st['x'] = x_mean + sigma * eps_n
+        st['edge_x'] = edge_x_mean + sigma * eps_e
+        st['x_mean'], st['edge_x_mean'] = x_mean, edge_x_mean
+        return st
+
+    def sampling(self, model, z_T, node_mask, edge_mask, edge_z_T=None, context=None):
+        st = self.init_state(z_T, edge_z_T)
+        for i in range(len(self.t_array)):
+            st = self.step(model, i, st, node_mask, edge_mask, context)
         return st['x_mean'], st['edge_x_mean']

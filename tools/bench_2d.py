@@ -1,0 +1,105 @@
+"""Benchmark of the 2-D sampling step (DGT_concat_2D + AncestralSampler_2D) at the configs' evaluation batch, and of the baseline a
+user without the HIP path would run on the same GPU: the dense torch evaluation of the same network (tests/oracle2d.py) on the
+device, chunked by molecules to fit memory, under the same sampler.
+
+    python tools/bench_2d.py --workload zinc|moses [--batch 2000] [--steps 20] [--warmup 3] [--baseline-steps 3] [--no-baseline]
+
+Atom counts are drawn from the training histogram (tests/golden/n_nodes_2d.json, seed 42).  Timing as bench.py does it: warm-up,
+synchronise, `steps` sampler.step calls, synchronise.  Prints one JSON line: ms/step, molecules/s at 1000 steps, the directed-edge
+count, ns per directed edge per step, and the same for the torch baseline with the ratio.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+
+from jodo_amd import configs                                                      # noqa: E402
+from jodo_amd.diffusion.noise_schedule import NoiseScheduleVP                     # noqa: E402
+from jodo_amd.models import get_model_class, get_node_dist, deterministic_init_   # noqa: E402
+from jodo_amd.models.utils import sample_gaussian_with_mask, sample_symmetric_edge_feature_noise      # noqa: E402
+from jodo_amd.sampling import AncestralSampler_2D, build_masks                    # noqa: E402
+import oracle2d as O2                                                             # noqa: E402
+
+WORKLOADS = {'zinc': ('vpsde_zinc_2d_jodo', 'zinc250k'), 'moses': ('vpsde_moses_2d_jodo', 'moses')}
+
+
+class ChunkedDense:
+    """The dense torch evaluation on the device, `chunk` molecules at a time (each chunk cut to its own largest molecule)."""
+
+    def __init__(self, sd, hp, n_nodes, chunk):
+        self.sd, self.hp, self.n, self.chunk = sd, hp, n_nodes, chunk
+
+    def __call__(self, t, xh, node_mask, edge_mask, context=None, **kw):
+        B, N = xh.shape[0], xh.shape[1]
+        em = edge_mask.reshape(B, N, N, 1)
+        ox, oe = torch.zeros_like(xh), torch.zeros_like(kw['edge_x'])
+        for lo in range(0, B, self.chunk):
+            hi = min(lo + self.chunk, B)
+            n = int(max(self.n[lo:hi]))
+            cut = lambda v, two: None if v is None else (v[lo:hi, :n, :n] if two else v[lo:hi, :n])
+            a, b = O2.forward_dense(self.sd, self.hp, cut(xh, 0), cut(node_mask, 0), cut(em, 1).reshape(-1, 1), cut(kw['edge_x'], 1),
+                                    cut(kw.get('cond_x'), 0), cut(kw.get('cond_edge_x'), 1), kw['noise_level'][lo:hi])
+            ox[lo:hi, :n], oe[lo:hi, :n, :n] = a, b
+        return ox, oe
+
+
+def time_steps(sampler, model, z, edge_z, node_mask, edge_mask, warmup, steps):
+    st = sampler.init_state(z, edge_z)
+    with torch.no_grad():
+        for i in range(warmup):
+            st = sampler.step(model, i, st, node_mask, edge_mask, None)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(warmup, warmup + steps):
+            st = sampler.step(model, i, st, node_mask, edge_mask, None)
+        torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / steps * 1e3, st
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--workload', choices=sorted(WORKLOADS), default='zinc')
+    ap.add_argument('--batch', type=int, default=2000)
+    ap.add_argument('--steps', type=int, default=20)
+    ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--baseline-steps', type=int, default=3)
+    ap.add_argument('--baseline-chunk', type=int, default=250)
+    ap.add_argument('--no-baseline', action='store_true')
+    args = ap.parse_args()
+    torch.set_num_threads(8)
+    dev = torch.device('cuda:0')
+    cfg_name, info = WORKLOADS[args.workload]
+    cfg = configs.get(cfg_name)
+    model = deterministic_init_(get_model_class('DGT_concat_2D')(cfg), seed=7).to(dev).eval()
+    torch.manual_seed(42)
+    n_nodes = get_node_dist(O2.load_n_nodes_hist(os.path.join(ROOT, 'tests', 'golden', 'n_nodes_2d.json'), info)).sample(args.batch).tolist()
+    B, N = args.batch, max(n_nodes)
+    node_mask, edge_mask = build_masks(n_nodes, N, dev)
+    nd = cfg.data.atom_types + int(cfg.model.include_fc_charge)
+    z = sample_gaussian_with_mask((B, N, nd), dev, node_mask)
+    edge_z = sample_symmetric_edge_feature_noise(B, N, cfg.model.edge_ch, edge_mask)
+    ns = NoiseScheduleVP(cfg.sde.schedule, continuous_beta_0=cfg.sde.continuous_beta_0, continuous_beta_1=cfg.sde.continuous_beta_1)
+    sampler = AncestralSampler_2D(ns, torch.linspace(ns.T, 1e-3, 1000), True, True)
+    directed = sum(n * (n - 1) for n in n_nodes)
+    ms, st = time_steps(sampler, model, z, edge_z, node_mask, edge_mask, args.warmup, args.steps)
+    out = dict(workload=args.workload, config=cfg_name, batch=B, max_n=N, atoms=sum(n_nodes), directed_edges=directed, steps=args.steps,
+               warmup=args.warmup, hip_ms_per_step=round(ms, 4), hip_molecules_per_s_1000_steps=round(B / (ms * 1e-3 * 1000), 2),
+               hip_ns_per_directed_edge_step=round(ms * 1e6 / directed, 3), finite=bool(torch.isfinite(st['x']).all() and torch.isfinite(st['edge_x']).all()))
+    if not args.no_baseline:
+        sd = {k: v.detach() for k, v in model.state_dict().items()}
+        base = ChunkedDense(sd, O2.Hyper2D.from_config(cfg), n_nodes, args.baseline_chunk)
+        bms, _ = time_steps(sampler, base, z, edge_z, node_mask, edge_mask, 2, args.baseline_steps)
+        out.update(torch_dense_ms_per_step=round(bms, 3), torch_dense_molecules_per_s_1000_steps=round(B / (bms * 1e-3 * 1000), 3),
+                   torch_dense_chunk=args.baseline_chunk, torch_dense_steps=args.baseline_steps, speedup_vs_torch_dense=round(bms / ms, 2))
+    print(json.dumps(out))
+
+
+if __name__ == '__main__':
+    main()
