@@ -454,6 +454,25 @@ int jodo_dgt2d_forward(const jodo_cfg2d* cfg, int B, int N, const int32_t* n_nod
 int jodo_sampler_step_2d(int B, int N, int node_feats, int edge_ch, const int32_t* n_nodes_dev, float cx, float cp, float sigma,
                          const float* x, const float* edge_x, const float* pred, const float* edge_pred, const float* eps_node,
                          const float* eps_edge, float* x_next, float* edge_next, float* x_mean, float* edge_mean, void* stream);
+/* The same update with BOTH draws generated in the kernel (Philox4x32-10 + Box-Muller keyed by `seed`, the generator and the element
+ * numbering of jodo_sampler_step_rng, so that one restatement covers both): node channel k of atom a = b N + i is component k & 3 of
+ * element a * 64 + (k >> 2) of the feature stream, masked to i < n_b (no position channels, no centre-of-mass step); edge channel f of
+ * (b, r, c) is component f of cell (b N + max(r, c)) N + min(r, c) of the edge stream, zero on the diagonal and outside n_b — both
+ * orientations evaluate the same counter.  Host-scalar form (coef_tab_dev = step_dev = NULL: coefficients by value, draw index `draw`)
+ * or table form (row *step_dev of coef_tab_dev [steps][4] = (c_x, c_pred, sigma, noise_level), draw index `draw` + *step_dev: one
+ * captured hipGraph of a step replays for every step, between jodo_step_begin and jodo_step_end).  node_feats <= 256, edge_ch <= 4.
+ * One launch; all four outputs are written fully, padding included. */
+int jodo_sampler_step_2d_rng(int B, int N, int node_feats, int edge_ch, const int32_t* n_nodes_dev, float c_x, float c_pred, float sigma,
+                             const float* coef_tab_dev, const int32_t* step_dev, uint64_t seed, uint32_t draw, const float* x,
+                             const float* edge_x, const float* pred, const float* edge_pred, float* x_next, float* edge_next,
+                             float* x_mean, float* edge_mean, void* stream);
+/* jodo_decode_2d  <- post_process_2D sampling.py:100-141 + the inverse scaler utils.py:71-105 for xh [B,N,atom_types(+1)] without
+ *                    positions: the scaler in the framework's fp32 operation order (x * norm, then (x + 1) / 2 when centred, then the
+ *                    mask), atom type [B,N] u8 = first maximum, formal charge [B,N] i8 = rintf (0 when include_fc = 0), bond type
+ *                    [B,N,N] u8 by the rules of jodo_decode; zeros on padding and the diagonal. */
+int jodo_decode_2d(int B, int N, int atom_types, int include_fc, int edge_ch, int compress_edge, int centered, float atom_norm,
+                   float fc_norm, float edge_norm, const int32_t* n_nodes_dev, const float* xh, const float* edge_x,
+                   uint8_t* atom_type_out, int8_t* fc_out, uint8_t* edge_type_out, void* stream);
 
 const char* jodo_last_error(void);
 

@@ -27,7 +27,22 @@ def lib():
                 "Build it with: python -c 'import __graft_entry__ as g; g.build()'" % LIB_PATH)
         _lib = ctypes.CDLL(LIB_PATH)
         _lib.jodo_last_error.restype = ctypes.c_char_p
+        _bind_2d_sampling(_lib)
     return _lib
+
+
+def _bind_2d_sampling(L):
+    """Argument types of the 2-D round's caller-side exports (include/jodo_hip.h): a library without them is an error here, not at
+    the first sampling step."""
+    i, f, p = ctypes.c_int, ctypes.c_float, ctypes.c_void_p
+    try:
+        step, dec = L.jodo_sampler_step_2d_rng, L.jodo_decode_2d
+    except AttributeError as e:
+        raise JodoHipError("%s lacks the 2-D sampling exports (%s): rebuild it with python -c 'import __graft_entry__ as g; g.build()'"
+                           % (LIB_PATH, e))
+    step.argtypes = [i, i, i, i, p, f, f, f, p, p, ctypes.c_uint64, ctypes.c_uint32] + [p] * 9
+    dec.argtypes = [i] * 7 + [f, f, f] + [p] * 7
+    step.restype = dec.restype = i
 
 
 def check(code, what=''):

@@ -150,29 +150,86 @@ __global__ __launch_bounds__(256) void k_step_edges(int B, int N, int ch, const 
     e_next[g] = __fadd_rn(mean, __fmul_rn(sigma, e));
 }
 
+// ---- the 2-D sampler's update with both draws generated in the kernel (jodo_sampler_step_2d_rng): node tensor [B,N,nd] WITHOUT
+// position channels, edge tensor [B,N,N,ch].  ONE launch over two index ranges: a thread of the first owns the four node channels
+// 4q .. 4q+3 of one atom (one Philox evaluation: element atom * 64 + q of stream RNG_FEAT, the numbering of rng_feat above), a
+// thread of the second owns all channels of one cell (b, r, c) (one evaluation: cell (b, max, min) of stream RNG_EDGE, as
+// rng_edge; both orientations of a pair evaluate the same counter, so the edge noise is exactly symmetric).  Every output
+// element is written by exactly one thread with plain stores; padding and the diagonal get mean + sigma * 0.
+__global__ __launch_bounds__(256) void k_step_2d_rng(int B, int N, int nd, int ch, const int* __restrict__ n_nodes, float c_x, float c_pred,
+                                                     float sigma, const float* __restrict__ coef, const int* __restrict__ step, Rng rng,
+                                                     const float* __restrict__ x, const float* __restrict__ ex,
+                                                     const float* __restrict__ pred, const float* __restrict__ epred,
+                                                     float* __restrict__ x_next, float* __restrict__ e_next, float* __restrict__ x_mean,
+                                                     float* __restrict__ e_mean) {
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int nq = (nd + 3) >> 2;
+    const size_t n_quad = (size_t)B * N * nq, n_cell = (size_t)B * N * N;
+    if (g >= n_quad + n_cell) return;
+    if (coef) { const float* c = coef + 4 * (size_t)(*step); c_x = c[0]; c_pred = c[1]; sigma = c[2]; }
+    const unsigned draw = rng_draw(rng, coef ? step : nullptr);
+    float z[4] = {0.f, 0.f, 0.f, 0.f};
+    if (g < n_quad) {
+        const int q = (int)(g % nq);
+        const size_t atom = g / nq;
+        const int i = (int)(atom % N), b = (int)(atom / N);
+        if (i < n_nodes[b]) philox_normal4(rng.seed, draw, RNG_FEAT, atom * 64 + (size_t)q, z);
+        const int k1 = min(4 * q + 4, nd);
+        for (int k = 4 * q; k < k1; ++k) {
+            const size_t o = atom * nd + k;
+            const float mean = __fadd_rn(__fmul_rn(c_x, x[o]), __fmul_rn(c_pred, pred[o]));
+            x_mean[o] = mean;
+            x_next[o] = __fadd_rn(mean, __fmul_rn(sigma, z[k & 3]));
+        }
+    } else {
+        const size_t cell = g - n_quad;
+        const int c = (int)(cell % N), r = (int)((cell / N) % N), b = (int)(cell / ((size_t)N * N));
+        const int n = n_nodes[b];
+        if (r < n && c < n && r != c) {
+            const int lo = r > c ? r : c, hi = r > c ? c : r;          // strict lower triangle entry (row lo, col hi)
+            philox_normal4(rng.seed, draw, RNG_EDGE, ((size_t)b * N + lo) * N + hi, z);
+        }
+        for (int f = 0; f < ch; ++f) {
+            const size_t o = cell * ch + f;
+            const float mean = __fadd_rn(__fmul_rn(c_x, ex[o]), __fmul_rn(c_pred, epred[o]));
+            e_mean[o] = mean;
+            e_next[o] = __fadd_rn(mean, __fmul_rn(sigma, z[f]));
+        }
+    }
+}
+
 struct DecodeArgs {
     int B, N, atom_types, include_fc, ch, compress_edge, centered;
     float pos_norm, atom_norm, fc_norm, edge_norm;
 };
 
-// one thread per (b, i): positions, atom type, formal charge
+// the inverse scaler in the framework's fp32 operation order (utils.py:71-105): x * norm, then (x + 1) / 2 when centred — each
+// operation rounded on its own (no fused multiply-add), so that a value on a decision threshold falls on the framework's side
+__device__ __forceinline__ float inv_scale(float v, float norm, int centered) {
+    v = __fmul_rn(v, norm);
+    return centered ? __fadd_rn(v, 1.f) * 0.5f : v;
+}
+
+// one thread per (b, i): positions (P = 3; P = 0: the 2-D models' node tensor without them, pos unused), atom type, formal charge
+template <int P>
 __global__ __launch_bounds__(256) void k_decode_nodes(DecodeArgs A, const int* __restrict__ n_nodes, const float* __restrict__ xh,
                                                       float* __restrict__ pos, uint8_t* __restrict__ atom_type,
                                                       int8_t* __restrict__ fc) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= A.B * A.N) return;
     const int b = idx / A.N, i = idx % A.N;
-    const int F = 3 + A.atom_types + (A.include_fc ? 1 : 0);
+    const int F = P + A.atom_types + (A.include_fc ? 1 : 0);
     const float* r = xh + (size_t)idx * F;
     const bool real = i < n_nodes[b];
-    float* p = pos + (size_t)idx * 3;
-    for (int k = 0; k < 3; ++k) p[k] = real ? r[k] * A.pos_norm : 0.f;
+    if (P) {
+        float* p = pos + (size_t)idx * P;
+        for (int k = 0; k < P; ++k) p[k] = real ? r[k] * A.pos_norm : 0.f;
+    }
     // argmax over the inverse-scaled categories (an increasing affine map: same argmax; first maximum wins)
     int best = 0;
     float bv = -INFINITY;
     for (int k = 0; k < A.atom_types; ++k) {
-        float v = r[3 + k] * A.atom_norm;
-        if (A.centered) v = (v + 1.f) / 2.f;
+        float v = inv_scale(r[P + k], A.atom_norm, A.centered);
         if (!real) v = 0.f;
         if (v > bv) { bv = v; best = k; }
     }
@@ -194,8 +251,7 @@ __global__ __launch_bounds__(256) void k_decode_edges(DecodeArgs A, const int* _
     const float* r = ex + idx * A.ch;
     float h[4] = {0.f, 0.f, 0.f, 0.f};
     for (int k = 0; k < A.ch && k < 4; ++k) {
-        float v = r[k] * A.edge_norm;
-        if (A.centered) v = (v + 1.f) / 2.f;
+        const float v = inv_scale(r[k], A.edge_norm, A.centered);
         h[k] = real ? v : 0.f;
     }
     int t = 0;
@@ -278,6 +334,25 @@ extern "C" int jodo_sampler_step_rng(int B, int N, int node_feats, int edge_ch, 
         return jodo_set_error(JODO_ERR_ARG, "sampler_step_rng: pass both the device table and the step counter, or neither");
     return sampler_step_launch(B, N, node_feats, edge_ch, n_nodes_dev, c_x, c_pred, sigma, coef_tab_dev, step_dev, Rng{seed, draw, 1u, 1},
                                x, edge_x, pred, edge_pred, nullptr, nullptr, nullptr, x_next, edge_next, x_mean, edge_mean, stream);
+}
+
+extern "C" int jodo_sampler_step_2d_rng(int B, int N, int node_feats, int edge_ch, const int32_t* n_nodes_dev, float c_x, float c_pred,
+                                        float sigma, const float* coef_tab_dev, const int32_t* step_dev, uint64_t seed, uint32_t draw,
+                                        const float* x, const float* edge_x, const float* pred, const float* edge_pred, float* x_next,
+                                        float* edge_next, float* x_mean, float* edge_mean, void* stream) {
+    if (B <= 0 || N <= 0 || node_feats < 1 || edge_ch < 1) return jodo_set_error(JODO_ERR_ARG, "sampler_step_2d_rng: bad shape");
+    if (!n_nodes_dev || !x || !edge_x || !pred || !edge_pred || !x_next || !edge_next || !x_mean || !edge_mean)
+        return jodo_set_error(JODO_ERR_ARG, "sampler_step_2d_rng: null argument");
+    if ((coef_tab_dev == nullptr) != (step_dev == nullptr))
+        return jodo_set_error(JODO_ERR_ARG, "sampler_step_2d_rng: pass both the device table and the step counter, or neither");
+    if (edge_ch > 4 || node_feats > 256)
+        return jodo_set_error(JODO_ERR_UNSUPPORTED, "sampler_step_2d_rng: at most 4 edge channels and 256 node channels");
+    const size_t tot = (size_t)B * N * ((node_feats + 3) / 4) + (size_t)B * N * N;
+    if ((tot + 255) / 256 > 0x7fffffffull) return jodo_set_error(JODO_ERR_UNSUPPORTED, "sampler_step_2d_rng: batch too large for one launch");
+    hipLaunchKernelGGL(k_step_2d_rng, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, B, N, node_feats, edge_ch,
+                       n_nodes_dev, c_x, c_pred, sigma, coef_tab_dev, step_dev, Rng{seed, draw, 1u, 1}, x, edge_x, pred, edge_pred, x_next,
+                       edge_next, x_mean, edge_mean);
+    return jodo_check_launch("k_step_2d_rng");
 }
 
 extern "C" int jodo_step_begin(int B, const float* coef_tab_dev, const int32_t* step_dev, float* noise_level_out, void* stream) {
@@ -448,7 +523,25 @@ extern "C" int jodo_decode(int B, int N, int atom_types, int include_fc, int edg
         return jodo_set_error(JODO_ERR_ARG, "decode: null argument");
     DecodeArgs A{B, N, atom_types, include_fc, edge_ch, compress_edge, centered, pos_norm, atom_norm, fc_norm, edge_norm};
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_decode_nodes, dim3((B * N + 255) / 256), dim3(256), 0, st, A, n_nodes_dev, xh, pos_out, atom_type_out, fc_out);
+    hipLaunchKernelGGL(k_decode_nodes<3>, dim3((B * N + 255) / 256), dim3(256), 0, st, A, n_nodes_dev, xh, pos_out, atom_type_out, fc_out);
+    int rc = jodo_check_launch("k_decode_nodes");
+    if (rc != JODO_OK) return rc;
+    const size_t tot = (size_t)B * N * N;
+    hipLaunchKernelGGL(k_decode_edges, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, A, n_nodes_dev, edge_x, edge_type_out);
+    return jodo_check_launch("k_decode_edges");
+}
+
+extern "C" int jodo_decode_2d(int B, int N, int atom_types, int include_fc, int edge_ch, int compress_edge, int centered, float atom_norm,
+                              float fc_norm, float edge_norm, const int32_t* n_nodes_dev, const float* xh, const float* edge_x,
+                              uint8_t* atom_type_out, int8_t* fc_out, uint8_t* edge_type_out, void* stream) {
+    if (B <= 0 || N <= 0 || atom_types < 1 || atom_types > 255 || edge_ch < 1 || edge_ch > 4)
+        return jodo_set_error(JODO_ERR_ARG, "decode_2d: bad shape");
+    if (!n_nodes_dev || !xh || !edge_x || !atom_type_out || !fc_out || !edge_type_out)
+        return jodo_set_error(JODO_ERR_ARG, "decode_2d: null argument");
+    DecodeArgs A{B, N, atom_types, include_fc, edge_ch, compress_edge, centered, 1.f, atom_norm, fc_norm, edge_norm};
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_decode_nodes<0>, dim3((B * N + 255) / 256), dim3(256), 0, st, A, n_nodes_dev, xh, (float*)nullptr, atom_type_out,
+                       fc_out);
     int rc = jodo_check_launch("k_decode_nodes");
     if (rc != JODO_OK) return rc;
     const size_t tot = (size_t)B * N * N;

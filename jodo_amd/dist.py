@@ -9,6 +9,8 @@ slice of the batch, and the decoded results are gathered once per round over RCC
 Wire format per rank (padded to the global maxima so a single all_gather per tensor suffices):
   n_nodes [Bmax] i32 (0 = padding molecule), pos [Bmax,Nmax,3] f32, atom_type [Bmax,Nmax] u8,
   charge [Bmax,Nmax] i8, bond [Bmax,Nmax,Nmax] u8.
+The 2-D models have no positions: their rounds carry pos = None, no position collective runs and the
+molecule tuples come back with None first.
 """
 import torch
 import torch.distributed as dist
@@ -43,15 +45,17 @@ def _pad_to(t, shape):
 def gather_molecules(pos, atom_type, charge, bond, n_nodes, group=None):
     """All ranks call with their local decoded batch; returns on every rank a dict of concatenated
     tensors (rank order, padding molecules removed):
-      n_nodes [Btot], pos [Btot,Nmax,3], atom_type [Btot,Nmax], charge [Btot,Nmax], bond [Btot,Nmax,Nmax]."""
+      n_nodes [Btot], pos [Btot,Nmax,3], atom_type [Btot,Nmax], charge [Btot,Nmax], bond [Btot,Nmax,Nmax].
+    pos = None on every rank (2-D molecules): no position collective, and no 'pos' entry in the result."""
     world = dist.get_world_size(group)
-    dev = pos.device
-    dims = torch.tensor([pos.shape[0], pos.shape[1]], device=dev, dtype=torch.int64)
+    dev = atom_type.device
+    dims = torch.tensor([atom_type.shape[0], atom_type.shape[1]], device=dev, dtype=torch.int64)
     dist.all_reduce(dims, op=dist.ReduceOp.MAX, group=group)
     Bm, Nm = int(dims[0]), int(dims[1])
-    send = dict(n_nodes=_pad_to(n_nodes.to(torch.int32), (Bm,)),
-                pos=_pad_to(pos.float(), (Bm, Nm, 3)),
-                atom_type=_pad_to(atom_type.to(torch.uint8), (Bm, Nm)),
+    send = dict(n_nodes=_pad_to(n_nodes.to(torch.int32), (Bm,)))
+    if pos is not None:
+        send['pos'] = _pad_to(pos.float(), (Bm, Nm, 3))
+    send.update(atom_type=_pad_to(atom_type.to(torch.uint8), (Bm, Nm)),
                 charge=_pad_to(charge.to(torch.int8), (Bm, Nm)),
                 bond=_pad_to(bond.to(torch.uint8), (Bm, Nm, Nm)))
     out = {}
@@ -65,9 +69,14 @@ def gather_molecules(pos, atom_type, charge, bond, n_nodes, group=None):
 
 def unpack_molecules(g):
     """dict from gather_molecules -> list of (pos[n,3], atom_type[n], edge_type[n,n], fc[n]) CPU tuples,
-    the format evaluation code of the reference consumes (sampling.py:12-32)."""
+    the format evaluation code of the reference consumes (sampling.py:12-32); without a 'pos' entry (2-D molecules) the tuples are
+    (None, atom_type[n], edge_type[n,n], fc[n]) as mol_process_2D builds them (sampling.py:35-50; fc is zeros [n] for a model without
+    a charge channel: the wire format carries one charge per atom)."""
     n = g['n_nodes'].cpu().tolist()
-    pos, at, ch, bd = g['pos'].cpu(), g['atom_type'].cpu().long(), g['charge'].cpu().long(), g['bond'].cpu().float()
+    at, ch, bd = g['atom_type'].cpu().long(), g['charge'].cpu().long(), g['bond'].cpu().float()
+    if 'pos' not in g:
+        return [(None, at[i, :k], bd[i, :k, :k], ch[i, :k]) for i, k in enumerate(n)]
+    pos = g['pos'].cpu()
     return [(pos[i, :k], at[i, :k], bd[i, :k, :k], ch[i, :k]) for i, k in enumerate(n)]
 
 
@@ -75,29 +84,38 @@ def _cat_rounds(decoded):
     """Rounds of padded decoded tensors (sampling_fn.last_decoded) -> one padded batch, on the device they live on."""
     if not decoded:
         raise ValueError("gather_sampled: no decoded rounds (a rank with no molecules passes decoded=[] and device=...)")
-    N = max(int(r[0].shape[1]) for r in decoded)
+    N = max(int(r[1].shape[1]) for r in decoded)
     cat = lambda k, shape: torch.cat([_pad_to(r[k], (r[k].shape[0],) + shape) for r in decoded], dim=0)
-    return cat(0, (N, 3)), cat(1, (N,)), cat(2, (N,)), cat(3, (N, N)), torch.cat([r[4] for r in decoded], dim=0)
+    if any(r[0] is None for r in decoded):                     # 2-D rounds: no positions
+        if not all(r[0] is None for r in decoded):
+            raise ValueError("gather_sampled: rounds with and without positions cannot be mixed")
+        pos = None
+    else:
+        pos = cat(0, (N, 3))
+    return pos, cat(1, (N,)), cat(2, (N,)), cat(3, (N, N)), torch.cat([r[4] for r in decoded], dim=0)
 
 
-def gather_sampled(decoded, indices, device=None, group=None):
+def gather_sampled(decoded, indices, device=None, group=None, with_pos=True):
     """End-of-sampling collective for `get_sampling_fn(shard=...)`: every rank passes the decoded tensors of its rounds
     (`sampling_fn.last_decoded`: per round pos [B,N,3] f32, atom_type [B,N] u8, charge [B,N] i8, bond [B,N,N] u8, n_nodes [B] i32 —
     on the GPU box the outputs of jodo_decode, still on the device: nothing is re-packed on the host) and their global indices
     (`sampling_fn.last_indices`); returns, on every rank, the full list of molecule tuples (pos[n,3], atom_type[n],
     edge_type[n,n], fc[n]) in global order — the list an unsharded run would have produced.  One all_gather per tensor
-    (RCCL over xGMI with device tensors and the "nccl" backend; gloo with CPU tensors)."""
+    (RCCL over xGMI with device tensors and the "nccl" backend; gloo with CPU tensors).
+    Rounds of the 2-D sampling function carry None for pos: no position collective runs and the tuples are (None, atom_type[n],
+    edge_type[n,n], fc[n]).  with_pos matters only for a rank with decoded=[]: it passes with_pos=False in a 2-D run, so that it
+    joins the same collectives as the ranks that hold molecules."""
     if decoded:
         pos, at, ch, bd, n = _cat_rounds(decoded)
-        device = pos.device if device is None else torch.device(device)
-        if pos.device != device:
-            pos, at, ch, bd, n = (t.to(device) for t in (pos, at, ch, bd, n))
+        device = at.device if device is None else torch.device(device)
+        if at.device != device:
+            pos, at, ch, bd, n = (None if t is None else t.to(device) for t in (pos, at, ch, bd, n))
     else:                                                      # a rank whose share is empty still takes part in the collectives
         device = torch.device(device or 'cpu')
-        pos = torch.zeros(0, 1, 3, device=device)
+        pos = torch.zeros(0, 1, 3, device=device) if with_pos else None
         at, ch = torch.zeros(0, 1, dtype=torch.uint8, device=device), torch.zeros(0, 1, dtype=torch.int8, device=device)
         bd, n = torch.zeros(0, 1, 1, dtype=torch.uint8, device=device), torch.zeros(0, dtype=torch.int32, device=device)
-    B = int(pos.shape[0])
+    B = int(at.shape[0])
     if len(indices) != B:
         raise ValueError("gather_sampled: %d molecules but %d global indices" % (B, len(indices)))
     g = gather_molecules(pos, at, ch, bd, n, group=group)

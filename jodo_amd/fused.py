@@ -1,5 +1,5 @@
 """Python plumbing for the caller-side HIP kernels (csrc/sampler_kernels.hip): the fused ancestral update
-and the fused decode.  Device tensors in, device tensors out; raises (no CPU fallback) on CPU tensors —
+and the fused decode, for the 3-D + edge models and (the *_2d functions) the 2-D ones.  Device tensors in, device tensors out; raises (no CPU fallback) on CPU tensors —
 the callers in sampling.py pick the framework path themselves when they run on the CPU (host-logic tests).
 """
 import ctypes
@@ -132,6 +132,28 @@ def sampler_step_2d(n_nodes_dev, c_x, c_pred, sigma, x, edge_x, pred, edge_pred,
     return x_next, e_next, x_mean, e_mean
 
 
+def sampler_step_2d_rng(bufs, n_nodes_dev, c_x, c_pred, sigma, x, edge_x, pred, edge_pred, rng):
+    """The 2-D ancestral update with both draws generated inside the kernel (jodo_sampler_step_2d_rng, host-scalar form; rng = DeviceNoise,
+    one draw index per call) on the ping-pong `bufs` (StepBuffers): nothing is allocated per step.  Returns (x_next, edge_next, x_mean,
+    edge_mean); the returned tensors live in `bufs` and stay valid until the call after next."""
+    x, edge_x, pred, edge_pred = _f32c(x, 'x'), _f32c(edge_x, 'edge_x'), _f32c(pred, 'pred'), _f32c(edge_pred, 'edge_pred')
+    B, N, nd = x.shape
+    ch = edge_x.shape[-1]
+    if edge_x.shape != (B, N, N, ch) or pred.shape != x.shape or edge_pred.shape != edge_x.shape or bufs.x[0].shape != x.shape \
+            or bufs.e[0].shape != edge_x.shape:
+        raise ValueError("sampler_step_2d_rng: shape mismatch")
+    nxt = bufs.cur ^ 1
+    xn, en = bufs.x[nxt], bufs.e[nxt]
+    if xn.data_ptr() == x.data_ptr() or en.data_ptr() == edge_x.data_ptr():
+        raise RuntimeError("sampler_step_2d_rng: output buffer aliases the input state")
+    capi.check(capi.lib().jodo_sampler_step_2d_rng(
+        B, N, nd, ch, capi.ptr(n_nodes_dev), float(c_x), float(c_pred), float(sigma), None, None, rng.seed, rng.next_draw(),
+        capi.ptr(x), capi.ptr(edge_x), capi.ptr(pred), capi.ptr(edge_pred), capi.ptr(xn), capi.ptr(en), capi.ptr(bufs.x_mean),
+        capi.ptr(bufs.e_mean), capi.current_stream_ptr()), 'jodo_sampler_step_2d_rng')
+    bufs.cur = nxt
+    return xn, en, bufs.x_mean, bufs.e_mean
+
+
 def decode(config, xh, edge_x, n_nodes_dev):
     """post_process + inverse scaling on the device.  Returns compact device tensors
     (pos f32 [B,N,3], atom_type u8 [B,N], fc i8 [B,N], edge_type u8 [B,N,N])."""
@@ -165,6 +187,40 @@ def mols_from_decoded(pos, at, fc, et, n_nodes):
     for i, n in enumerate(n_nodes):
         n = int(n)
         mols.append((pos[i, :n], at[i, :n], et[i, :n, :n], fc[i, :n]))
+    return mols
+
+
+def decode_2d(config, xh, edge_x, n_nodes_dev):
+    """post_process_2D + inverse scaling on the device (jodo_decode_2d).  Returns compact device tensors
+    (atom_type u8 [B,N], fc i8 [B,N] — zeros when the config has no charge channel —, edge_type u8 [B,N,N])."""
+    xh, edge_x = _f32c(xh, 'xh'), _f32c(edge_x, 'edge_x')
+    B, N, F = xh.shape
+    atom_types = int(config.data.atom_types)
+    include_fc = int(bool(config.model.include_fc_charge))
+    if F != atom_types + include_fc or edge_x.shape[:3] != (B, N, N):
+        raise ValueError("xh has %d features, config says %d (edge_x %s)" % (F, atom_types + include_fc, tuple(edge_x.shape)))
+    nf = _norm_factors(config)
+    edge_norm = nf[3] if len(nf) > 3 else 1
+    dev = xh.device
+    at = torch.empty(B, N, dtype=torch.uint8, device=dev)
+    fc = torch.empty(B, N, dtype=torch.int8, device=dev)
+    et = torch.empty(B, N, N, dtype=torch.uint8, device=dev)
+    capi.check(capi.lib().jodo_decode_2d(
+        B, N, atom_types, include_fc, int(edge_x.shape[-1]), int(bool(config.data.compress_edge)), int(bool(config.data.centered)),
+        float(nf[1]), float(nf[2]), float(edge_norm), capi.ptr(n_nodes_dev), capi.ptr(xh), capi.ptr(edge_x), capi.ptr(at), capi.ptr(fc),
+        capi.ptr(et), capi.current_stream_ptr()), 'jodo_decode_2d')
+    return at, fc, et
+
+
+def mols_from_decoded_2d(at, fc, et, n_nodes, include_fc=True):
+    """One device->host copy per tensor, then per-molecule views in mol_process_2D's tuple format (None, atom_type[n] i64,
+    edge_type[n,n] f32, fc[n] i64) — sampling.py:35-50; without a charge channel fc is mol_process_2D's empty-charge form, a float32
+    [n, 0] (what post_process_2D makes of the empty charge tensor)."""
+    at, fc, et = at.cpu().long(), fc.cpu().long(), et.cpu().float()
+    mols = []
+    for i, n in enumerate(n_nodes):
+        n = int(n)
+        mols.append((None, at[i, :n], et[i, :n, :n], fc[i, :n] if include_fc else torch.zeros(n, 0)))
     return mols
 
 

@@ -16,8 +16,11 @@ Additions that do not change the reference behaviour:
 
 The 2-D experiments (`config.only_2D`, model DGT_concat_2D): `AncestralSampler_2D` (:599-660), `post_process_2D` (:100-141),
 `mol_process_2D` (:35-50) and the 2-D sampling function of `get_sampling_fn` (:234-276), with the reference's RNG use.  The
-additions above are not built for the 2-D path: `shard=`, `hip_graph=True`, `device_noise=True` and `method='fast'` raise
-NotImplementedError there; `cpu_noise=True` (2-D only) makes every draw on the CPU generator in the reference's shapes and order.
+additions above exist for the 2-D path on a GPU device: `shard=` (both modes, both assignments), `device_noise=True` (both draws of a
+step inside jodo_sampler_step_2d_rng), `hip_graph=True` (GraphedAncestralRound2D; needs device noise) and the device decode
+(jodo_decode_2d); on a CPU `config.device` they raise NotImplementedError like the model itself (no CPU fallback).  `method='fast'`
+raises: the reference has no DPM-solver for 2-D graphs.  `cpu_noise=True` (2-D only) makes every draw on the CPU generator in the
+reference's shapes and order.
 """
 import random
 
@@ -179,6 +182,15 @@ class _ParityNoise:
         return {'node': self.node, 'edge': self.edge, 'pos': self.pos}[kind]()
 
 
+class _ParityNoise2D(_ParityNoise):
+    """_ParityNoise for the 2-D sampling function: node draws are plain masked Gaussians [bs, N, node_nf] (no position channels, no
+    centre-of-mass step), then the symmetric edge draw — shapes and order of `sampling_fn_2D` (sampling.py:234-276) and of
+    AncestralSampler_2D's steps."""
+
+    def node(self):
+        return self._cut(sample_gaussian_with_mask((self.bs, self.N, self.node_nf), 'cpu', self.nm), 1)
+
+
 def get_sampling_fn(config, noise_scheduler, nodes_dist, batch_size, n_samples, inverse_scaler, eps=1e-3,
                     prop_dist=None, shard=None, return_raw=False, fused_decode=True, hip_graph=False,
                     shard_mode='perf', shard_assign='contiguous', seed=None, device_noise=None, cpu_noise=False):
@@ -216,8 +228,15 @@ def get_sampling_fn(config, noise_scheduler, nodes_dist, batch_size, n_samples, 
     if not pred_edge:
         raise NotImplementedError("only the edge-predicting sampling paths (3-D + edge, 2-D) are in scope")
     if config.only_2D:
+        if torch.device(device).type != 'cuda':
+            # DGT_concat_2D has no CPU fallback, and neither have the round's options that exist for it
+            for name, val in (('shard', shard is not None), ('hip_graph', bool(hip_graph)), ('device_noise', bool(device_noise))):
+                if val:
+                    raise NotImplementedError("%s on the 2-D sampling path (config.only_2D) needs a GPU device: config.device is %s and "
+                                              "there is no CPU fallback" % (name, device))
         return _get_sampling_fn_2d(config, noise_scheduler, nodes_dist, batch_size, n_samples, inverse_scaler, eps, shard=shard,
-                                   return_raw=return_raw, hip_graph=hip_graph, device_noise=device_noise, cpu_noise=cpu_noise)
+                                   return_raw=return_raw, hip_graph=hip_graph, device_noise=device_noise, cpu_noise=cpu_noise,
+                                   shard_mode=shard_mode, shard_assign=shard_assign, seed=seed, fused_decode=fused_decode)
     if cpu_noise:
         raise ValueError("cpu_noise is an option of the 2-D sampling function; the 3-D path replays CPU draws with shard_mode='parity'")
     if shard_mode not in ('perf', 'parity') or shard_assign not in ('contiguous', 'lpt'):
@@ -361,60 +380,159 @@ def get_sampling_fn(config, noise_scheduler, nodes_dist, batch_size, n_samples, 
 
 
 def _get_sampling_fn_2d(config, noise_scheduler, nodes_dist, batch_size, n_samples, inverse_scaler, eps, shard=None, return_raw=False,
-                        hip_graph=False, device_noise=None, cpu_noise=False):
+                        hip_graph=False, device_noise=None, cpu_noise=False, shard_mode='perf', shard_assign='contiguous', seed=None,
+                        fused_decode=True):
     """sampling.py:234-276 (`sampling_fn_2D`): atom counts for all rounds first, then per round z = sample_gaussian_with_mask,
     symmetric edge noise, AncestralSampler_2D, post_process_2D, mol_process_2D; `random.shuffle` at the end.  cpu_noise: every draw
     is made by the CPU generator (reference shapes and order) and copied to the device, so that a seeded run reproduces the CPU
-    reference's noise stream on the GPU (tests)."""
-    for name, val in (('shard', shard is not None), ('hip_graph', bool(hip_graph)), ('device_noise', bool(device_noise))):
-        if val:
-            raise NotImplementedError("%s is not implemented for the 2-D sampling path (config.only_2D)" % name)
+    reference's noise stream on the GPU (tests).
+
+    shard / shard_mode / shard_assign / seed / device_noise / hip_graph / fused_decode: as documented on get_sampling_fn, with the 2-D
+    draws (_ParityNoise2D; jodo_sampler_step_2d_rng keyed by DeviceNoise.for_rank(seed, rank, round)) and GraphedAncestralRound2D.
+    device_noise defaults to on with hip_graph (the captured step cannot hold torch's generator) and with shard in 'perf' mode; it
+    is ignored on CPU tensors, where an explicit device_noise=True or hip_graph=True is refused — as is every option through the
+    public entry on a CPU config.device; this builder takes shard= with torch-drawn noise on the CPU (host tests with a CPU model).
+    The initial z / edge_z stay torch draws.  `sampling_fn.last_indices` / `last_decoded` as in the 3-D path; a round's decoded tuple
+    is (None, atom_type [B,N] u8, charge [B,N] i8, bond [B,N,N] u8, n_nodes [B] i32)."""
     if config.sampling.method == 'fast':
         raise NotImplementedError("sampling.method='fast' (DPM-solver) is not implemented for the 2-D sampling path")
     if config.sampling.method != 'ancestral':
         raise ValueError('Invalid sampling method!')
     device = config.device
+    on_gpu = torch.device(device).type == 'cuda'
+    for name, val in (('hip_graph', bool(hip_graph)), ('device_noise', bool(device_noise))):
+        if val and not on_gpu:
+            raise NotImplementedError("%s on the 2-D sampling path (config.only_2D) needs a GPU device: config.device is %s and there "
+                                      "is no CPU fallback" % (name, device))
+    if shard_mode not in ('perf', 'parity') or shard_assign not in ('contiguous', 'lpt'):
+        raise ValueError("shard_mode in {'perf','parity'}, shard_assign in {'contiguous','lpt'}")
+    if shard is not None and not (0 <= shard[0] < shard[1]):
+        raise ValueError("shard=(rank, world) with 0 <= rank < world")
+    replayed = cpu_noise or (shard is not None and shard_mode == 'parity')
+    if hip_graph and (replayed or (device_noise is not None and not device_noise)):
+        raise ValueError("hip_graph=True needs device noise: the captured step draws inside the update kernel (not with "
+                         "device_noise=False, cpu_noise=True or shard_mode='parity')")
+    if cpu_noise and (shard is not None or device_noise):
+        raise ValueError("cpu_noise replays the unsharded run's CPU draws; a sharded run does that with shard_mode='parity'")
+    if device_noise is None:
+        device_noise = bool(hip_graph) or (shard is not None and shard_mode == 'perf')
     atom_types = config.data.atom_types
     include_fc = config.model.include_fc_charge
     node_nf = atom_types + int(include_fc)
     edge_nf = config.model.edge_ch
     compress_edge = config.data.compress_edge
+    steps = config.sampling.steps
     rounds = int(np.ceil(n_samples / batch_size))
-    time_steps = torch.linspace(noise_scheduler.T, eps, config.sampling.steps)      # host scalars, as in the 3-D path
+    round_counter = [0]
+    decoded_rounds = []          # per round of a sharded run: (None, atom_type [B,N] u8, charge [B,N] i8, bond [B,N,N] u8, n_nodes [B] i32)
+    time_steps = torch.linspace(noise_scheduler.T, eps, steps)      # host scalars, as in the 3-D path
     sampler = AncestralSampler_2D(noise_scheduler, time_steps, config.model.pred_data, config.model.self_cond)
+
+    def one_round(model, n_nodes, noise=None):
+        """n_nodes molecules (this process's share of a round) -> list of decoded molecule tuples."""
+        bs = len(n_nodes)
+        max_n = int(max(n_nodes))
+        node_mask, edge_mask = build_masks(n_nodes, max_n, device)
+        if noise is not None:
+            z, edge_z = noise.node(), noise.edge()
+            sampler.noise_fn = noise
+        elif cpu_noise:
+            nm_c, em_c = build_masks(n_nodes, max_n, 'cpu')
+            z = sample_gaussian_with_mask((bs, max_n, node_nf), 'cpu', nm_c).to(device)
+            edge_z = sample_symmetric_edge_feature_noise(bs, max_n, edge_nf, em_c).to(device)
+            sampler.noise_fn = lambda i, kind, like: (
+                sample_gaussian_with_mask(tuple(like.shape), 'cpu', nm_c) if kind == 'node'
+                else sample_symmetric_edge_feature_noise(like.shape[0], like.shape[1], like.shape[-1], em_c)).to(like.device)
+        else:
+            z = sample_gaussian_with_mask((bs, max_n, node_nf), device, node_mask)
+            edge_z = sample_symmetric_edge_feature_noise(bs, max_n, edge_nf, edge_mask)
+        sampler.device_noise = None
+        if device_noise and sampler.noise_fn is None and z.is_cuda:
+            from . import fused
+            sampler.device_noise = fused.DeviceNoise.for_rank(int(config.seed if seed is None else seed),
+                                                              shard[0] if shard is not None else 0, round_counter[0])
+        round_counter[0] += 1
+        try:
+            if hip_graph:
+                # one captured HIP graph per round, replayed for every step (jodo_amd/graphed.py)
+                from .graphed import GraphedAncestralRound2D
+                x_node, x_edge = GraphedAncestralRound2D(sampler, model, node_mask, edge_mask).run(z, edge_z)
+            else:
+                x_node, x_edge = sampler.sampling(model, z, node_mask, edge_mask, edge_z, None)
+        finally:
+            sampler.noise_fn = None
+            sampler.device_noise = None
+        if x_node.is_cuda and fused_decode and getattr(inverse_scaler, 'from_config', False):
+            # device-side decode: compact u8/i8 results, one device->host copy per tensor
+            from . import fused
+            nd = fused.n_nodes_from_mask(node_mask)
+            dec = fused.decode_2d(config, x_node, x_edge, nd)
+            if shard is not None:                              # the gather takes the decoded DEVICE tensors as they are (dist.gather_sampled)
+                decoded_rounds.append((None,) + dec + (nd,))
+            return fused.mols_from_decoded_2d(*dec, n_nodes, include_fc=include_fc)
+        one_hot, fc, edge_types = post_process_2D(x_node, atom_types, include_fc, node_mask, inverse_scaler, x_edge, edge_mask,
+                                                  compress_edge)
+        if shard is not None:
+            fcq = fc[..., 0] if fc.shape[-1] != 0 else torch.zeros(fc.shape[:2], device=fc.device)
+            decoded_rounds.append((None, one_hot.argmax(2).to(torch.uint8), fcq.round().to(torch.int8), edge_types.to(torch.uint8),
+                                   torch.as_tensor([int(n) for n in n_nodes], dtype=torch.int32, device=one_hot.device)))
+        return mol_process_2D(one_hot, fc, n_nodes, edge_types)
 
     def sampling_fn_2D(model):
         model.eval()
         mols = []
+        del decoded_rounds[:]
+        sampling_fn_2D.last_decoded = decoded_rounds
+        total = rounds * batch_size
         with torch.no_grad():
-            n_nodes_all = nodes_dist.sample(rounds * batch_size)
-            for r in range(rounds):
-                n_nodes = n_nodes_all[r * batch_size:(r + 1) * batch_size]
-                max_n = int(max(n_nodes))
-                node_mask, edge_mask = build_masks(n_nodes, max_n, device)
-                if cpu_noise:
-                    nm_c, em_c = build_masks(n_nodes, max_n, 'cpu')
-                    z = sample_gaussian_with_mask((batch_size, max_n, node_nf), 'cpu', nm_c).to(device)
-                    edge_z = sample_symmetric_edge_feature_noise(batch_size, max_n, edge_nf, em_c).to(device)
-                    sampler.noise_fn = lambda i, kind, like: (
-                        sample_gaussian_with_mask(tuple(like.shape), 'cpu', nm_c) if kind == 'node'
-                        else sample_symmetric_edge_feature_noise(like.shape[0], like.shape[1], like.shape[-1], em_c)).to(like.device)
-                else:
-                    z = sample_gaussian_with_mask((batch_size, max_n, node_nf), device, node_mask)
-                    edge_z = sample_symmetric_edge_feature_noise(batch_size, max_n, edge_nf, edge_mask)
-                try:
-                    x_node, x_edge = sampler.sampling(model, z, node_mask, edge_mask, edge_z, None)
-                finally:
-                    sampler.noise_fn = None
-                one_hot, fc, edge_types = post_process_2D(x_node, atom_types, include_fc, node_mask, inverse_scaler, x_edge,
-                                                          edge_mask, compress_edge)
-                mols += mol_process_2D(one_hot, fc, n_nodes, edge_types)
-                print('Generate {}, Total {}.'.format(len(mols), n_samples))
-        if return_raw:
-            return mols
-        random.shuffle(mols)
-        return mols[:n_samples]
+            if shard is None:                                  # the reference's procedure
+                n_nodes_all = nodes_dist.sample(total)
+                for r in range(rounds):
+                    mols += one_round(model, n_nodes_all[r * batch_size:(r + 1) * batch_size])
+                    print('Generate {}, Total {}.'.format(len(mols), n_samples))
+                sampling_fn_2D.last_indices = list(range(total))
+                if return_raw:
+                    return mols
+                random.shuffle(mols)
+                return mols[:n_samples]
 
+            rank, world = shard
+            base = int(config.seed if seed is None else seed)
+            torch.manual_seed(base)                            # identical on every rank
+            n_nodes_all = nodes_dist.sample(total)
+            if shard_mode == 'perf':
+                from .dist import assign_lpt, shard_range
+                if shard_assign == 'lpt':
+                    mine = assign_lpt(n_nodes_all.tolist(), world)[rank]
+                else:
+                    lo, hi = shard_range(total, rank, world)
+                    mine = list(range(lo, hi))
+                from .fused import mix64
+                torch.manual_seed(mix64(base, 1 + rank) >> 1)  # this rank's own stream, as in the 3-D path (INTEGRATION.md §3)
+                for r0 in range(0, len(mine), batch_size):
+                    idx = torch.as_tensor(mine[r0:r0 + batch_size], dtype=torch.long)
+                    mols += one_round(model, n_nodes_all[idx])
+                    if rank == 0:
+                        print('Generate {} on rank 0, Total {}.'.format(len(mols), n_samples))
+                sampling_fn_2D.last_indices = list(mine)
+            else:                                              # parity: replay the unsharded run's draws
+                from .dist import shard_range
+                indices = []
+                for r in range(rounds):
+                    n_nodes = n_nodes_all[r * batch_size:(r + 1) * batch_size]
+                    lo, hi = shard_range(len(n_nodes), rank, world)
+                    noise = _ParityNoise2D(n_nodes.tolist(), lo, hi, node_nf, edge_nf, device)
+                    if hi == lo:                               # nothing of this round is ours: stay in step with the stream
+                        for _ in range(steps + 1):
+                            noise.node(); noise.edge()
+                        continue
+                    mols += one_round(model, n_nodes[lo:hi], noise)
+                    indices += list(range(r * batch_size + lo, r * batch_size + hi))
+                sampling_fn_2D.last_indices = indices
+        return mols                                            # caller gathers / shuffles
+
+    sampling_fn_2D.last_indices = None
+    sampling_fn_2D.last_decoded = decoded_rounds
     return sampling_fn_2D
 
 
@@ -643,10 +761,13 @@ class AncestralSampler_2D:
     """Ancestral sampler without 3-D positions (sampling.py:599-660): every node channel gets plain masked Gaussian noise, the edge
     noise is symmetric; returns the noise-free mean of the last step.  `noise_fn(step, kind, like)` replays recorded draws
     ('node' / 'edge', in the reference's draw order).  On GPU tensors with a data-predicting model the update runs as one HIP
-    kernel (jodo_sampler_step_2d) fed with the same draws."""
+    kernel (jodo_sampler_step_2d) fed with the same draws.  `device_noise` (a fused.DeviceNoise or None): on GPU tensors with a
+    data-predicting model both draws are generated inside the update kernel instead (jodo_sampler_step_2d_rng, one draw index per
+    step; same distribution, not the reference's stream); `noise_fn` wins over it."""
 
-    def __init__(self, noise_scheduler, time_steps, model_pred_data, self_cond=False, noise_fn=None, fused=True):
+    def __init__(self, noise_scheduler, time_steps, model_pred_data, self_cond=False, noise_fn=None, fused=True, device_noise=None):
         self.noise_scheduler = noise_scheduler
+        self.device_noise = device_noise
         self.t_array = time_steps
         self.s_array = torch.cat([time_steps[1:], torch.zeros(1, device=time_steps.device)])
         self.model_pred_data = model_pred_data
@@ -683,6 +804,12 @@ class AncestralSampler_2D:
             from . import fused
             if st.get('_n_nodes') is None:
                 st['_n_nodes'] = fused.n_nodes_from_mask(node_mask)
+            if self.noise_fn is None and self.device_noise is not None:           # drawn inside the kernel (Philox)
+                if st.get('_bufs') is None:
+                    st['_bufs'] = fused.StepBuffers(x, edge_x)
+                st['x'], st['edge_x'], st['x_mean'], st['edge_x_mean'] = fused.sampler_step_2d_rng(
+                    st['_bufs'], st['_n_nodes'], float(c_x), float(c_pred), float(sigma), x, edge_x, pred_t, edge_pred_t, self.device_noise)
+                return st
             eps_n, eps_e = self._noise(i, x, edge_x, node_mask, edge_mask)
             st['x'], st['edge_x'], st['x_mean'], st['edge_x_mean'] = fused.sampler_step_2d(
                 st['_n_nodes'], float(c_x), float(c_pred), float(sigma), x, edge_x, pred_t, edge_pred_t, eps_n, eps_e)

@@ -3,10 +3,22 @@ user without the HIP path would run on the same GPU: the dense torch evaluation 
 device, chunked by molecules to fit memory, under the same sampler.
 
     python tools/bench_2d.py --workload zinc|moses [--batch 2000] [--steps 20] [--warmup 3] [--baseline-steps 3] [--no-baseline]
+    python tools/bench_2d.py --workload zinc|moses --round [--steps 1000] [--batches 2000,128] [--forms a,b,c,cd] [--repeat 1]
+                             [--parent-json FILE] [--out profiles/dgt2d_round_zinc.json]
 
 Atom counts are drawn from the training histogram (tests/golden/n_nodes_2d.json, seed 42).  Timing as bench.py does it: warm-up,
 synchronise, `steps` sampler.step calls, synchronise.  Prints one JSON line: ms/step, molecules/s at 1000 steps, the directed-edge
 count, ns per directed edge per step, and the same for the torch baseline with the ratio.
+
+--round: ONE complete sampling round of `--steps` steps per batch size and form, timed from the initial state to the last step
+(weights packed by a 3-step round before; plan creation and graph capture are inside the timed round):
+    a   eager, torch draws — what AncestralSampler_2D.sampling did before in-kernel noise existed; its host decode
+        (post_process_2D + mol_process_2D) is timed separately
+    b   eager, both draws of a step inside jodo_sampler_step_2d_rng
+    c   one captured step replayed (GraphedAncestralRound2D), in-kernel draws
+    cd  c plus the device decode (jodo_decode_2d) and the per-molecule host tuples
+Form a uses nothing newer than the sampler itself, so this file copied into a checkout of an older commit measures that commit
+(`--forms a --repeat 2`); `--parent-json` embeds such a record, with the spread of its runs, next to this run's numbers.
 """
 import argparse
 import json
@@ -63,16 +75,107 @@ def time_steps(sampler, model, z, edge_z, node_mask, edge_mask, warmup, steps):
     return (time.perf_counter() - t0) / steps * 1e3, st
 
 
+def _setup(workload, batch, dev):
+    cfg_name, info = WORKLOADS[workload]
+    cfg = configs.get(cfg_name)
+    torch.manual_seed(42)
+    n_nodes = get_node_dist(O2.load_n_nodes_hist(os.path.join(ROOT, 'tests', 'golden', 'n_nodes_2d.json'), info)).sample(batch).tolist()
+    N = max(n_nodes)
+    node_mask, edge_mask = build_masks(n_nodes, N, dev)
+    nd = cfg.data.atom_types + int(cfg.model.include_fc_charge)
+    z = sample_gaussian_with_mask((batch, N, nd), dev, node_mask)
+    edge_z = sample_symmetric_edge_feature_noise(batch, N, cfg.model.edge_ch, edge_mask)
+    return cfg, n_nodes, node_mask, edge_mask, z, edge_z
+
+
+def _one_round(form, cfg, model, ns, steps, n_nodes, node_mask, edge_mask, z, edge_z):
+    """-> (seconds of the loop, seconds of the decode or None, finite)"""
+    from jodo_amd import sampling as S
+    from jodo_amd.utils import get_data_inverse_scaler
+    sampler = AncestralSampler_2D(ns, torch.linspace(ns.T, 1e-3, steps), True, True)
+    if form != 'a':
+        from jodo_amd import fused
+        sampler.device_noise = fused.DeviceNoise.for_rank(42, 0, 0)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    with torch.no_grad():
+        if form in ('c', 'cd'):
+            from jodo_amd.graphed import GraphedAncestralRound2D
+            x, e = GraphedAncestralRound2D(sampler, model, node_mask, edge_mask).run(z, edge_z)
+        else:
+            x, e = sampler.sampling(model, z, node_mask, edge_mask, edge_z, None)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        dec = None
+        if form == 'a':
+            one_hot, fc, et = S.post_process_2D(x, cfg.data.atom_types, cfg.model.include_fc_charge, node_mask, get_data_inverse_scaler(cfg), e,
+                                                edge_mask, cfg.data.compress_edge)
+            mols = S.mol_process_2D(one_hot, fc, n_nodes, et)
+            dec = time.perf_counter() - t1
+        elif form == 'cd':
+            mols = fused.mols_from_decoded_2d(*fused.decode_2d(cfg, x, e, fused.n_nodes_from_mask(node_mask)), n_nodes,
+                                              include_fc=cfg.model.include_fc_charge)
+            dec = time.perf_counter() - t1
+        assert dec is None or len(mols) == len(n_nodes)
+    return t1 - t0, dec, bool(torch.isfinite(x).all() and torch.isfinite(e).all())
+
+
+def round_leg(args):
+    torch.set_num_threads(8)
+    dev = torch.device('cuda:0')
+    cfg_name, _ = WORKLOADS[args.workload]
+    model = deterministic_init_(get_model_class('DGT_concat_2D')(configs.get(cfg_name)), seed=7).to(dev).eval()
+    out = dict(workload=args.workload, config=cfg_name, steps=args.steps, forms={
+        'a': 'eager, torch draws', 'b': 'eager, in-kernel draws', 'c': 'graph replay, in-kernel draws', 'cd': 'c + device decode'}, batches={})
+    for batch in [int(b) for b in args.batches.split(',')]:
+        cfg, n_nodes, node_mask, edge_mask, z, edge_z = _setup(args.workload, batch, dev)
+        ns = NoiseScheduleVP(cfg.sde.schedule, continuous_beta_0=cfg.sde.continuous_beta_0, continuous_beta_1=cfg.sde.continuous_beta_1)
+        _one_round('a', cfg, model, ns, 3, n_nodes, node_mask, edge_mask, z, edge_z)           # packs the weights, loads the kernels
+        rec = {}
+        for form in args.forms.split(','):
+            runs = []
+            for _ in range(args.repeat):
+                loop, dec, finite = _one_round(form, cfg, model, ns, args.steps, n_nodes, node_mask, edge_mask, z, edge_z)
+                total = loop + (dec or 0.0)
+                runs.append(dict(ms_per_step=round(loop / args.steps * 1e3, 4), round_s=round(loop, 3),
+                                 decode_ms=None if dec is None else round(dec * 1e3, 2), molecules_per_s=round(batch / total, 2), finite=finite))
+                print(json.dumps(dict(batch=batch, form=form, **runs[-1])), flush=True)
+            rec[form] = runs[0] if args.repeat == 1 else dict(runs=runs, ms_per_step=round(sum(r['ms_per_step'] for r in runs) / len(runs), 4),
+                                                               spread_ms_per_step=round(max(r['ms_per_step'] for r in runs) - min(r['ms_per_step'] for r in runs), 4))
+        if 'a' in rec and 'c' in rec:
+            rec['c_over_a'] = round(rec['c']['ms_per_step'] / rec['a']['ms_per_step'], 4)
+        out['batches'][str(batch)] = dict(max_n=max(n_nodes), atoms=sum(n_nodes), **rec)
+    if args.parent_json:
+        with open(args.parent_json) as f:
+            out['parent_commit'] = json.load(f)
+    print(json.dumps(out))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, 'w') as f:
+            json.dump(out, f, indent=1)
+            f.write('\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--round', action='store_true', help='time complete sampling rounds in the forms a, b, c, cd (see the module docstring)')
+    ap.add_argument('--batches', default='2000,128')
+    ap.add_argument('--forms', default='a,b,c,cd')
+    ap.add_argument('--repeat', type=int, default=1)
+    ap.add_argument('--parent-json', default=None)
+    ap.add_argument('--out', default=None)
     ap.add_argument('--workload', choices=sorted(WORKLOADS), default='zinc')
     ap.add_argument('--batch', type=int, default=2000)
-    ap.add_argument('--steps', type=int, default=20)
+    ap.add_argument('--steps', type=int, default=None, help='default 20; 1000 with --round')
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--baseline-steps', type=int, default=3)
     ap.add_argument('--baseline-chunk', type=int, default=250)
     ap.add_argument('--no-baseline', action='store_true')
     args = ap.parse_args()
+    if args.steps is None:
+        args.steps = 1000 if args.round else 20
+    if args.round:
+        return round_leg(args)
     torch.set_num_threads(8)
     dev = torch.device('cuda:0')
     cfg_name, info = WORKLOADS[args.workload]
