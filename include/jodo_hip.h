@@ -474,6 +474,36 @@ int jodo_decode_2d(int B, int N, int atom_types, int include_fc, int edge_ch, in
                    float fc_norm, float edge_norm, const int32_t* n_nodes_dev, const float* xh, const float* edge_x,
                    uint8_t* atom_type_out, int8_t* fc_out, uint8_t* edge_type_out, void* stream);
 
+/* ---- training step of the 2-D model (csrc/dgt2d_train.hip) ---------------------------------------------------------------------
+ * jodo_train2d_* mirror jodo_train_* one for one (same conventions: parameters by name in PyTorch layouts, workspace kept by the
+ * caller between forward and backward, gradients fully written — bytes in gaps under 16 bytes between two gradient buffers included —
+ * in a fixed launch order without atomics) for DGT_concat_2D: the grad-enabled model call of get_sde_2D_loss_fn (losses.py:210-283)
+ * and its loss.backward().  Dense directed n x n tiles per molecule like the 3-D engine (the reference draws the edge FFN's dropout per
+ * directed edge).  xh [B,N,nd], edge_x [B,N,N,ch], cond_x / cond_edge_x both given or both NULL, noise_level [B]; `context` must be
+ * NULL.  Dropout: the 3-D path's four sites and element numbering (site = 8 l + 1 .. 4, edge element = row of the dense tile).
+ * jodo_train2d_set_option: 0 / 1 = fused forward / backward chains (csrc/train_fused.hip k2d_chain_a, k2d_bwd_a, chain B / B', node
+ * LayerNorms): 0 (default: one launch per operation) / 1 (JODO_ERR_UNSUPPORTED for widths the chains are not built for);
+ * 2 = 1 (default) / 0 the following forwards are (not) followed by a backward (the fused chains then skip backward-only stores).
+ * jodo_train2d_debug_locate: selectors 0 .. 7 as jodo_train_debug_locate; 8 = xhat of the edges' LayerNorm1 [R, De], 9 = its rstd [R],
+ * 10 = et [R, De], 11 = t0 = tanh(lin_edge0 et) [R, QK], 12 = t1 = tanh(lin_edge1 et) [R, D]. */
+typedef struct jodo_train2d jodo_train2d;
+int jodo_train2d_create(const jodo_cfg2d* cfg, int B, int N, const int32_t* n_nodes_host, const jodo_tensor* params, int n_params,
+                        jodo_train2d** out);
+void jodo_train2d_destroy(jodo_train2d* t);
+size_t jodo_train2d_desc_bytes(const jodo_train2d* t);
+size_t jodo_train2d_workspace_bytes(const jodo_train2d* t);
+const void* jodo_train2d_desc_host(const jodo_train2d* t);
+int jodo_train2d_upload(jodo_train2d* t, void* desc_dev, void* stream);
+int jodo_train2d_set_option(jodo_train2d* t, int option, int value);
+int jodo_train2d_debug_locate(const jodo_train2d* t, int what, int layer, size_t* byte_offset, size_t* count);
+int jodo_train2d_forward(jodo_train2d* t, const void* desc_dev, const float* const* params_dev, int n_params, const float* xh,
+                         const float* edge_x, const float* cond_x, const float* cond_edge_x, const float* noise_level,
+                         const float* context, float dropout_p, uint64_t seed, float* out_xh, float* out_edge, int32_t* flags_out,
+                         void* workspace, void* stream);
+int jodo_train2d_backward(jodo_train2d* t, const void* desc_dev, const float* const* params_dev, float* const* grads_dev, int n_params,
+                          const float* noise_level, const float* d_out_xh, const float* d_out_edge, float dropout_p, uint64_t seed,
+                          void* workspace, void* stream);
+
 const char* jodo_last_error(void);
 
 /* measurement helper (synchronises, default stream): fp32 MFMA throughput of the box in TFLOP/s from a

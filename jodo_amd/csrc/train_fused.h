@@ -68,6 +68,20 @@ void fused_bwd_b(hipStream_t s, const FusedDims& d, const FusedTopo& t, const Fu
 void fused_bwd_a(hipStream_t s, const FusedDims& d, const FusedTopo& t, const FusedBlockParams& p, const float* packed, const float* dt1, const float* dt0,
                  const float* xh_e1, const float* rs_e1, const float* emod, float* det, float* de1, float* dG, float* de_prev);
 
+// ---- the 2-D model (DGT_concat_2D, dgt2d_train.hip): LayerNorm1 acts on e directly (no Gaussian basis, no per-block edge_emb) and
+// QK = 255.  Chain B / B' and the node-row kernels above are used as they are; chain B has a predicate of its own because
+// fused_available's conditions on QK do not concern it.  Operand images at the offsets of fused_pack_layout.
+bool fused_chain_b_available(const FusedDims& d);
+bool fused2d_available(const FusedDims& d);
+void fused2d_pack_block(hipStream_t s, const FusedDims& d, const FusedBlockParams& p, float* packed);       // le0, le1, ff3_w, ff4_w, ero_w
+void fused2d_pack_block_bwd(hipStream_t s, const FusedDims& d, const FusedBlockParams& p, float* packed);   // transposed ff4_w, ff3_w, le1, le0
+// chain A (2-D): LayerNorm1 -> modulate -> tanh(lin_edge0 .) [R, QK], tanh(lin_edge1 .) [R, D]; xhat, rstd, et stored when t.save
+void fused2d_chain_a(hipStream_t s, const FusedDims& d, const FusedTopo& t, const float* packed, const float* e_in, const float* emod, float* xh_e1,
+                     float* rs_e1, float* et, float* t0, float* t1);
+// chain A' (2-D): det = lin_edge1^T dt1 + lin_edge0^T dt0 (stored: the modulation sums read it) -> LayerNorm1 + modulate backward -> de_prev +=
+void fused2d_bwd_a(hipStream_t s, const FusedDims& d, const FusedTopo& t, const float* packed, const float* dt1, const float* dt0, const float* xh_e1,
+                   const float* rs_e1, const float* emod, float* det, float* de_prev);
+
 // ---- node rows (F = D in {128, 256, 384}): LayerNorm + modulate with its row statistics in one launch, one wave per row.
 // forward:  x = res_b ? a + mods[mol, g_off + f] res_b : a;  xhat, rstd kept;  y = xhat (1 + mods[mol, sc_off + f]) + mods[mol, sh_off + f]
 void fused_node_ln_mod(hipStream_t s, long rows, int F, const float* a, const float* res_b, const int* row_mol, const float* mods, int ldm, int g_off,

@@ -542,6 +542,118 @@ __global__ __launch_bounds__(64, 1) void k_bwd_a(ArgsBA A) {
     }
 }
 
+// ---- the 2-D model's chain A and A' (DGT_concat_2D: no Gaussian basis and no per-block edge_emb in front of LayerNorm1; QK = 255 is odd,
+// so rows of t0 / dt0 are only 4-byte aligned and take scalar accesses with a bound on the padded 256th column, which is never stored)
+struct Args2A {
+    Common c;
+    const float *e_in, *emod;
+    float *xh, *rs, *et, *t0, *t1;
+    int QK;
+};
+
+template <int D>
+__global__ __launch_bounds__(64, 1) void k2d_chain_a(Args2A A) {
+    using X = FD<D>;
+    const int lane = threadIdx.x & 63, j = lane & 31, half = lane >> 5;
+    const long r = (long)blockIdx.x * 32 + j;
+    const bool valid = r < A.c.R;
+    const long rc = valid ? r : (long)A.c.R - 1;
+    const int mol = A.c.em[rc];
+    const bool keep = valid && A.c.save != 0;
+    const WSrc ws = make_wsrc(A.c.packed, lane);
+    WPipe<X::PG> wp;
+    wpipe_prime(wp, ws, A.c.oL0);
+    float x[X::HE];
+    load_nat<X::NE>(A.e_in + rc * X::De, half, x);
+    const float rstd = layer_norm_rs<X::HE>(x);
+    if (keep) {
+        store_nat<X::NE>(A.xh + r * X::De, half, x);
+        if (half == 0) A.rs[r] = rstd;
+    }
+    const float* mr = A.emod + (long)mol * 6 * X::De;
+    modulate<X::NE>(x, mr, mr + X::De, half);
+    if (keep) store_nat<X::NE>(A.et + r * X::De, half, x);
+    const int nb0 = (A.QK + 31) / 32;
+#pragma unroll 1
+    for (int b = 0; b < nb0; ++b) {                                   // tanh(lin_edge0 et): QK outputs in blocks of 32
+        const unsigned cur = A.c.oL0 + (unsigned)(b * X::KQE) * 1024;
+        f32x16 acc = mfma_block_p<X::KQE>(wp, ws, cur, b + 1 < nb0 ? cur + X::KQE * 1024 : A.c.oL1, x, zero16());
+        float T[16];
+        tanh16(acc, T);
+        if (valid) {
+            float* o = A.t0 + r * A.QK + b * 32 + half * 16;
+#pragma unroll
+            for (int s = 0; s < 16; ++s)
+                if (b * 32 + half * 16 + s < A.QK) o[s] = T[s];
+        }
+    }
+#pragma unroll 1
+    for (int b = 0; b < X::ND; ++b) {                                 // tanh(lin_edge1 et)
+        const unsigned cur = A.c.oL1 + (unsigned)(b * X::KQE) * 1024;
+        f32x16 acc = mfma_block_p<X::KQE>(wp, ws, cur, b + 1 < X::ND ? cur + X::KQE * 1024 : A.c.oL1, x, zero16());
+        float T[16];
+        tanh16(acc, T);
+        if (valid) store16(A.t1 + r * D + b * 32 + half * 16, T);
+    }
+}
+
+struct Args2BA {
+    Common c;
+    const float *dt1, *dt0, *xh, *rs, *emod;
+    float *det, *de_prev;
+    int QK;
+};
+
+template <int D>
+__global__ __launch_bounds__(64, 1) void k2d_bwd_a(Args2BA A) {
+    using X = FD<D>;
+    const int lane = threadIdx.x & 63, j = lane & 31, half = lane >> 5;
+    const long r = (long)blockIdx.x * 32 + j;
+    const bool valid = r < A.c.R;
+    const long rc = valid ? r : (long)A.c.R - 1;
+    const int mol = A.c.em[rc];
+    const float* mr = A.emod + (long)mol * 6 * X::De;
+    const WSrc ws = make_wsrc(A.c.packed, lane);
+    WPipe<X::PG> wp;
+    wpipe_prime(wp, ws, A.c.oL1T);
+    float x[X::HD];
+    load_nat<X::ND>(A.dt1 + rc * D, half, x);
+    f32x16 acc[X::NE];
+#pragma unroll
+    for (int b = 0; b < X::NE; ++b) {                                 // det = lin_edge1^T dt1 ...
+        const unsigned cur = A.c.oL1T + (unsigned)(b * X::KQD) * 1024;
+        acc[b] = mfma_block_p<X::KQD>(wp, ws, cur, b + 1 < X::NE ? cur + X::KQD * 1024 : A.c.oL0T, x, zero16());
+    }
+    {
+        const float* row = A.dt0 + rc * A.QK;                         // the columns past QK are zero (and so are their rows of the packed image)
+#pragma unroll
+        for (int b = 0; b < X::ND; ++b)
+#pragma unroll
+            for (int s = 0; s < 16; ++s) {
+                const int f = b * 32 + half * 16 + s;
+                x[b * 16 + s] = f < A.QK ? row[f] : 0.f;
+            }
+    }
+    float v[X::HE];
+#pragma unroll
+    for (int b = 0; b < X::NE; ++b) {                                 // ... + lin_edge0^T dt0
+        const unsigned cur = A.c.oL0T + (unsigned)(b * X::KQD) * 1024;
+        acc[b] = mfma_block_p<X::KQD>(wp, ws, cur, b + 1 < X::NE ? cur + X::KQD * 1024 : A.c.oL0T, x, acc[b]);
+        float o[16];
+#pragma unroll
+        for (int s = 0; s < 16; ++s) { o[s] = acc[b][s]; v[b * 16 + s] = acc[b][s]; }
+        if (valid) store16(A.det + r * X::De + b * 32 + half * 16, o);
+    }
+    ln_mod_bwd_regs<X::NE>(v, A.xh + rc * X::De, mr + X::De, A.rs[rc], half);
+    if (valid) {                                                      // accumulated into d e[l] (no edge_emb between e[l] and LayerNorm1 here)
+        float p[X::HE];
+        load_nat<X::NE>(A.de_prev + r * X::De, half, p);
+#pragma unroll
+        for (int i = 0; i < X::HE; ++i) p[i] += v[i];
+        store_nat<X::NE>(A.de_prev + r * X::De, half, p);
+    }
+}
+
 // ---- operand packing: PyTorch [out, in] (row stride ld, first column col0) -> [out block][quad][lane] float4 in the natural maps
 // of dgt_pack.cpp (register R of half h = feature (R / 16) 32 + 16 h + R % 16 on both sides); rows >= n_out are zero
 struct PackItem { const float* w; int ld, col0, n_out, nb, kq; unsigned dst; int trans, n_in; };   // dst in floats, nb output blocks, kq quads per block;
@@ -746,6 +858,72 @@ void fused_bwd_a(hipStream_t s, const FusedDims& d, const FusedTopo& t, const Fu
     if (d.D == 128) hipLaunchKernelGGL(k_bwd_a<128>, grid, dim3(64), 0, s, A);
     else if (d.D == 256) hipLaunchKernelGGL(k_bwd_a<256>, grid, dim3(64), 0, s, A);
     else hipLaunchKernelGGL(k_bwd_a<384>, grid, dim3(64), 0, s, A);
+}
+
+// ---- the 2-D model (dgt2d_train.hip): chain A / A' above, chain B / B' as they are.  The operand images live at the offsets of
+// fused_pack_layout (the slices of edge_emb, input_lin, coord_mlp.0 and the Gaussian table stay unused).
+bool fused_chain_b_available(const FusedDims& d) {         // chain B does not touch q / k: no condition on QK
+    return (d.D == 128 || d.D == 256 || d.D == 384) && (d.r == 2 || d.r == 4) && d.De == d.D / 4 && d.ce >= 1 && d.ce <= 32 && (d.r * d.De) % 64 == 0;
+}
+bool fused2d_available(const FusedDims& d) { return fused_chain_b_available(d) && d.QK >= 1 && d.QK <= d.D; }
+
+void fused2d_pack_block(hipStream_t s, const FusedDims& d, const FusedBlockParams& p, float* packed) {
+    const FusedPackLayout L = fused_pack_layout(d);
+    const int De = d.De, D = d.D;
+    PackArgs P;
+    auto item = [](const float* w, int ld, int n_out, int K, size_t dst) {
+        PackItem it; it.w = w; it.ld = ld; it.col0 = 0; it.n_out = n_out; it.nb = (n_out + 31) / 32; it.kq = K / 8; it.dst = (unsigned)dst; it.trans = 0; it.n_in = K; return it;
+    };
+    P.it[0] = item(p.le0, De, d.QK, De, L.l0);
+    P.it[1] = item(p.le1, De, D, De, L.l1);
+    P.it[2] = item(p.ff3_w, De, d.r * De, De, L.ff3);
+    P.it[3] = item(p.ff4_w, d.r * De, De, d.r * De, L.ff4);
+    P.it[4] = item(p.ero_w, De, d.ce, De, L.ero);
+    for (int i = 5; i < 8; ++i) { P.it[i] = P.it[4]; P.it[i].nb = 0; }
+    P.first[0] = 0;
+    for (int i = 0; i < 8; ++i) P.first[i + 1] = P.first[i] + P.it[i].nb * P.it[i].kq;
+    P.out = packed; P.means = nullptr; P.stds = nullptr; P.De = 0; P.tab = 0;
+    hipLaunchKernelGGL(k_pack, dim3(P.first[8]), dim3(64), 0, s, P);          // (no block past first[8]: no Gaussian table)
+}
+
+void fused2d_pack_block_bwd(hipStream_t s, const FusedDims& d, const FusedBlockParams& p, float* packed) {
+    const FusedPackLayout L = fused_pack_layout(d);
+    const int De = d.De, D = d.D;
+    PackArgs P;
+    auto item = [](const float* w, int ld, int n_out, int K, int n_in, size_t dst) {
+        PackItem it; it.w = w; it.ld = ld; it.col0 = 0; it.n_out = n_out; it.nb = (n_out + 31) / 32; it.kq = K / 8; it.dst = (unsigned)dst; it.trans = 1; it.n_in = n_in; return it;
+    };
+    P.it[0] = item(p.ff4_w, d.r * De, d.r * De, De, De, L.ff4t);
+    P.it[1] = item(p.ff3_w, De, De, d.r * De, d.r * De, L.ff3t);
+    P.it[2] = item(p.le1, De, De, D, D, L.l1t);
+    P.it[3] = item(p.le0, De, De, D, d.QK, L.l0t);
+    for (int i = 4; i < 8; ++i) { P.it[i] = P.it[3]; P.it[i].nb = 0; }
+    P.first[0] = 0;
+    for (int i = 0; i < 8; ++i) P.first[i + 1] = P.first[i] + P.it[i].nb * P.it[i].kq;
+    P.out = packed; P.means = nullptr; P.stds = nullptr; P.De = 0; P.tab = 0;
+    hipLaunchKernelGGL(k_pack, dim3(P.first[8]), dim3(64), 0, s, P);
+}
+
+void fused2d_chain_a(hipStream_t s, const FusedDims& d, const FusedTopo& t, const float* packed, const float* e_in, const float* emod, float* xh_e1,
+                     float* rs_e1, float* et, float* t0, float* t1) {
+    Args2A A;
+    A.c = common_of(d, t, packed);
+    A.e_in = e_in; A.emod = emod; A.xh = xh_e1; A.rs = rs_e1; A.et = et; A.t0 = t0; A.t1 = t1; A.QK = d.QK;
+    const dim3 grid((unsigned)((t.R + 31) / 32));
+    if (d.D == 128) hipLaunchKernelGGL(k2d_chain_a<128>, grid, dim3(64), 0, s, A);
+    else if (d.D == 256) hipLaunchKernelGGL(k2d_chain_a<256>, grid, dim3(64), 0, s, A);
+    else hipLaunchKernelGGL(k2d_chain_a<384>, grid, dim3(64), 0, s, A);
+}
+
+void fused2d_bwd_a(hipStream_t s, const FusedDims& d, const FusedTopo& t, const float* packed, const float* dt1, const float* dt0, const float* xh_e1,
+                   const float* rs_e1, const float* emod, float* det, float* de_prev) {
+    Args2BA A;
+    A.c = common_of(d, t, packed);
+    A.dt1 = dt1; A.dt0 = dt0; A.xh = xh_e1; A.rs = rs_e1; A.emod = emod; A.det = det; A.de_prev = de_prev; A.QK = d.QK;
+    const dim3 grid((unsigned)((t.R + 31) / 32));
+    if (d.D == 128) hipLaunchKernelGGL(k2d_bwd_a<128>, grid, dim3(64), 0, s, A);
+    else if (d.D == 256) hipLaunchKernelGGL(k2d_bwd_a<256>, grid, dim3(64), 0, s, A);
+    else hipLaunchKernelGGL(k2d_bwd_a<384>, grid, dim3(64), 0, s, A);
 }
 
 // ---- node rows: LayerNorm + modulate, one wave per row (round 5, second half) -------------------------------------------------------

@@ -19,7 +19,13 @@
 #include <stdint.h>
 #include "train_common.h"
 
-namespace jt {
+// The kernels below have external linkage, so a second translation unit that launches them (dgt2d_train.hip) compiles its own copy
+// under a namespace of its own: it defines JT_OPS_NS before including this header.  Default: jt, as dgt_train.hip always had them.
+#ifndef JT_OPS_NS
+#define JT_OPS_NS jt
+#endif
+namespace JT_OPS_NS {
+using namespace ::jt;         // (train_common.h: Drop, drop_mul)
 
 #define JT_IDX(n)                                                          \
     const long i_ = (long)blockIdx.x * (long)blockDim.x + (long)threadIdx.x; \
@@ -847,4 +853,4 @@ __global__ void k_node_out_bwd(Topo t, int nd, const float* __restrict__ dout, f
     if (j < 3) dposf[r * 3 + j] = v; else datom[r * nd + (j - 3)] = v;
 }
 
-}  // namespace jt
+}  // namespace JT_OPS_NS

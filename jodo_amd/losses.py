@@ -7,6 +7,7 @@
                                       50 % self-conditioning double forward, weighted data-prediction loss
   kabsch_batch, get_align_position / get_align_noise  :388-440
   process_edge_batch        :470-498
+  get_sde_2D_loss_fn        :210-283  the 2-D model's loss (node features and edges, no positions); process_batch_2D :454-468
 
 The arithmetic of the model call — forward with kept activations and loss.backward() — is jodo_train_forward / jodo_train_backward
 (csrc/dgt_train.hip) behind models/dgt.py; everything here is the thin tensor algebra the reference also keeps in Python.
@@ -17,7 +18,7 @@ import random
 import numpy as np
 import torch
 
-from .models.utils import (remove_mean_with_mask, sample_combined_position_feature_noise,
+from .models.utils import (remove_mean_with_mask, sample_combined_position_feature_noise, sample_gaussian_with_mask,
                            sample_symmetric_edge_feature_noise)
 from .utils import expand_dims, get_self_cond_fn
 
@@ -131,9 +132,12 @@ def optimization_manager(config):
 
 
 def get_step_fn(noise_scheduler, train, optimize_fn, scaler, config, prop_dist=None):
-    if not config.pred_edge or config.only_2D:
-        raise NotImplementedError("the HIP path implements the 3D graph model (pred_edge, not only_2D)")
-    loss_fn = get_sde_graph_loss_fn(noise_scheduler, train, scaler, config, prop_dist)
+    if not config.pred_edge:
+        raise NotImplementedError("the HIP path implements the graph models that predict edges (pred_edge)")
+    if config.only_2D:
+        loss_fn = get_sde_2D_loss_fn(noise_scheduler, train, scaler, config)
+    else:
+        loss_fn = get_sde_graph_loss_fn(noise_scheduler, train, scaler, config, prop_dist)
     # A step on the HIP module has no host synchronisation of its own (tests/test_train_gpu.py), so the host could queue arbitrarily far
     # ahead of the card (its side of a QM9 step is ~9 ms, the card's ~18).  The step therefore waits for the step BEFORE the one it has
     # just queued: the card always has a whole step of work left, the queue — and the batches, staging buffers and activations it pins —
@@ -147,6 +151,11 @@ def get_step_fn(noise_scheduler, train, optimize_fn, scaler, config, prop_dist=N
     def step_fn(state, batch):
         model = state['model']
         if train:
+            if config.only_2D:
+                # asking for a training step is the opt-in to the 2-D model's HIP training path (models/dgt2d.py hip_training)
+                inner = getattr(model, 'module', model)
+                if hasattr(inner, 'hip_training'):
+                    inner.hip_training = True
             optimizer = state['optimizer']
             optimizer.zero_grad()
             loss = loss_fn(model, batch)
@@ -311,6 +320,70 @@ def process_edge_batch(batch, device, include_charges, scaler, prop_norm):
     if stage is not None:
         stage.end()
     return torch.cat([pos, atoms, charges], dim=2), edges, node_mask, edge_mask, context
+
+
+@torch.no_grad()
+def process_batch_2D(batch, device, include_charges, scaler):
+    """Batch dict of the data loader -> (xh [B,N,nd], edge_x [B,N,N,ch], node_mask [B,N,1], edge_mask): no positions, everything
+    through the training scaler (losses.py:454-468 of the reference)."""
+    dev = torch.device(device)
+    node_mask, edge_mask = batch['atom_mask'].to(dev).unsqueeze(2), batch['edge_mask'].to(dev)
+    counts = _host_counts(batch['atom_mask'], batch['edge_mask'])
+    if counts is not None:
+        node_mask._jodo_counts = counts                      # read by the HIP module's training path (models/dgt2d.py _train_engine)
+    atom_type, edge_type = batch['atom_one_hot'].to(dev), batch['edge_one_hot'].to(dev)
+    fc_charge = (batch['formal_charges'] if include_charges else torch.zeros(0)).to(dev)
+    _, atom_type, fc_charge, edge_type = scaler(None, atom_type, fc_charge, node_mask, edge_type, edge_mask)
+    return torch.cat([atom_type, fc_charge], dim=2), edge_type, node_mask, edge_mask
+
+
+def get_sde_2D_loss_fn(noise_scheduler, train, scaler, config):
+    """loss_fn(model, batch) -> scalar: node-feature and edge loss of one batch of 2-D graphs at per-molecule random times, with the
+    reference's use of the random generators in its order: torch.rand (t), node noise, edge noise, then python's random() for the
+    50 % self-conditioning double forward."""
+    m = config.model
+    device, include_charges, reduce_mean = config.device, m.include_fc_charge, config.training.reduce_mean
+    pred_data, self_cond = m.pred_data, m.self_cond
+    _, w_atom, w_edge = (float(w) for w in m.loss_weights.split(','))
+
+    def loss_fn(model, batch):
+        model.train() if train else model.eval()
+        xh, edge_x, node_mask, edge_mask = process_batch_2D(batch, device, include_charges, scaler)
+        B = xh.shape[0]
+        n_nodes = node_mask.squeeze(-1).sum(-1)
+        t = torch.rand(B, device=xh.device) * (1. - 1e-5) + 1e-5
+        alpha_t, sigma_t = noise_scheduler.marginal_prob(t)
+        noise = sample_gaussian_with_mask(xh.size(), xh.device, node_mask)
+        edge_noise = sample_symmetric_edge_feature_noise(B, edge_x.shape[1], edge_x.shape[-1], edge_mask)
+        z_t = expand_dims(alpha_t, xh.dim()) * xh + expand_dims(sigma_t, noise.dim()) * noise
+        edge_z_t = expand_dims(alpha_t, edge_x.dim()) * edge_x + expand_dims(sigma_t, edge_noise.dim()) * edge_noise
+        noise_level = torch.log(alpha_t ** 2 / sigma_t ** 2)
+        kw = dict(edge_x=edge_z_t, noise_level=noise_level)
+        if self_cond:
+            assert pred_data
+            cond_x = cond_edge_x = None
+            if random.random() < 0.5:
+                with torch.no_grad():
+                    cond_x, cond_edge_x = model(t, z_t, node_mask, edge_mask, cond_x=None, cond_edge_x=None, **kw)
+                    cond_x, cond_edge_x = cond_x.detach(), cond_edge_x.detach()
+            pred, edge_pred = model(t, z_t, node_mask, edge_mask, cond_x=cond_x, cond_edge_x=cond_edge_x, **kw)
+        else:
+            pred, edge_pred = model(t, z_t, node_mask, edge_mask, **kw)
+        if pred_data:
+            l_atom = torch.square(pred - xh).mean(-1).sum(-1)
+            l_edge = torch.square(edge_x - edge_pred).mean(-1).reshape(B, -1).sum(-1)
+        else:
+            l_atom = torch.square(noise - pred).mean(-1).sum(-1)
+            l_edge = torch.square(edge_noise - edge_pred).mean(-1).reshape(B, -1).sum(-1)
+        if reduce_mean:
+            l_atom = l_atom / n_nodes
+            l_edge = l_edge / (edge_mask.reshape(B, -1).sum(-1) + 1e-8)
+        losses = w_atom * l_atom + w_edge * l_edge
+        if pred_data:
+            losses = torch.sqrt(alpha_t / sigma_t) * losses
+        return losses.mean()
+
+    return loss_fn
 
 
 def get_sde_graph_loss_fn(noise_scheduler, train, scaler, config, prop_norm=None):

@@ -6,8 +6,12 @@ the same call as the reference class:
     model(t, xh, node_mask, edge_mask, context=None, edge_x=..., cond_x=..., cond_edge_x=..., noise_level=...)
         -> (atom_pred [B,N,nd], edge_pred [B,N,N,ch])
 The arithmetic runs in libjodo_hip.so (csrc/dgt2d_forward.hip, `jodo_dgt2d_forward`) on the current HIP stream: the weights are
-packed once (csrc/dgt2d_pack.cpp), a descriptor and a workspace are built per batch of atom counts.  Inference only: there is no
-CPU or eager fallback, no training path and no split-bf16 form for this model — those raise.
+packed once (csrc/dgt2d_pack.cpp), a descriptor and a workspace are built per batch of atom counts.  There is no CPU or eager
+fallback and no split-bf16 form for this model — those raise.
+
+Training is opt-in: with `model.hip_training = True` (jodo_amd.losses.get_step_fn sets it when asked for a training step) a
+grad-enabled call runs csrc/dgt2d_train.hip through jodo_amd.train.TrainEngine2D and `loss.backward()` fills every parameter's
+gradient; a default module keeps refusing grad-enabled calls ("inference only").
 """
 import ctypes
 
@@ -93,6 +97,7 @@ class DGT_concat_2D(nn.Module):
         self.force_directed = False   # tests: always the directed fallback
         self.max_blocks = -1          # tests: stop after this many blocks (the workspace then holds h and e of that block)
         self.last_flags = None
+        self.hip_training = False     # opt-in: grad-enabled calls go through the HIP training path (csrc/dgt2d_train.hip)
         self.register_load_state_dict_post_hook(_drop_packed_after_load)
 
     # -- weights (same invalidation rules as _DGTBase._weights) ------------------------------------
@@ -170,15 +175,23 @@ class DGT_concat_2D(nn.Module):
                                "use tests/oracle2d.py for CPU checks" % xh.device)
         if self.split_bf16:
             raise NotImplementedError("split_bf16 is not implemented for DGT_concat_2D (exact fp32 only)")
-        if torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters()) or
-                                        any(t_ is not None and t_.requires_grad for t_ in (xh, edge_x, cond_x, cond_edge_x, noise_level))):
+        inputs_want_grad = any(t_ is not None and t_.requires_grad for t_ in (xh, edge_x, cond_x, cond_edge_x, noise_level))
+        wants_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        if not self.hip_training and torch.is_grad_enabled() and (wants_grad or inputs_want_grad):
             raise NotImplementedError("DGT_concat_2D is inference only: call it under torch.no_grad() (training / backward for the 2-D "
                                       "model is not implemented)")
+        if self.hip_training and torch.is_grad_enabled() and inputs_want_grad:
+            raise RuntimeError("the HIP DGT returns parameter gradients only: detach the inputs (the reference's loss detaches the "
+                               "self-conditioning inputs, losses.py:250, and needs no input gradient)")
         if (cond_x is None) != (cond_edge_x is None):
             raise ValueError("cond_x and cond_edge_x must both be given or both be None")
         B, N, dims = xh.shape
         if dims != self.in_node_dim or edge_x.shape != (B, N, N, self.edge_ch):
             raise ValueError("shape mismatch: xh %s edge_x %s" % (tuple(xh.shape), tuple(edge_x.shape)))
+        if self.hip_training and (wants_grad or (self.training and self.dropout_p > 0)):
+            # training path (csrc/dgt2d_train.hip): activations kept for loss.backward(); under model.train() dropout is active in the
+            # no-grad self-conditioning forward too (losses.py:246-250 of the reference), which is why that call comes here as well
+            return self._forward_train(xh, edge_x, cond_x, cond_edge_x, noise_level, node_mask, edge_mask, wants_grad)
         dev = xh.device
         f32 = lambda x: None if x is None else x.detach().to(torch.float32).contiguous()
         xh_, ex_, cx_, cex_, nl_ = f32(xh), f32(edge_x), f32(cond_x), f32(cond_edge_x), f32(noise_level)
@@ -193,6 +206,64 @@ class DGT_concat_2D(nn.Module):
             capi.current_stream_ptr()), 'jodo_dgt2d_forward')
         self.last_flags = plan['flags']
         self._last_plan = plan
+        return out_x, out_e
+
+    # -- training path (opt-in: hip_training) ------------------------------------------------------------
+    def _train_engine(self, node_mask, edge_mask, device):
+        """One TrainEngine2D (jodo_train2d handle + device tables) per batch of atom counts, keyed by the counts themselves like
+        DGT_concat._train_engine; all engines of the module share its two activation workspaces."""
+        from ..train import TrainEngine2D
+        B, N = node_mask.shape[0], node_mask.shape[1]
+        opts = tuple(sorted((getattr(self, 'train_options', None) or {}).items()))
+        last = self.__dict__.get('_train_last')
+        if (last is not None and last[0] is node_mask and last[1] == node_mask._version and last[2] is edge_mask
+                and last[3] == edge_mask._version and last[4] == opts):
+            return last[5]                                       # the two forwards of a self-conditioned step: no host work
+        hint = getattr(node_mask, '_jodo_counts', None)          # counts the loss already has on the host (losses.process_batch_2D)
+        if hint is not None and len(hint) == B:
+            n_host = np.ascontiguousarray(hint, dtype=np.int32)
+        else:
+            nm = node_mask.reshape(B, N)
+            n_nodes = nm.sum(1).round().to(torch.int32)
+            prefix = (torch.arange(N, device=nm.device).unsqueeze(0) < n_nodes.unsqueeze(1))
+            em = edge_mask.reshape(B, N, N)
+            want = prefix.unsqueeze(1) & prefix.unsqueeze(2) & (~torch.eye(N, dtype=torch.bool, device=nm.device))
+            ok = torch.stack([(prefix.to(nm.dtype) == nm).all(), (want.to(em.dtype) == em).all()]).to(torch.int32)
+            host = torch.cat([n_nodes, ok]).cpu().numpy()        # counts and both mask checks in one transfer
+            if not host[B]:
+                raise ValueError("node_mask must be a prefix mask (real atoms first), as the samplers build it")
+            if not host[B + 1]:
+                raise ValueError("edge_mask must be node_mask x node_mask with the diagonal removed")
+            n_host = np.ascontiguousarray(host[:B])
+        key = (str(device), N, opts) + tuple(int(v) for v in n_host)
+        cache = self.__dict__.setdefault('_train_engines', {})
+        eng = cache.pop(key, None)
+        if eng is None:
+            named = self.__dict__.get('_train_named')
+            if named is None:
+                named = self.__dict__['_train_named'] = TrainEngine2D.named_table([(k, tuple(v.shape)) for k, v in self.state_dict().items()])
+            pool = self.__dict__.setdefault('_train_pool', TrainEngine2D.new_pool())
+            eng = TrainEngine2D(self._cfg_struct, n_host, N, named, device, pool=pool, options=dict(opts))
+            while len(cache) >= 16:
+                cache.pop(next(iter(cache)))
+        cache[key] = eng                                         # most recently used last
+        self.__dict__['_train_last'] = (node_mask, node_mask._version, edge_mask, edge_mask._version, opts, eng)
+        return eng
+
+    def _forward_train(self, xh, edge_x, cond_x, cond_edge_x, noise_level, node_mask, edge_mask, wants_grad):
+        from ..train import dgt2d_autograd
+        f32 = lambda x: None if x is None else x.detach().to(torch.float32).contiguous()
+        eng = self._train_engine(node_mask, edge_mask, xh.device)
+        p = float(self.dropout_p) if self.training else 0.0
+        # dropout masks: counter-based, keyed by a seed drawn from torch's generator (so torch.manual_seed reproduces a step)
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if p > 0 else 0
+        params = list(self.parameters())                         # state_dict order: this tree has no buffers
+        args = (eng, p, seed, f32(xh), f32(edge_x), f32(cond_x), f32(cond_edge_x), f32(noise_level))
+        if wants_grad:
+            out_x, out_e = dgt2d_autograd(*args, params)
+        else:                                                    # the no-grad self-conditioning forward of a training step
+            out_x, out_e = eng.forward([q.detach().contiguous() for q in params], *args[3:], None, p, seed, save_activations=False)
+        self.last_flags = eng.flags
         return out_x, out_e
 
     # -- tests: the state inside the workspace after the last call ------------------------------------

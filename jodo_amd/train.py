@@ -1,6 +1,7 @@
 """Python plumbing of the training side behind the C ABI; device tensors in, device tensors out, no CPU
 fallback.
 
+  TrainEngine2D / dgt2d_autograd   the same for DGT_concat_2D (csrc/dgt2d_train.hip), behind models/dgt2d.py when `hip_training` is set
   TrainEngine / dgt_autograd   the whole score network under autograd: jodo_train_forward keeps the activations,
                                jodo_train_backward returns the gradient of every parameter (csrc/dgt_train.hip, train_ops.h,
                                train_gemm.hip) — what loss.backward() does in /root/reference/losses.py:286-385.  models/dgt.py
@@ -20,7 +21,15 @@ class TrainEngine:
     """One batch shape (atom counts) of the training path: owns the jodo_train handle, its device tables and the workspace that
     carries the activations from forward to backward.  `lib` / `stream_ptr` exist for the build container's CPU suite, which
     drives the host-emulation build of the same sources (tests/emul/) with host tensors; the product path (models/dgt.py) never
-    passes them and always runs libjodo_hip.so on the current HIP stream."""
+    passes them and always runs libjodo_hip.so on the current HIP stream.
+
+    The pool / slot / pinned-ring code is shared by every engine class: a subclass names its family of C entry points in `_abi`
+    (TrainEngine2D below: jodo_train2d_*, which mirror jodo_train_* one for one)."""
+
+    _abi = 'jodo_train'
+
+    def _fn(self, name):
+        return getattr(self.L, '%s_%s' % (self._abi, name))
 
     @staticmethod
     def named_table(named_shapes):
@@ -54,19 +63,19 @@ class TrainEngine:
         n_host = np.ascontiguousarray(np.asarray(n_nodes, dtype=np.int32))
         self.B, self.N = int(n_host.shape[0]), int(N)
         self.handle = ctypes.c_void_p()
-        self._check(self.L.jodo_train_create(ctypes.byref(cfg_struct), self.B, self.N, n_host.ctypes.data_as(ctypes.c_void_p), named['arr'],
-                                             self.n_params, ctypes.byref(self.handle)), 'jodo_train_create')
-        self.L.jodo_train_desc_bytes.restype = ctypes.c_size_t
-        self.L.jodo_train_workspace_bytes.restype = ctypes.c_size_t
-        self.L.jodo_train_desc_bytes.argtypes = [ctypes.c_void_p]
-        self.L.jodo_train_workspace_bytes.argtypes = [ctypes.c_void_p]
+        self._check(self._fn('create')(ctypes.byref(cfg_struct), self.B, self.N, n_host.ctypes.data_as(ctypes.c_void_p), named['arr'],
+                                             self.n_params, ctypes.byref(self.handle)), self._abi + '_create')
+        self._fn('desc_bytes').restype = ctypes.c_size_t
+        self._fn('workspace_bytes').restype = ctypes.c_size_t
+        self._fn('desc_bytes').argtypes = [ctypes.c_void_p]
+        self._fn('workspace_bytes').argtypes = [ctypes.c_void_p]
         for opt, val in (options or {}).items():                 # jodo_train_set_option, e.g. {0: 0} = op-by-op forward (tests)
-            self._check(self.L.jodo_train_set_option(self.handle, int(opt), int(val)), 'jodo_train_set_option')
-        self.desc = torch.empty(self.L.jodo_train_desc_bytes(self.handle), dtype=torch.uint8, device=device)
+            self._check(self._fn('set_option')(self.handle, int(opt), int(val)), self._abi + '_set_option')
+        self.desc = torch.empty(self._fn('desc_bytes')(self.handle), dtype=torch.uint8, device=device)
         # The activation workspace (2.6 GB at QM9 batch 128) is shared by every engine of a module through `pool`: data loaders
         # produce a new set of atom counts every step, so handles come and go while the pool's buffers, grown to the largest request,
         # serve them all.  A slot's stamp names the forward whose activations it holds.
-        self.ws_bytes = int(self.L.jodo_train_workspace_bytes(self.handle))
+        self.ws_bytes = int(self._fn('workspace_bytes')(self.handle))
         self.pool = pool if pool is not None else self.new_pool()
         self._upload_tables()
         self.flags = torch.zeros(8, dtype=torch.int32, device=device)
@@ -79,8 +88,8 @@ class TrainEngine:
 
     def __del__(self):
         try:
-            self.L.jodo_train_destroy.argtypes = [ctypes.c_void_p]
-            self.L.jodo_train_destroy(self.handle)
+            self._fn('destroy').argtypes = [ctypes.c_void_p]
+            self._fn('destroy')(self.handle)
         except Exception:
             pass
 
@@ -91,7 +100,7 @@ class TrainEngine:
         step, and that synchronisation was the last one left in a training step.)"""
         n = int(self.desc.numel())
         if self._stream is not capi.current_stream_ptr:          # a caller-chosen stream: the plain (synchronising) upload on that stream
-            self._check(self.L.jodo_train_upload(self.handle, capi.ptr(self.desc), self._stream()), 'jodo_train_upload')
+            self._check(self._fn('upload')(self.handle, capi.ptr(self.desc), self._stream()), self._abi + '_upload')
             return
         ring = self.pool.setdefault('pin', {'bufs': [None] * 4, 'events': [None] * 4, 'next': 0})
         i = ring['next']
@@ -100,11 +109,11 @@ class TrainEngine:
             ring['events'][i].synchronize()
         if ring['bufs'][i] is None or ring['bufs'][i].numel() < n:
             ring['bufs'][i] = torch.empty(int(n * 1.25) + 4096, dtype=torch.uint8, pin_memory=True)
-        self.L.jodo_train_desc_host.restype = ctypes.c_void_p
-        self.L.jodo_train_desc_host.argtypes = [ctypes.c_void_p]
-        src = self.L.jodo_train_desc_host(self.handle)
+        self._fn('desc_host').restype = ctypes.c_void_p
+        self._fn('desc_host').argtypes = [ctypes.c_void_p]
+        src = self._fn('desc_host')(self.handle)
         if not src:
-            raise capi.JodoHipError("jodo_train_desc_host returned NULL")
+            raise capi.JodoHipError(self._abi + "_desc_host returned NULL")
         ctypes.memmove(ring['bufs'][i].data_ptr(), src, n)
         self.desc.copy_(ring['bufs'][i][:n], non_blocking=True)
         ev = torch.cuda.Event()
@@ -141,12 +150,12 @@ class TrainEngine:
         self._slot, self.stamp = slot, slot['stamp']
         out_x, out_e = torch.empty_like(xh), torch.empty_like(edge_x)
         if bool(save_activations) != getattr(self, '_saving', True):    # option 2: a forward nobody differentiates skips backward-only stores
-            self._check(self.L.jodo_train_set_option(self.handle, 2, 1 if save_activations else 0), 'jodo_train_set_option')
+            self._check(self._fn('set_option')(self.handle, 2, 1 if save_activations else 0), self._abi + '_set_option')
             self._saving = bool(save_activations)
-        self._check(self.L.jodo_train_forward(
+        self._check(self._fn('forward')(
             self.handle, capi.ptr(self.desc), self._ptrs(params), self.n_params, capi.ptr(xh), capi.ptr(edge_x), capi.ptr(cond_x),
             capi.ptr(cond_edge_x), capi.ptr(noise_level), capi.ptr(context), ctypes.c_float(dropout_p), ctypes.c_uint64(seed),
-            capi.ptr(out_x), capi.ptr(out_e), capi.ptr(self.flags), capi.ptr(slot['buf']), self._stream()), 'jodo_train_forward')
+            capi.ptr(out_x), capi.ptr(out_e), capi.ptr(self.flags), capi.ptr(slot['buf']), self._stream()), self._abi + '_forward')
         return out_x, out_e
 
     def release(self, stamp):
@@ -167,8 +176,8 @@ class TrainEngine:
         2 = f1 [Nn, r D], 3 = a1 = SiLU(f1) x dropout, 4 = f2 [Nn, D], 5 = f3 [R, r De], 6 = a3 = SiLU(f3) x dropout, 7 = f4 [R, De]
         (f2, f4 before their dropout); flat float32."""
         off, cnt = ctypes.c_size_t(), ctypes.c_size_t()
-        self.L.jodo_train_debug_locate.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
-        self._check(self.L.jodo_train_debug_locate(self.handle, int(what), int(layer), ctypes.byref(off), ctypes.byref(cnt)), 'jodo_train_debug_locate')
+        self._fn('debug_locate').argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+        self._check(self._fn('debug_locate')(self.handle, int(what), int(layer), ctypes.byref(off), ctypes.byref(cnt)), self._abi + '_debug_locate')
         buf = self._slot['buf']
         return buf[off.value:off.value + 4 * cnt.value].view(torch.float32).clone()
 
@@ -191,12 +200,20 @@ class TrainEngine:
         if tail != lay[2]:                                       # padding behind the LAST slice: no gradient buffer follows it, so the
             flat[tail:].zero_()                                  # library's fill does not reach it, and the norm of `flat` reads it
         grads = carve(flat, lay[0], lay[1])
-        self._check(self.L.jodo_train_backward(
+        self._check(self._fn('backward')(
             self.handle, capi.ptr(self.desc), self._ptrs(params), self._ptrs(grads), self.n_params, capi.ptr(noise_level),
             capi.ptr(d_out_x), capi.ptr(d_out_e), ctypes.c_float(dropout_p), ctypes.c_uint64(seed), capi.ptr(slot['buf']),
-            self._stream()), 'jodo_train_backward')
+            self._stream()), self._abi + '_backward')
         slot['live'] = False                                     # = release(stamp); a second backward over the same activations still works until a forward takes the slot
         return grads
+
+
+class TrainEngine2D(TrainEngine):
+    """The same for DGT_concat_2D (csrc/dgt2d_train.hip): `cfg_struct` is a jodo_cfg2d, xh has no position channels, and there is no
+    context.  Pool, slots and the pinned staging ring are TrainEngine's.  debug_fetch knows five more selectors: 8 = xhat of the
+    edges' LayerNorm1 [R, De], 9 = its rstd [R], 10 = et [R, De], 11 = t0 [R, QK], 12 = t1 [R, D]."""
+
+    _abi = 'jodo_train2d'
 
 
 def release_slot(pool, stamp):
@@ -240,3 +257,8 @@ class _DGTTrainFn(torch.autograd.Function):
 
 def dgt_autograd(engine, dropout_p, seed, xh, edge_x, cond_x, cond_edge_x, noise_level, context, params):
     return _DGTTrainFn.apply(engine, dropout_p, seed, xh, edge_x, cond_x, cond_edge_x, noise_level, context, *params)
+
+
+def dgt2d_autograd(engine, dropout_p, seed, xh, edge_x, cond_x, cond_edge_x, noise_level, params):
+    """The 2-D score network (a TrainEngine2D) as the same autograd node: no context."""
+    return _DGTTrainFn.apply(engine, dropout_p, seed, xh, edge_x, cond_x, cond_edge_x, noise_level, None, *params)

@@ -8,10 +8,17 @@ oracle/ref_import.py with 8 torch threads.  Weights are deterministic_init_ (see
                                                  state, decodes, per-entry decision margins and the share below 1e-3 per kind
   tests/golden/samplefn2d_zinc.npz               the reference's own get_sampling_fn (2-D), batch 16, 10 steps, seeded; the draws
                                                  are a function of the seed (checksums stored), results before the final shuffle
+  tests/golden/grad2d_zinc.npz, grad2d_moses.npz the reference's own get_sde_2D_loss_fn + loss.backward() (eval-mode dropout, self-conditioned
+                                                 branch) on a small synthetic batch: inputs, draws, predictions, loss, ~20 parameter gradients
+  tests/golden/loss2d_zinc.npz                   the same loss_fn call as data of the loss alone: batch, seeds, t, both noises, the coin, loss
+  tests/golden/train_drop2d_zinc.npz             the reference under model.train() with the training path's dropout masks injected
+                                                 (oracle/make_golden.py DropInjector, oracle/philox_ref.dropout_masks): no-grad call with
+                                                 seed 1, grad-enabled call on its outputs with seed 2, output and parameter gradients
   tests/golden/sd2d_manifest.json                state_dict keys, shapes and order for both configs
   tests/golden/n_nodes_2d.json                   the two train_n_nodes tables
 
-While doing so it asserts tests/oracle2d.py against the reference within 1e-5 (float32).
+While doing so it asserts tests/oracle2d.py (and tests/oracle2d_train.py, the masked form) against the reference within 1e-5
+(float32) on outputs and 2e-4 relative on the recorded gradients.
 Run:  python tools/make_golden_2d.py [name-prefix ...]
 """
 import importlib.util
@@ -39,11 +46,11 @@ MARGIN_CAP = 0.05           # at most 5 % of the real entries of a decision kind
 CFG = {'zinc': 'vpsde_zinc_2d_jodo', 'moses': 'vpsde_moses_2d_jodo'}
 
 
-def build_reference_model(ref, cfg_name, seed, head_gain=1.0):
+def build_reference_model(ref, cfg_name, seed, head_gain=1.0, gain=1.0):
     cfg = reference_config(cfg_name)
     cfg.device = torch.device('cpu')
     model = ref.models.utils._MODELS[cfg.model.name](cfg).eval()
-    deterministic_init_(model, seed=seed)
+    deterministic_init_(model, seed=seed, gain=gain)
     if head_gain != 1.0:
         with torch.no_grad():
             for k in ('node_pred_mlp.4.weight', 'edge_type_mlp.4.weight', 'edge_exist_mlp.4.weight'):
@@ -274,6 +281,234 @@ def samplefn_fixture(ref, batch=16, steps=10, seed=42, model_seed=42):
     print('samplefn2d_zinc.npz ok; n_nodes', rec['n_nodes'].tolist(), 'shares', shares)
 
 
+TRAIN_NODES = {'zinc': [1, 2, 3, 9, 33, 38], 'moses': [2, 5, 27]}     # tests/test_train2d_*.py: the smallest shapes that reach every path
+TRAIN_GAIN = 1.5
+
+
+def synthetic_batch_2d(cfg, n_nodes, seed):
+    """A loader-shaped batch of 2-D graphs (tests/test_losses2d_host.py rebuilds nothing: the batch is stored)."""
+    B, N = len(n_nodes), max(n_nodes)
+    nm, em = masks(n_nodes)
+    ch = cfg.model.edge_ch
+    g = torch.Generator().manual_seed(seed)
+    at = torch.randint(0, cfg.data.atom_types, (B, N), generator=g)
+    bond = torch.randint(0, 4, (B, N, N), generator=g)
+    bond = torch.triu(bond, 1)
+    bond = bond + bond.transpose(1, 2)
+    chans = [(bond > 0).float(), bond.float() / 3.]
+    if ch == 3:
+        chans.append((bond == 3).float())
+    return dict(atom_mask=nm[..., 0], edge_mask=em, atom_one_hot=torch.nn.functional.one_hot(at, cfg.data.atom_types).float() * nm,
+                edge_one_hot=torch.stack(chans, -1) * em.reshape(B, N, N, 1),
+                formal_charges=torch.randint(-1, 2, (B, N, 1), generator=g).float() * nm)
+
+
+def grad_names_2d(L):
+    mid, last = L // 2, L - 1
+    return ['e_block_0.ff_linear3.weight', 'e_block_0.ff_linear3.bias', 'e_block_0.ff_linear4.bias', 'e_block_0.ff_linear1.bias',
+            'e_block_0.attn_mpnn.lin_edge0.weight', 'e_block_%d.attn_mpnn.lin_query.weight' % mid, 'e_block_%d.attn_mpnn.lin_edge1.weight' % mid,
+            'e_block_%d.node2edge_lin.weight' % mid, 'e_block_%d.node2edge_lin.bias' % mid,
+            'e_block_%d.node_time_mlp.1.bias' % mid, 'e_block_%d.edge_time_mlp.1.bias' % mid,
+            'e_block_%d.ff_linear2.bias' % last, 'e_block_%d.ff_linear4.weight' % last, 'e_block_%d.attn_mpnn.lin_key.bias' % last,
+            'node_%d.weight' % last, 'edge_0.weight', 'time_mlp.0.weights', 'time_mlp.3.bias',
+            'node_pred_mlp.4.weight', 'edge_type_mlp.4.weight', 'edge_exist_mlp.4.weight', 'node_emb.weight', 'edge_emb.weight']
+
+
+def grad2d_fixture(ref, which, seed=41):
+    """The reference's OWN 2-D training loss and loss.backward() (losses.py:210-283, self-conditioned branch taken, eval mode so that
+    dropout is the identity) on a small synthetic batch; layout of grad_qm9.npz.  For zinc the same call is stored once more as
+    loss2d_zinc.npz: the data of the loss function alone (batch, seeds, draws, coin, loss)."""
+    import random as pyrandom
+    cfg, model = build_reference_model(ref, CFG[which], seed, head_gain=HEAD_GAIN_2D, gain=TRAIN_GAIN)
+    hp = O2.Hyper2D.from_config(cfg)
+    L = ref.losses
+    ns = ref.diffusion.noise_schedule.NoiseScheduleVP(cfg.sde.schedule, continuous_beta_0=cfg.sde.continuous_beta_0,
+                                                      continuous_beta_1=cfg.sde.continuous_beta_1)
+    scaler = ref.utils.get_data_scaler(cfg)
+    n_nodes = TRAIN_NODES[which]
+    nm, em = masks(n_nodes)
+    batch = synthetic_batch_2d(cfg, n_nodes, seed)
+    loss_fn = L.get_sde_2D_loss_fn(ns, False, scaler, cfg)
+    rec = {}
+    inner = model.forward
+
+    def recording_forward(t, xh, node_mask, edge_mask, context=None, **kw):
+        if torch.is_grad_enabled():
+            rec.update(t=t.clone(), z_t=xh.clone(), edge_z_t=kw['edge_x'].clone(), noise_level=kw['noise_level'].clone(),
+                       cond_x=None if kw.get('cond_x') is None else kw['cond_x'].clone(),
+                       cond_edge_x=None if kw.get('cond_edge_x') is None else kw['cond_edge_x'].clone())
+        out = inner(t, xh, node_mask, edge_mask, context, **kw)
+        if torch.is_grad_enabled():
+            rec.update(pred=out[0].detach().clone(), edge_pred=out[1].detach().clone())
+        return out
+
+    orig_n, orig_e = L.sample_gaussian_with_mask, L.sample_symmetric_edge_feature_noise
+
+    def rn(*a, **k):
+        v = orig_n(*a, **k)
+        rec['noise'] = v.clone()
+        return v
+
+    def re_(*a, **k):
+        v = orig_e(*a, **k)
+        rec['edge_noise'] = v.clone()
+        return v
+
+    model.forward = recording_forward
+    L.sample_gaussian_with_mask, L.sample_symmetric_edge_feature_noise = rn, re_
+    for tries in range(64):                                    # a python-random seed whose first draw takes the self-cond branch
+        pyrandom.seed(seed + tries)
+        coin = pyrandom.random()
+        if coin < 0.5:
+            py_seed = seed + tries
+            pyrandom.seed(py_seed)
+            break
+    torch.manual_seed(seed)
+    model.zero_grad()
+    try:
+        loss = loss_fn(model, batch)
+        threads = torch.get_num_threads()
+        torch.set_num_threads(1)                               # the CPU backward's scatter sums are reordered by threads: keep the file reproducible
+        loss.backward()
+        torch.set_num_threads(threads)
+    finally:
+        L.sample_gaussian_with_mask, L.sample_symmetric_edge_feature_noise = orig_n, orig_e
+        del model.forward
+    assert rec['cond_x'] is not None
+    xh, edge_x, _, _ = L.process_batch_2D(batch, cfg.device, cfg.model.include_fc_charge, scaler)
+    alpha_t, sigma_t = ns.marginal_prob(rec['t'])
+    names = grad_names_2d(hp.L)
+    params = dict(model.named_parameters())
+    assert len(set(names)) == len(names) and all(params[k].grad is not None and float(params[k].grad.abs().max()) > 0 for k in names)
+    # the oracle's autograd against the reference's, here and now
+    sd = {k: v.detach().clone().requires_grad_(True) for k, v in model.state_dict().items()}
+    px, pe = O2.forward_dense(sd, hp, rec['z_t'], nm, em, rec['edge_z_t'], rec['cond_x'], rec['cond_edge_x'], rec['noise_level'])
+    err = max((px - rec['pred']).abs().max().item(), (pe - rec['edge_pred']).abs().max().item())
+    assert err < 1e-5, "dense 2-D oracle vs reference (training step): %g" % err
+    ol = loss2d_from_outputs(cfg, px, pe, xh, edge_x, nm, em, alpha_t, sigma_t)
+    assert abs(ol.item() - loss.item()) < 1e-5 * abs(loss.item()), (ol.item(), loss.item())
+    ol.backward()
+    for k in names:
+        a, b = sd[k].grad, params[k].grad
+        rel = (a - b).abs().max().item() / (b.abs().max().item() + 1e-12)
+        assert rel < 2e-4, "oracle gradient of %s: rel err %g" % (k, rel)
+    from oracle.make_golden import savez_stable
+    fname = 'grad2d_%s.npz' % which
+    savez_stable(os.path.join(OUT, fname), torch_num_threads=np.int64(torch.get_num_threads()), cfg_name=np.array(CFG[which]), seed=np.int64(seed),
+                 gain=np.float32(TRAIN_GAIN), head_gain=np.float32(HEAD_GAIN_2D), n_nodes=np.array(n_nodes),
+                 t=rec['t'].numpy(), z_t=rec['z_t'].numpy(), edge_z_t=rec['edge_z_t'].numpy(), noise_level=rec['noise_level'].numpy(),
+                 cond_x=rec['cond_x'].numpy(), cond_edge_x=rec['cond_edge_x'].numpy(), xh=xh.numpy(), edge_x=edge_x.numpy(),
+                 noise=rec['noise'].numpy(), edge_noise=rec['edge_noise'].numpy(), alpha_t=alpha_t.numpy(), sigma_t=sigma_t.numpy(),
+                 pred=rec['pred'].numpy(), edge_pred=rec['edge_pred'].numpy(), loss=np.float64(loss.item()),
+                 grad_names=np.array(names), **{'grad_%d' % i: params[k].grad.numpy() for i, k in enumerate(names)})
+    print(fname, 'ok; loss', loss.item(), 'dense err', err, 'bytes', os.path.getsize(os.path.join(OUT, fname)))
+    if which == 'zinc':
+        savez_stable(os.path.join(OUT, 'loss2d_zinc.npz'), cfg_name=np.array(CFG[which]), seed=np.int64(seed), py_seed=np.int64(py_seed),
+                     gain=np.float32(TRAIN_GAIN), head_gain=np.float32(HEAD_GAIN_2D), n_nodes=np.array(n_nodes), coin=np.float64(coin),
+                     t=rec['t'].numpy(), noise=rec['noise'].numpy(), edge_noise=rec['edge_noise'].numpy(), loss=np.float64(loss.item()),
+                     **{'batch_' + k: v.numpy() for k, v in batch.items()})
+        print('loss2d_zinc.npz ok; bytes', os.path.getsize(os.path.join(OUT, 'loss2d_zinc.npz')))
+
+
+def loss2d_from_outputs(cfg, pred, edge_pred, xh, edge_x, nm, em, alpha_t, sigma_t):
+    """The data-prediction branch of losses.py:256-281 on given predictions (the oracle's autograd starts here)."""
+    B = xh.shape[0]
+    _, w_atom, w_edge = (float(w) for w in cfg.model.loss_weights.split(','))
+    l_atom = torch.square(pred - xh).mean(-1).sum(-1)
+    l_edge = torch.square(edge_x - edge_pred).mean(-1).reshape(B, -1).sum(-1)
+    if cfg.training.reduce_mean:
+        l_atom = l_atom / nm.squeeze(-1).sum(-1)
+        l_edge = l_edge / (em.reshape(B, -1).sum(-1) + 1e-8)
+    return (torch.sqrt(alpha_t / sigma_t) * (w_atom * l_atom + w_edge * l_edge)).mean()
+
+
+def train_drop2d_fixture(ref, which='zinc', seed=43, s1=0x2545F4914F6CDD1D, s2=0x9E3779B97F4A7C15 >> 2):
+    """Training-mode dropout of the reference with the training path's masks: the 2-D model under model.train(), each block's
+    nn.Dropout replaced by oracle/make_golden.py's DropInjector fed from oracle/philox_ref.dropout_masks.  A no-grad
+    self-conditioning call with the masks of seed s1, a grad-enabled call on its outputs with seed s2, then backward of seeded
+    output gradients.  tests/oracle2d_train.forward_dense_drop with the same masks is checked here too."""
+    from oracle import philox_ref as PR
+    from oracle.make_golden import DropInjector, savez_stable
+    import oracle2d_train as O2T
+    cfg, model = build_reference_model(ref, CFG[which], seed, head_gain=HEAD_GAIN_2D, gain=TRAIN_GAIN)
+    hp = O2.Hyper2D.from_config(cfg)
+    p = float(cfg.model.dropout)
+    assert p > 0
+    model.train()
+    n_nodes = TRAIN_NODES[which]
+    B, N = len(n_nodes), max(n_nodes)
+    nm, em = masks(n_nodes)
+    D, De, r, L = hp.D, hp.De, hp.r, hp.L
+    widths = {'A1': r * D, 'F2': D, 'A3': r * De, 'F4': De}
+    inj, hooks = [], []
+    for l in range(L):
+        blk = model._modules['e_block_%d' % l]
+        assert isinstance(blk.dropout, torch.nn.Dropout) and blk.dropout.p == p
+        d = DropInjector(l, widths)
+        d.N = N
+        blk.dropout = d
+        inj.append(d)
+
+        def pre(m, args, d=d):
+            d.edge_index = args[2]                          # forward(h, edge_attr, edge_index, ...)
+        hooks.append(blk.register_forward_pre_hook(pre))
+    _, _, xh, ex, nl = make_inputs(cfg, n_nodes, seed)
+    g = torch.Generator().manual_seed(seed + 200)
+    d_x = torch.randn(B, N, hp.nd, generator=g)
+    d_e = torch.randn(B, N, N, hp.ch, generator=g)
+    m1 = PR.dropout_masks(s1, p, n_nodes, L, D, De, r)
+    m2 = PR.dropout_masks(s2, p, n_nodes, L, D, De, r)
+
+    def run(ms, cx, cex):
+        for d in inj:
+            d.masks, d.calls = ms, 0
+        out = model(torch.ones(B), xh, nm, em, edge_x=ex, noise_level=nl, cond_x=cx, cond_edge_x=cex)
+        assert all(d.calls == 4 for d in inj)
+        return out
+
+    try:
+        with torch.no_grad():
+            r1 = run(m1, None, None)
+        model.zero_grad()
+        r2 = run(m2, r1[0], r1[1])
+        threads = torch.get_num_threads()
+        torch.set_num_threads(1)
+        ((r2[0] * d_x).sum() + (r2[1] * d_e).sum()).backward()
+        torch.set_num_threads(threads)
+    finally:
+        for h_ in hooks:
+            h_.remove()
+    params = dict(model.named_parameters())
+    names = ['e_block_%d.ff_linear%d.bias' % (l, k) for l in range(L) for k in (1, 2, 3, 4)]
+    names += ['e_block_0.ff_linear3.weight', 'e_block_%d.ff_linear4.weight' % (L - 1), 'e_block_%d.node2edge_lin.bias' % (L // 2),
+              'e_block_%d.attn_mpnn.lin_edge0.weight' % (L - 2), 'node_emb.bias', 'edge_emb.bias', 'time_mlp.0.weights',
+              'edge_exist_mlp.4.weight', 'node_pred_mlp.4.weight']
+    assert len(set(names)) == len(names) and all(params[k].grad is not None for k in names)
+    sd = {k: v.detach().clone().requires_grad_(True) for k, v in model.state_dict().items()}
+    with torch.no_grad():
+        o1 = O2T.forward_dense_drop(sd, hp, xh, nm, em, ex, None, None, nl, drop=m1)
+    err1 = max((o1[0] - r1[0]).abs().max().item(), (o1[1] - r1[1]).abs().max().item())
+    px, pe = O2T.forward_dense_drop(sd, hp, xh, nm, em, ex, r1[0], r1[1], nl, drop=m2)
+    err = max(err1, (px - r2[0]).abs().max().item(), (pe - r2[1]).abs().max().item())
+    assert err < 1e-5, "masked dense 2-D oracle vs reference (dropout): %g" % err
+    ((px * d_x).sum() + (pe * d_e).sum()).backward()
+    for k in names:
+        a, b = sd[k].grad, params[k].grad
+        rel = (a - b).abs().max().item() / (b.abs().max().item() + 1e-12)
+        assert rel < 2e-4, "masked oracle gradient of %s (dropout): rel err %g" % (k, rel)
+    with torch.no_grad():                                   # the masks matter: eval mode gives another function
+        e2 = O2.forward_dense(sd, hp, xh, nm, em, ex, r1[0], r1[1], nl)
+    assert (e2[0] - r2[0]).abs().max().item() > 1e-2 and (e2[1] - r2[1]).abs().max().item() > 1e-2
+    fname = 'train_drop2d_%s.npz' % which
+    savez_stable(os.path.join(OUT, fname), cfg_name=np.array(CFG[which]), seed=np.int64(seed), gain=np.float32(TRAIN_GAIN),
+                 head_gain=np.float32(HEAD_GAIN_2D), n_nodes=np.array(n_nodes), p=np.float32(p),
+                 seed1=np.uint64(s1), seed2=np.uint64(s2), xh=xh.numpy(), edge_x=ex.numpy(), noise_level=nl.numpy(),
+                 out1_x=r1[0].numpy(), out1_e=r1[1].numpy(), out2_x=r2[0].detach().numpy(), out2_e=r2[1].detach().numpy(),
+                 d_out_x=d_x.numpy(), d_out_e=d_e.numpy(), grad_names=np.array(names),
+                 **{'grad_%d' % i: params[k].grad.numpy() for i, k in enumerate(names)})
+    print(fname, 'ok; dense err', err, 'bytes', os.path.getsize(os.path.join(OUT, fname)))
+
+
 def manifest(ref):
     out = {}
     for which, name in CFG.items():
@@ -301,6 +536,9 @@ def main():
         'traj2d_zinc': lambda: traj_fixture(ref, 'zinc'),
         'traj2d_moses': lambda: traj_fixture(ref, 'moses'),
         'samplefn2d_zinc': lambda: samplefn_fixture(ref),
+        'grad2d_zinc': lambda: grad2d_fixture(ref, 'zinc'),
+        'grad2d_moses': lambda: grad2d_fixture(ref, 'moses'),
+        'train_drop2d_zinc': lambda: train_drop2d_fixture(ref, 'zinc'),
     }
     want = sys.argv[1:]
     for name, job in jobs.items():

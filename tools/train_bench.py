@@ -3,6 +3,12 @@ config.training.batch_size molecules with the dataset's atom-count histogram —
 double forward, dropout 0.1, loss.backward() through jodo_train_backward, AdamW + clipping + EMA.  Prints one JSON line.
 
     python tools/train_bench.py [--workload qm9|geom] [--batch B] [--steps K] [--warmup W]
+    python tools/train_bench.py --workload zinc2d|moses2d [--steps K] [--warmup W] [--runs R]
+
+The 2-D workloads (DGT_concat_2D, batch 128, atom counts from tests/golden/n_nodes_2d.json, a new CPU batch every step) time the HIP
+step (csrc/dgt2d_train.hip, fused and op-by-op form) and, on the same GPU under the same loss, optimiser and batches, the dense
+torch step — autograd through tests/oracle2d.forward_dense on the device, the baseline of tools/bench_2d.py.  The forms alternate inside
+one command, R runs each; the result (with the spread of the runs) is written to profiles/train2d_{zinc,moses}_b128.json.
 
 Work model: a grad-enabled forward + backward costs 3 x the forward's projection flops (forward, input gradient, weight gradient);
 the no-grad self-conditioning forward (half of the steps) one more; `gemm_flops_per_step` prices the projections only
@@ -186,6 +192,90 @@ def run(workload='qm9', batch=0, steps=10, warmup=3, seed=42, options=None, save
                      'first-correct kernels (train_ops.h), not yet tuned')
 
 
+def run_2d(workload='zinc2d', steps=10, warmup=3, seed=42, runs=2, batch=128):
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import oracle2d as O2                                     # the dense torch baseline (checker-side formulas, run on the device)
+    from jodo_amd import configs, losses as L
+    from jodo_amd.diffusion import NoiseScheduleVP
+    from jodo_amd.models import get_model_class, deterministic_init_
+    from jodo_amd.models.ema import ExponentialMovingAverage
+    from jodo_amd.utils import get_data_scaler
+    name, hist_name = dict(zinc2d=('vpsde_zinc_2d_jodo', 'zinc250k'), moses2d=('vpsde_moses_2d_jodo', 'moses'))[workload]
+    cfg = configs.get(name)
+    dev = torch.device('cuda:0')
+    cfg.device = dev
+    hp = O2.Hyper2D.from_config(cfg)
+    hist = O2.load_n_nodes_hist(os.path.join(ROOT, 'tests', 'golden', 'n_nodes_2d.json'), hist_name)['train_n_nodes']
+    sizes, weights = torch.tensor(list(hist.keys())), torch.tensor(list(hist.values()), dtype=torch.float64)
+    g = torch.Generator().manual_seed(seed)
+    n_batches = warmup + steps
+    batches = []
+    for k in range(n_batches):
+        nk = sizes[torch.multinomial(weights, batch, replacement=True, generator=g)].tolist()
+        b = synthetic_batch(cfg, nk, seed + 1 + k)
+        del b['positions']
+        batches.append(b)
+    ns = NoiseScheduleVP(cfg.sde.schedule, continuous_beta_0=cfg.sde.continuous_beta_0, continuous_beta_1=cfg.sde.continuous_beta_1)
+
+    class DenseTorch2D(torch.nn.Module):
+        """The registered module's parameter tree evaluated by plain torch operations on padded dense tensors (no dropout)."""
+
+        def __init__(self):
+            super().__init__()
+            self.inner = get_model_class(cfg.model.name)(cfg)
+
+        def forward(self, t, xh, node_mask, edge_mask, context=None, **kw):
+            sd = dict(self.inner.named_parameters())
+            return O2.forward_dense(sd, hp, xh, node_mask, edge_mask, kw['edge_x'], kw.get('cond_x'), kw.get('cond_edge_x'), kw['noise_level'])
+
+    def make(form):
+        if form.startswith('hip_'):
+            model = deterministic_init_(get_model_class(cfg.model.name)(cfg), seed=seed).to(dev)
+            model.train_options = {0: 1, 1: 1} if form == 'hip_fused' else {0: 0, 1: 0}
+        else:
+            model = DenseTorch2D()
+            deterministic_init_(model.inner, seed=seed)
+            model = model.to(dev)
+        state = dict(model=model, optimizer=L.get_optimizer(cfg, model.parameters()),
+                     ema=ExponentialMovingAverage(model.parameters(), decay=cfg.model.ema_decay), step=1)
+        return state, L.get_step_fn(ns, True, L.optimization_manager(cfg), get_data_scaler(cfg), cfg)
+
+    forms = ('hip_fused', 'hip_op_by_op', 'dense_torch')
+    made = {f: make(f) for f in forms}
+    times = {f: [] for f in forms}
+    losses = {}
+    for r in range(runs):
+        for f in forms:                                       # the forms alternate inside one command
+            state, step_fn = made[f]
+            torch.manual_seed(seed + r)
+            for k in range(warmup):
+                float(step_fn(state, batches[k]))
+            torch.cuda.synchronize()
+            n_selfcond = _same_coin_flips(seed + 7, steps)
+            t0 = time.perf_counter()
+            held = [step_fn(state, batches[warmup + k]).detach() for k in range(steps)]
+            torch.cuda.synchronize()
+            times[f].append((time.perf_counter() - t0) / steps)
+            losses[f] = float(held[-1])
+    out = dict(workload=name, batch=batch, steps=steps, warmup=warmup, runs=runs, self_conditioned_steps='%d of %d in every timed leg' % (n_selfcond, steps),
+               mean_sum_n2=sum(int(b['atom_mask'].sum(1).square().sum()) for b in batches) / n_batches, forms={})
+    for f in forms:
+        ts = times[f]
+        best = min(ts)
+        out['forms'][f] = dict(ms_per_step_runs=[t * 1e3 for t in ts], ms_per_step=best * 1e3, molecules_per_s=batch / best,
+                               spread_ms=(max(ts) - min(ts)) * 1e3, loss_last=losses[f])
+    out['dense_torch_over_hip_fused'] = out['forms']['dense_torch']['ms_per_step'] / out['forms']['hip_fused']['ms_per_step']
+    out['op_by_op_over_fused'] = out['forms']['hip_op_by_op']['ms_per_step'] / out['forms']['hip_fused']['ms_per_step']
+    out['ratio_note'] = ('the dense-torch leg runs WITHOUT dropout (tests/oracle2d.forward_dense has none) while the HIP legs run dropout 0.1 and '
+                         'draw a seed per model call: the ratio flatters the baseline slightly; every form keeps its model and optimiser state '
+                         'across the runs, so run 2 times later weights than run 1 (same work per step)')
+    out['note'] = ('one optimiser step = (50 %: no-grad self-conditioning forward) + grad forward + backward + AdamW / clipping / EMA on a new CPU '
+                   'batch; hip_fused / hip_op_by_op: csrc/dgt2d_train.hip with jodo_train2d_set_option 0 and 1 at 1 / 0 (dropout 0.1 active); '
+                   'dense_torch: autograd through tests/oracle2d.forward_dense on the same GPU (padded dense tensors, no '
+                   'dropout); ms_per_step = best of the runs, spread_ms = max - min over the runs')
+    return out
+
+
 def cpu_step(workload='qm9', batch=16, steps=2, seed=42, threads=16):
     """The same optimiser-free step on the host: forward + loss.backward() through the port of the reference's sparse formulation
     (oracle.forward_faithful under torch.autograd, eval-mode dropout) — what the reference's CPU training step costs, per molecule."""
@@ -229,7 +319,17 @@ if __name__ == '__main__':
     ap.add_argument('--cpu', action='store_true', help='also time the host port of the same forward + backward (small batch)')
     ap.add_argument('--train-opt', action='append', default=[], help='jodo_train_set_option=value (A/B runs), e.g. 0=0 1=0: op-by-op forward / backward')
     ap.add_argument('--save-always', action='store_true', help='the no-grad self-conditioning forward keeps its activations too (round-4 behaviour)')
+    ap.add_argument('--runs', type=int, default=2, help='2-D workloads: runs per form (the forms alternate)')
     a = ap.parse_args()
+    if a.workload in ('zinc2d', 'moses2d'):
+        out = run_2d(a.workload, a.steps, a.warmup, runs=a.runs, batch=a.batch or 128)
+        if (a.batch or 128) == 128:
+            os.makedirs(os.path.join(ROOT, 'profiles'), exist_ok=True)
+            with open(os.path.join(ROOT, 'profiles', 'train2d_%s_b128.json' % a.workload[:-2]), 'w') as f:
+                json.dump(out, f, indent=1)
+                f.write('\n')
+        print(json.dumps(out))
+        sys.exit(0)
     out = run(a.workload, a.batch, a.steps, a.warmup, options={int(o.split('=')[0]): int(o.split('=')[1]) for o in a.train_opt}, save_always=a.save_always)
     out['train_options'] = a.train_opt; out['save_always'] = a.save_always
     if a.cpu:
