@@ -447,6 +447,28 @@ int jodo_dgt2d_forward(const jodo_cfg2d* cfg, int B, int N, const int32_t* n_nod
                        const int64_t* woff, int n_woff, const float* xh, const float* edge_x, const float* cond_x,
                        const float* cond_edge_x, const float* noise_level, float* out_xh, float* out_edge, int32_t* flags_dev,
                        void* workspace, int force_directed, int max_blocks, void* stream);
+/* Pair-symmetric attention walk (opt-in; csrc/dgt2d_forward.hip k2d_attn_pair): with symmetric inputs every unordered pair's edge
+ * row is normalised and pushed through lin_edge0 / lin_edge1 + tanh once and serves both directions.  Both atoms of a pair sit in one
+ * workgroup: the batch is cut into groups of whole molecules of up to 128 atom slots (largest molecule first, gaps filled with the
+ * largest remaining molecule that fits; N <= 64, so every molecule fits).
+ * jodo_dgt2d_pair_layout: out[0] = int32 words of the group descriptor, out[1] = groups, out[2] = work items, out[3] / out[4] = word
+ * offsets of the item table and of the slot table, out[5] = slots per group (128), out[6] = words per item (4), out[7] = reserved.
+ * jodo_dgt2d_pair_fill_desc writes it into HOST memory: items [items][4] = (group, first offset, last offset, 0), longest first (one
+ * item per group with the offsets 1 .. max n / 2 of its molecules); slots [groups][128] = (molecule << 8) | atom, a molecule's atoms
+ * in consecutive slots, -1 for an unused slot.  The walk: the atom i of a molecule of n atoms meets partner (i + d) mod n at every
+ * offset d <= n / 2 of its item; at d = n / 2 of an even n both atoms of a pair meet it and each takes it as a target only. */
+enum jodo2d_walk { JODO_2D_WALK_DIRECTED = 0, JODO_2D_WALK_PAIR = 1 };
+int jodo_dgt2d_pair_layout(const jodo_cfg2d* cfg, int B, int N, const int32_t* n_nodes_host, int64_t* out8);
+int jodo_dgt2d_pair_fill_desc(const jodo_cfg2d* cfg, int B, int N, const int32_t* n_nodes_host, int32_t* desc_host, int64_t n_words);
+/* jodo_dgt2d_forward with a walk selector.  walk = JODO_2D_WALK_DIRECTED: exactly jodo_dgt2d_forward (pair_desc_dev is not read).
+ * walk = JODO_2D_WALK_PAIR: pair_desc_dev is the device copy of the group descriptor; the choice is made on the device, without a
+ * host synchronisation: with flags[0] == 1 k2d_attn_pair does the attention and the directed kernel leaves at once, with
+ * flags[0] == 0 (asymmetric inputs, force_directed) it is the other way round.  The kernel that did the work records it in
+ * flags_dev[2] (1 = pair walk, 0 = directed); jodo_dgt2d_forward never writes that slot. */
+int jodo_dgt2d_forward_walk(const jodo_cfg2d* cfg, int B, int N, const int32_t* n_nodes_host, const void* desc_dev,
+                            const void* pair_desc_dev, int walk, const float* packed_w, const int64_t* woff, int n_woff, const float* xh,
+                            const float* edge_x, const float* cond_x, const float* cond_edge_x, const float* noise_level, float* out_xh,
+                            float* out_edge, int32_t* flags_dev, void* workspace, int force_directed, int max_blocks, void* stream);
 /* Ancestral update of the 2-D sampler (sampling.py:637-658) for a node tensor WITHOUT position channels, replayed-draw form:
  * x_mean = cx x + cp pred, x_next = x_mean + sigma eps_node masked to the real atoms (all node channels are plain masked noise);
  * the edge tensors likewise with eps_edge [B,N,N,ch] read from its strict lower triangle for both orientations of a pair (the

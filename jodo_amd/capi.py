@@ -28,6 +28,7 @@ def lib():
         _lib = ctypes.CDLL(LIB_PATH)
         _lib.jodo_last_error.restype = ctypes.c_char_p
         _bind_2d_sampling(_lib)
+        _bind_2d_pair(_lib)
     return _lib
 
 
@@ -43,6 +44,24 @@ def _bind_2d_sampling(L):
     step.argtypes = [i, i, i, i, p, f, f, f, p, p, ctypes.c_uint64, ctypes.c_uint32] + [p] * 9
     dec.argtypes = [i] * 7 + [f, f, f] + [p] * 7
     step.restype = dec.restype = i
+
+
+WALK_DIRECTED, WALK_PAIR = 0, 1                 # enum jodo2d_walk
+
+
+def _bind_2d_pair(L):
+    """Argument types of the pair-walk exports of the 2-D model (jodo_dgt2d_pair_layout, jodo_dgt2d_pair_fill_desc,
+    jodo_dgt2d_forward_walk; include/jodo_hip.h)."""
+    i, p = ctypes.c_int, ctypes.c_void_p
+    try:
+        lay, fill, fwd = L.jodo_dgt2d_pair_layout, L.jodo_dgt2d_pair_fill_desc, L.jodo_dgt2d_forward_walk
+    except AttributeError as e:
+        raise JodoHipError("%s lacks the 2-D pair-walk exports (%s): rebuild it with python -c 'import __graft_entry__ as g; g.build()'"
+                           % (LIB_PATH, e))
+    lay.argtypes = [p, i, i, p, p]
+    fill.argtypes = [p, i, i, p, p, ctypes.c_int64]
+    fwd.argtypes = [p, i, i, p, p, p, i, p, p, i] + [p] * 9 + [i, i, p]
+    lay.restype = fill.restype = fwd.restype = i
 
 
 def check(code, what=''):

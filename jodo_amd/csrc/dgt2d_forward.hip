@@ -7,10 +7,13 @@
 //
 // Per block:  k2d_ln_mod (LN1 + modulate) -> k2d_gemm (q | k | v) -> k2d_attn -> k2d_gemm (node2edge) -> k2d_ln_mod (residual, LN2,
 // modulate) -> k2d_gemm x 2 (node FFN) -> k2d_gemm (node readout) -> k2d_pair (edge residual, LN, FFN, readout).
+// jodo_dgt2d_forward_walk with the pair walk puts k2d_attn_pair in k2d_attn's place when the inputs are symmetric: one evaluation of both
+// tanh projections per unordered pair, groups of whole molecules per workgroup, LDS hand-over between the two atoms of a pair.
 // Every projection is exact fp32 on v_mfma_f32_32x32x2_f32 in the strip model of dgt_device.h (32 items per wave, weights as A operand,
 // packed by csrc/dgt2d_pack.cpp).  The two per-edge kernels are persistent: a workgroup of four waves copies the block's weights
 // (128 KiB lin_edge0 | lin_edge1; 72 KiB edge FFN + readout) into LDS once and its waves then walk over the items.
 #include "dgt_device.h"
+#include <vector>
 #include "jodo_hip_internal.h"
 #include "../../include/jodo_hip.h"
 
@@ -303,7 +306,14 @@ __device__ __forceinline__ f32x16 mfma_lds(const float4* tile, int lane, const f
 // ---- 2-D attention: one wave per target atom, sources in chunks of 32 (one per lane pair), running softmax ---------------------------
 // Lane (j, h): source r0 + j, half h.  Scores: half 0 holds attention heads 0 (adjacency) .. 7, half 1 heads 8 .. 15; the value /
 // lin_edge1 channels of block ob on half h are those of head 8 h + ob (row maps of csrc/dgt2d_pack.cpp).
+// DEFER (the pair-walk entry launches both attention kernels): leave at once when the inputs are symmetric, k2d_attn_pair does the
+// work then; otherwise record in flags[2] that the directed walk ran.
+template <bool DEFER>
 __global__ __launch_bounds__(256, 1) void k2d_attn(K2 A) {
+    if (DEFER) {
+        if (A.flags[0]) return;
+        if (blockIdx.x == 0 && threadIdx.x == 0) const_cast<int32_t*>(A.flags)[2] = 0;
+    }
     __shared__ float4 wl[16 * 512];
     {
         const float4* src = reinterpret_cast<const float4*>(A.W + A.wb[J2B_LE_W]);
@@ -395,6 +405,193 @@ __global__ __launch_bounds__(256, 1) void k2d_attn(K2 A) {
         if (j < 16) {
 #pragma unroll
             for (int ob = 0; ob < 8; ++ob) out_row[(8 * h + ob) * 16 + j] = den[ob] > 0.f ? out[ob] / den[ob] : 0.f;
+        }
+    }
+}
+
+// ---- 2-D attention, pair-symmetric walk (opt-in; symmetric inputs only) ---------------------------------------------------------------
+// A workgroup of four waves owns a group of whole molecules in 128 atom slots (jodo_dgt2d_pair_fill_desc).  Lane pair (j, h) of wave w
+// owns the atom in slot 32 w + j as a TARGET; half h scores heads 8 h .. 8 h + 7 as in k2d_attn.  The waves walk the circulant offsets
+// d = 1 .. n / 2: at offset d the lane of atom i evaluates the unordered pair {i, p = (i + d) mod n} once (row (min, max) of the edge
+// state: LayerNorm, modulate, both tanh projections) and forms both directions from it: source p into its own softmax, and source i
+// into p's, which it hands over through LDS (8 scores per half, then the unweighted message v_i * T1 block by block).  It receives the
+// same from the lane of (i - d) mod n.  At d = n / 2 of an even n both lanes meet the same pair: each acts as target only.
+// The running (max, sum) and the 128 message accumulators are per lane, so there is no cross-lane reduction, no atomic and no
+// scatter; a target's sum order is the offset order, own source before received source, whatever its slot, group or batch.
+// The 128 message accumulators of a lane wait in accumulation registers while a pass does not touch them (the vector ALU reaches 256
+// of the 512 registers of a wave; left alone the compiler sends part of them to scratch instead).
+__device__ __forceinline__ void park(float (&out)[8][16]) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+#pragma unroll
+        for (int s = 0; s < 16; ++s) asm volatile("" : "+a"(out[k][s]));
+}
+struct Pair2 {
+    const int* items;            // [n_items][4]: group, first offset, last offset, 0; longest first
+    const int* slots;            // [groups][128]: (molecule << 8) | atom, or -1
+    int n_items;
+};
+constexpr int GS = 128;
+
+__global__ __launch_bounds__(256, 1) void k2d_attn_pair(K2 A, Pair2 Q) {
+    if (!A.flags[0]) return;                                 // asymmetric inputs / force_directed: k2d_attn<true> does the work
+    if (blockIdx.x == 0 && threadIdx.x == 0) const_cast<int32_t*>(A.flags)[2] = 1;
+    __shared__ float4 wl[16 * 512];                          // lin_edge0 | lin_edge1, 128 KiB
+    __shared__ float4 hs[2 * 2 * GS];                        // hand-over, scores:  [quad][half][slot], 8 KiB
+    __shared__ float4 hm[4 * 2 * GS];                        // hand-over, one message block: [quad][half][slot], 16 KiB
+    {
+        const float4* src = reinterpret_cast<const float4*>(A.W + A.wb[J2B_LE_W]);
+        for (int i = threadIdx.x; i < 16 * 512; i += 256) wl[i] = src[i];
+    }
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
+    const int slot = wave * 32 + j, uni = A.flags[1];
+    const int rounds = (Q.n_items + (int)gridDim.x - 1) / (int)gridDim.x;
+    for (int rd = 0; rd < rounds; ++rd) {
+        // items are sorted longest first; odd rounds run backwards so that a workgroup's long item is followed by a short one
+        const int it = rd * (int)gridDim.x + ((rd & 1) ? (int)gridDim.x - 1 - (int)blockIdx.x : (int)blockIdx.x);
+        if (it >= Q.n_items) continue;                       // (uniform over the workgroup)
+        const int g = Q.items[4 * it], d_first = Q.items[4 * it + 1], d_last = Q.items[4 * it + 2];
+        const int code = Q.slots[(size_t)g * GS + slot];
+        const bool used = code >= 0;
+        const int b = used ? code >> 8 : 0, i = used ? code & 255 : 0;
+        const int n = A.mol_n[b], noff = A.mol_noff[b];
+        const size_t eoff = (size_t)A.mol_eoff[b];
+        const int t = noff + i;
+        const float* md = A.mods + (size_t)(uni ? 0 : b) * MODW + (size_t)A.layer * MODB + 6 * D2;
+        const float* own = A.qkv + (size_t)t * 3 * D2 + h * 128;             // q | k | v of this atom at +0 | +D2 | +2 D2
+        float mx[8], den[8], out[8][16];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            mx[k] = -INFINITY; den[k] = 0.f;
+#pragma unroll
+            for (int s = 0; s < 16; ++s) out[k][s] = 0.f;
+        }
+        for (int d = d_first; d <= d_last; ++d) {
+            const bool act = used && 2 * d <= n;             // this lane has a pair at this offset
+            const bool recv = used && 2 * d < n;             // ... and is the partner of another lane's pair
+            int p = i + d, s_at = i - d;
+            if (p >= n) p -= n;
+            if (s_at < 0) s_at += n;
+            if (!act) p = i;                                 // idle lanes read a live address (the diagonal row) and drop the result
+            const int sslot = recv ? slot - i + s_at : slot; // the slot of the lane that sends to this one
+            const size_t row = eoff + (size_t)min(i, p) * n + max(i, p);
+            float et[32];
+            load_nat<2>(A.e + row * DE, h, et);
+            layer_norm<32>(et);
+            modulate<2>(et, md, md + DE, h);
+            const float* par = A.qkv + (size_t)(noff + p) * 3 * D2 + h * 128;
+            float so[7], to = 0.f, ss[7], ts = 0.f;
+#pragma unroll
+            for (int k = 0; k < 7; ++k) { so[k] = 0.f; ss[k] = 0.f; }
+            park(out);                                       // the score pass needs the vector registers
+#pragma unroll
+            for (int ob = 0; ob < 8; ++ob) {
+                const f32x16 acc = mfma_lds(wl + ob * 512, lane, et, zero16());
+                float tt[16];
+                tanh16(acc, tt);
+                const float* pb = launder(par) + ob * 16;    // (opaque per block: keeps the loads of later blocks below this one)
+                const float* ib = launder(own) + ob * 16;
+                {                                            // source p -> target i
+                    float qi[16], kp[16];
+                    load16(ib, qi);
+                    load16(pb + D2, kp);
+#pragma unroll
+                    for (int s = 0; s < 16; ++s) {
+                        const int c = ob * 16 + s;
+                        const float po = qi[s] * kp[s] * tt[s];
+                        if (c < 119) so[c / 17] += po; else to += po;
+                    }
+                }
+                {                                            // source i -> target p
+                    float qp[16], ki[16];
+                    load16(pb, qp);
+                    load16(ib + D2, ki);
+#pragma unroll
+                    for (int s = 0; s < 16; ++s) {
+                        const int c = ob * 16 + s;
+                        const float ps = qp[s] * ki[s] * tt[s];
+                        if (c < 119) ss[c / 17] += ps; else ts += ps;
+                    }
+                }
+                // (the sums are pinned here: instruction selection otherwise defers the eight blocks' tanh and products behind all
+                // eight MFMA chains, with eight accumulator blocks and every row load live at once)
+#pragma unroll
+                for (int k = 0; k < 7; ++k) asm volatile("" : "+v"(so[k]), "+v"(ss[k]));
+                asm volatile("" : "+v"(to), "+v"(ts));
+                pipeline_fence();
+            }
+            to = pair_sum(to);
+            ts = pair_sum(ts);
+            float So[8], Ss[8];
+            if (h == 0) {
+                float ao = 1.f, as = 1.f;
+                if (A.cond_edge_x) {
+                    ao = A.cond_edge_x[(((size_t)b * A.N + p) * A.N + i) * A.ch] >= A.th ? 1.f : -1e10f;
+                    as = A.cond_edge_x[(((size_t)b * A.N + i) * A.N + p) * A.ch] >= A.th ? 1.f : -1e10f;
+                }
+                So[0] = ao; Ss[0] = as;
+            } else {
+                So[0] = to * 0.25f; Ss[0] = ts * 0.25f;
+            }
+#pragma unroll
+            for (int k = 0; k < 7; ++k) { So[1 + k] = so[k] * 0.25f; Ss[1 + k] = ss[k] * 0.25f; }
+            hs[h * GS + slot] = make_float4(Ss[0], Ss[1], Ss[2], Ss[3]);
+            hs[2 * GS + h * GS + slot] = make_float4(Ss[4], Ss[5], Ss[6], Ss[7]);
+            __syncthreads();
+            float Sr[8];
+            {
+                const float4 a0 = hs[h * GS + sslot], a1 = hs[2 * GS + h * GS + sslot];
+                Sr[0] = a0.x; Sr[1] = a0.y; Sr[2] = a0.z; Sr[3] = a0.w; Sr[4] = a1.x; Sr[5] = a1.y; Sr[6] = a1.z; Sr[7] = a1.w;
+            }
+            float w1[8], w2[8], fsc[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const float s1 = act ? So[k] : -INFINITY, s2 = recv ? Sr[k] : -INFINITY;
+                const float mnew = fmaxf(mx[k], fmaxf(s1, s2));
+                const float muse = mnew == -INFINITY ? 0.f : mnew;
+                w1[k] = act ? fast_exp(s1 - muse) : 0.f;
+                w2[k] = recv ? fast_exp(s2 - muse) : 0.f;
+                fsc[k] = fast_exp(mx[k] - muse);
+                den[k] = (den[k] * fsc[k] + w1[k]) + w2[k];
+                mx[k] = mnew;
+            }
+#pragma unroll
+            for (int ob = 0; ob < 8; ++ob) {
+                const f32x16 acc = mfma_lds(wl + (8 + ob) * 512, lane, et, zero16());
+                float tt[16], vp[16], vi[16];
+                tanh16(acc, tt);
+                load16(launder(par) + 2 * D2 + ob * 16, vp);
+                load16(launder(own) + 2 * D2 + ob * 16, vi);
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    hm[(q * 2 + h) * GS + slot] = make_float4(vi[4 * q] * tt[4 * q], vi[4 * q + 1] * tt[4 * q + 1], vi[4 * q + 2] * tt[4 * q + 2],
+                                                              vi[4 * q + 3] * tt[4 * q + 3]);
+#pragma unroll
+                for (int s = 0; s < 16; ++s) out[ob][s] = fmaf(out[ob][s], fsc[ob], w1[ob] * (vp[s] * tt[s]));
+                __syncthreads();
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const float4 m = hm[(q * 2 + h) * GS + sslot];
+                    out[ob][4 * q + 0] = fmaf(w2[ob], m.x, out[ob][4 * q + 0]);
+                    out[ob][4 * q + 1] = fmaf(w2[ob], m.y, out[ob][4 * q + 1]);
+                    out[ob][4 * q + 2] = fmaf(w2[ob], m.z, out[ob][4 * q + 2]);
+                    out[ob][4 * q + 3] = fmaf(w2[ob], m.w, out[ob][4 * q + 3]);
+                }
+#pragma unroll
+                for (int s = 0; s < 16; ++s) asm volatile("" : "+a"(out[ob][s]));
+                if (ob < 7) __syncthreads();                 // (after block 7 the next offset's score barrier separates the reuse)
+            }
+        }
+        if (used) {                                          // n == 1: no offsets, den = 0, a zero row
+            float* out_row = A.hn + (size_t)t * D2 + h * 128;
+#pragma unroll
+            for (int ob = 0; ob < 8; ++ob) {
+                float v[16];
+#pragma unroll
+                for (int s = 0; s < 16; ++s) v[s] = den[ob] > 0.f ? out[ob][s] / den[ob] : 0.f;
+                store16(out_row + ob * 16, v);
+            }
         }
     }
 }
@@ -591,6 +788,56 @@ int gemm(hipStream_t st, const float* X, int ldx, float* Y, int ldy, const float
     return JODO_OK;
 }
 
+// ---- groups of whole molecules for the pair walk (host) -----------------------------------------------------------------------------
+// Molecules by descending size; a group takes the largest remaining molecule, then keeps taking the largest remaining one that still
+// fits its 128 slots (the 3-D plan's rule).  N <= 64: every molecule fits a group.  One work item per group, carrying the offsets
+// 1 .. max n / 2 of its molecules: a lane's running softmax lives in registers across all offsets of its atom, so a group's offset
+// range is not split (splitting it needs a merge pass; unmeasured).  Items are sorted longest first.
+struct PairLay {
+    int groups, items, off_items, off_slots, words;
+};
+struct PairGroup { int first, count, dmax; };               // range of `order`, largest n / 2
+
+int make_pair_groups(int B, int N, const int32_t* n, std::vector<int>* order, std::vector<PairGroup>* groups) {
+    if (B <= 0 || N <= 0 || !n) return jodo_set_error(JODO_ERR_ARG, "dgt2d_pair: bad batch");
+    if (N > 64) return jodo_set_error(JODO_ERR_UNSUPPORTED, "dgt2d_pair: padded width %d above 64", N);
+    if (B >= (1 << 19)) return jodo_set_error(JODO_ERR_UNSUPPORTED, "dgt2d_pair: batch %d too large", B);
+    std::vector<int> head(66, 0), next_at(66, 0);
+    for (int b = 0; b < B; ++b) {
+        if (n[b] < 1 || n[b] > N) return jodo_set_error(JODO_ERR_ARG, "dgt2d_pair: n_nodes[%d]=%d outside [1,%d]", b, n[b], N);
+        ++head[n[b] + 1];
+    }
+    for (int s = 1; s < 66; ++s) head[s] += head[s - 1];    // head[s] .. head[s + 1]: molecules of size s, ascending index
+    std::vector<int> by_size(B);
+    next_at = head;
+    for (int b = 0; b < B; ++b) by_size[next_at[n[b]]++] = b;
+    next_at = head;                                          // next unplaced molecule of each size
+    order->clear(); groups->clear();
+    order->reserve(B);
+    int left = B, top = 64;
+    while (left > 0) {
+        PairGroup g{(int)order->size(), 0, 0};
+        int room = GS;
+        for (;;) {
+            while (top > 0 && next_at[top] == head[top + 1]) --top;
+            int s = top < room ? top : room;
+            while (s > 0 && next_at[s] == head[s + 1]) --s;
+            if (s == 0) break;
+            order->push_back(by_size[next_at[s]++]);
+            if (g.count == 0) g.dmax = s / 2;
+            ++g.count; room -= s; --left;
+        }
+        groups->push_back(g);
+    }
+    return JODO_OK;
+}
+
+PairLay pair_lay(int groups) {
+    PairLay l;
+    l.groups = groups; l.items = groups; l.off_items = 0; l.off_slots = 4 * groups; l.words = 4 * groups + GS * groups;
+    return l;
+}
+
 }  // namespace
 
 extern "C" int jodo_dgt2d_layout(const jodo_cfg2d* cfg, int B, int N, const int32_t* n_nodes, int64_t* out8) {
@@ -622,10 +869,11 @@ extern "C" int jodo_dgt2d_fill_desc(const jodo_cfg2d* cfg, int B, int N, const i
     return JODO_OK;
 }
 
-extern "C" int jodo_dgt2d_forward(const jodo_cfg2d* cfg, int B, int N, const int32_t* n_nodes, const void* desc_dev, const float* packed_w,
-                                  const int64_t* woff, int n_woff, const float* xh, const float* edge_x, const float* cond_x,
-                                  const float* cond_edge_x, const float* noise_level, float* out_xh, float* out_edge, int32_t* flags_dev,
-                                  void* workspace, int force_directed, int max_blocks, void* stream) {
+// pair_desc_dev != NULL: the pair-walk entry (both attention kernels are launched, the flags decide on the device which one works)
+static int forward_2d(const jodo_cfg2d* cfg, int B, int N, const int32_t* n_nodes, const void* desc_dev, const void* pair_desc_dev,
+                      const float* packed_w, const int64_t* woff, int n_woff, const float* xh, const float* edge_x, const float* cond_x,
+                      const float* cond_edge_x, const float* noise_level, float* out_xh, float* out_edge, int32_t* flags_dev,
+                      void* workspace, int force_directed, int max_blocks, void* stream) {
     if (!desc_dev || !packed_w || !woff || !xh || !edge_x || !noise_level || !out_xh || !out_edge || !flags_dev || !workspace)
         return jodo_set_error(JODO_ERR_ARG, "dgt2d_forward: null argument");
     if (int rc = jodo_dgt2d_check_cfg(cfg)) return rc;
@@ -635,6 +883,15 @@ extern "C" int jodo_dgt2d_forward(const jodo_cfg2d* cfg, int B, int N, const int
         return jodo_set_error(JODO_ERR_ARG, "dgt2d_forward: weight table has %d slots, expected %d", n_woff, J2_GLOBAL_COUNT + cfg->n_layers * J2B_BLOCK_COUNT);
     Lay l;
     if (int rc = make_lay(B, N, n_nodes, &l)) return rc;
+    Pair2 Q{nullptr, nullptr, 0};
+    if (pair_desc_dev) {
+        std::vector<int> order;
+        std::vector<PairGroup> groups;
+        if (int rc = make_pair_groups(B, N, n_nodes, &order, &groups)) return rc;
+        const PairLay pl = pair_lay((int)groups.size());
+        const int* pd = static_cast<const int*>(pair_desc_dev);
+        Q.items = pd + pl.off_items; Q.slots = pd + pl.off_slots; Q.n_items = pl.items;
+    }
     hipStream_t st = (hipStream_t)stream;
     const int* dsc = static_cast<const int*>(desc_dev);
     float* ws = static_cast<float*>(workspace);
@@ -671,7 +928,12 @@ extern "C" int jodo_dgt2d_forward(const jodo_cfg2d* cfg, int B, int N, const int
         const float* gate_mlp = A.mods + (size_t)lyr * MODB + 5 * D2;
         L2D(k2d_ln_mod, (l.Nn + 3) / 4, 256, A, A.h, (const float*)nullptr, A.hm, 0, 0, D2);
         if ((rc = gemm(st, A.hm, D2, A.qkv, 3 * D2, W + A.wb[J2B_QKV_W], W + A.wb[J2B_QKV_B], l.Nn, D2, 24, 0, A))) return rc;
-        L2D(k2d_attn, persist, 256, A);
+        if (pair_desc_dev) {
+            L2D(k2d_attn_pair, persist, 256, A, Q);
+            L2D(k2d_attn<true>, persist, 256, A);
+        } else {
+            L2D(k2d_attn<false>, persist, 256, A);
+        }
         if ((rc = gemm(st, A.hn, D2, A.u, DE, W + A.wb[J2B_N2E_W], nullptr, l.Nn, D2, 2, 0, A))) return rc;
         L2D(k2d_ln_mod, (l.Nn + 3) / 4, 256, A, A.h, (const float*)A.hn, A.hm, 2 * D2, 3 * D2, 4 * D2);
         if ((rc = gemm(st, A.hm, D2, A.f1, 2 * D2, W + A.wb[J2B_FF1_W], W + A.wb[J2B_FF1_B], l.Nn, D2, 16, 1, A))) return rc;
@@ -685,6 +947,62 @@ extern "C" int jodo_dgt2d_forward(const jodo_cfg2d* cfg, int B, int N, const int
     if ((rc = gemm(st, A.nh2, D2 / 2, A.nh3, 32, W + A.wg[J2_NH3_W], W + A.wg[J2_NH3_B], l.Nn, D2 / 2, 1, 0, A))) return rc;
     L2D(k2d_finalize_nodes, (l.Nn * A.nd + 255) / 256, 256, A);
     if (l.P > 0) L2D(k2d_edge_head, (l.P + 31) / 32, 64, A);
+    return JODO_OK;
+}
+
+extern "C" int jodo_dgt2d_forward(const jodo_cfg2d* cfg, int B, int N, const int32_t* n_nodes, const void* desc_dev, const float* packed_w,
+                                  const int64_t* woff, int n_woff, const float* xh, const float* edge_x, const float* cond_x,
+                                  const float* cond_edge_x, const float* noise_level, float* out_xh, float* out_edge, int32_t* flags_dev,
+                                  void* workspace, int force_directed, int max_blocks, void* stream) {
+    return forward_2d(cfg, B, N, n_nodes, desc_dev, nullptr, packed_w, woff, n_woff, xh, edge_x, cond_x, cond_edge_x, noise_level, out_xh,
+                      out_edge, flags_dev, workspace, force_directed, max_blocks, stream);
+}
+
+extern "C" int jodo_dgt2d_forward_walk(const jodo_cfg2d* cfg, int B, int N, const int32_t* n_nodes, const void* desc_dev,
+                                       const void* pair_desc_dev, int walk, const float* packed_w, const int64_t* woff, int n_woff,
+                                       const float* xh, const float* edge_x, const float* cond_x, const float* cond_edge_x,
+                                       const float* noise_level, float* out_xh, float* out_edge, int32_t* flags_dev, void* workspace,
+                                       int force_directed, int max_blocks, void* stream) {
+    if (walk != JODO_2D_WALK_DIRECTED && walk != JODO_2D_WALK_PAIR)
+        return jodo_set_error(JODO_ERR_ARG, "dgt2d_forward_walk: walk %d is neither directed (0) nor pair (1)", walk);
+    if (walk == JODO_2D_WALK_PAIR && !pair_desc_dev)
+        return jodo_set_error(JODO_ERR_ARG, "dgt2d_forward_walk: the pair walk needs the group descriptor");
+    return forward_2d(cfg, B, N, n_nodes, desc_dev, walk == JODO_2D_WALK_PAIR ? pair_desc_dev : nullptr, packed_w, woff, n_woff, xh, edge_x,
+                      cond_x, cond_edge_x, noise_level, out_xh, out_edge, flags_dev, workspace, force_directed, max_blocks, stream);
+}
+
+extern "C" int jodo_dgt2d_pair_layout(const jodo_cfg2d* cfg, int B, int N, const int32_t* n_nodes, int64_t* out8) {
+    if (!out8) return jodo_set_error(JODO_ERR_ARG, "dgt2d_pair_layout: null argument");
+    if (int rc = jodo_dgt2d_check_cfg(cfg)) return rc;
+    std::vector<int> order;
+    std::vector<PairGroup> groups;
+    if (int rc = make_pair_groups(B, N, n_nodes, &order, &groups)) return rc;
+    const PairLay pl = pair_lay((int)groups.size());
+    out8[0] = pl.words; out8[1] = pl.groups; out8[2] = pl.items; out8[3] = pl.off_items; out8[4] = pl.off_slots; out8[5] = GS;
+    out8[6] = 4; out8[7] = 0;
+    return JODO_OK;
+}
+
+extern "C" int jodo_dgt2d_pair_fill_desc(const jodo_cfg2d* cfg, int B, int N, const int32_t* n_nodes, int32_t* desc, int64_t n_words) {
+    if (!desc) return jodo_set_error(JODO_ERR_ARG, "dgt2d_pair_fill_desc: null argument");
+    if (int rc = jodo_dgt2d_check_cfg(cfg)) return rc;
+    std::vector<int> order;
+    std::vector<PairGroup> groups;
+    if (int rc = make_pair_groups(B, N, n_nodes, &order, &groups)) return rc;
+    const PairLay pl = pair_lay((int)groups.size());
+    if (n_words < pl.words) return jodo_set_error(JODO_ERR_ARG, "dgt2d_pair_fill_desc: %lld words, need %d", (long long)n_words, pl.words);
+    // groups come out in descending order of their largest molecule, which is the order of their offset counts: longest items first
+    for (int g = 0; g < pl.groups; ++g) {
+        int32_t* item = desc + pl.off_items + 4 * g;
+        item[0] = g; item[1] = 1; item[2] = groups[g].dmax; item[3] = 0;
+        int32_t* slots = desc + pl.off_slots + (size_t)GS * g;
+        int at = 0;
+        for (int m = 0; m < groups[g].count; ++m) {
+            const int b = order[groups[g].first + m];
+            for (int i = 0; i < n_nodes[b]; ++i) slots[at++] = (b << 8) | i;
+        }
+        for (; at < GS; ++at) slots[at] = -1;
+    }
     return JODO_OK;
 }
 

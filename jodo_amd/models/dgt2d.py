@@ -9,6 +9,9 @@ The arithmetic runs in libjodo_hip.so (csrc/dgt2d_forward.hip, `jodo_dgt2d_forwa
 packed once (csrc/dgt2d_pack.cpp), a descriptor and a workspace are built per batch of atom counts.  There is no CPU or eager
 fallback and no split-bf16 form for this model — those raise.
 
+`model.pair_attention = True` (opt-in, runtime state) selects the pair-symmetric attention walk (`jodo_dgt2d_forward_walk`, kernel
+k2d_attn_pair): with symmetric inputs every unordered pair is evaluated once; `model.last_flags[2]` tells which walk ran.
+
 Training is opt-in: with `model.hip_training = True` (jodo_amd.losses.get_step_fn sets it when asked for a training step) a
 grad-enabled call runs csrc/dgt2d_train.hip through jodo_amd.train.TrainEngine2D and `loss.backward()` fills every parameter's
 gradient; a default module keeps refusing grad-enabled calls ("inference only").
@@ -98,6 +101,8 @@ class DGT_concat_2D(nn.Module):
         self.max_blocks = -1          # tests: stop after this many blocks (the workspace then holds h and e of that block)
         self.last_flags = None
         self.hip_training = False     # opt-in: grad-enabled calls go through the HIP training path (csrc/dgt2d_train.hip)
+        self.pair_attention = False   # opt-in: the pair-symmetric attention walk (k2d_attn_pair) when the inputs are symmetric;
+                                      # last_flags[2] tells which walk ran (1 = pair, 0 = directed).  The training path ignores it.
         self.register_load_state_dict_post_hook(_drop_packed_after_load)
 
     # -- weights (same invalidation rules as _DGTBase._weights) ------------------------------------
@@ -159,7 +164,27 @@ class DGT_concat_2D(nn.Module):
         if len(self._plans) >= 8:                        # bounded cache
             self._plans.pop(next(iter(self._plans)))
         self._plans[key] = plan
+        if self.pair_attention:
+            self._pair_desc(plan, device)
         return plan
+
+    def _pair_desc(self, plan, device):
+        """The group descriptor of the pair walk (jodo_dgt2d_pair_fill_desc), built once per plan from its host-side atom counts."""
+        desc = plan.get('pair_desc')
+        if desc is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("pair_attention was switched on under graph capture for a batch planned without it: run one eager "
+                                   "call with pair_attention = True first")
+            L = capi.lib()
+            lay = (ctypes.c_int64 * 8)()
+            n_ptr = plan['n_nodes'].ctypes.data_as(ctypes.c_void_p)
+            capi.check(L.jodo_dgt2d_pair_layout(ctypes.byref(self._cfg_struct), plan['B'], plan['N'], n_ptr, lay), 'jodo_dgt2d_pair_layout')
+            host = torch.empty(int(lay[0]), dtype=torch.int32)
+            capi.check(L.jodo_dgt2d_pair_fill_desc(ctypes.byref(self._cfg_struct), plan['B'], plan['N'], n_ptr,
+                                                   ctypes.c_void_p(host.data_ptr()), ctypes.c_int64(int(lay[0]))), 'jodo_dgt2d_pair_fill_desc')
+            desc = plan['pair_desc'] = host.to(device)
+            plan['pair_groups'] = int(lay[1])
+        return desc
 
     def _replicate_for_data_parallel(self):
         raise RuntimeError(
@@ -199,11 +224,20 @@ class DGT_concat_2D(nn.Module):
         _, blob, woff_c, n_woff = self._weights(dev)
         out_x = torch.empty_like(xh_)
         out_e = torch.empty_like(ex_)
-        capi.check(capi.lib().jodo_dgt2d_forward(
-            ctypes.byref(self._cfg_struct), B, N, plan['n_nodes'].ctypes.data_as(ctypes.c_void_p), capi.ptr(plan['desc']), capi.ptr(blob),
-            woff_c, n_woff, capi.ptr(xh_), capi.ptr(ex_), capi.ptr(cx_), capi.ptr(cex_), capi.ptr(nl_), capi.ptr(out_x), capi.ptr(out_e),
-            capi.ptr(plan['flags']), capi.ptr(plan['ws']), int(bool(self.force_directed)), int(self.max_blocks),
-            capi.current_stream_ptr()), 'jodo_dgt2d_forward')
+        n_ptr = plan['n_nodes'].ctypes.data_as(ctypes.c_void_p)
+        tail = (capi.ptr(blob), woff_c, n_woff, capi.ptr(xh_), capi.ptr(ex_), capi.ptr(cx_), capi.ptr(cex_), capi.ptr(nl_), capi.ptr(out_x),
+                capi.ptr(out_e), capi.ptr(plan['flags']), capi.ptr(plan['ws']), int(bool(self.force_directed)), int(self.max_blocks),
+                capi.current_stream_ptr())
+        if self.pair_attention:
+            capi.check(capi.lib().jodo_dgt2d_forward_walk(ctypes.byref(self._cfg_struct), B, N, n_ptr, capi.ptr(plan['desc']),
+                                                          capi.ptr(self._pair_desc(plan, dev)), capi.WALK_PAIR, *tail), 'jodo_dgt2d_forward_walk')
+            plan['walk_slot_used'] = True
+        else:
+            if plan.get('walk_slot_used'):               # flags[2] still holds an earlier pair-walk call's record
+                plan['flags'][2:3].zero_()
+                plan['walk_slot_used'] = False
+            capi.check(capi.lib().jodo_dgt2d_forward(ctypes.byref(self._cfg_struct), B, N, n_ptr, capi.ptr(plan['desc']), *tail),
+                       'jodo_dgt2d_forward')
         self.last_flags = plan['flags']
         self._last_plan = plan
         return out_x, out_e

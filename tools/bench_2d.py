@@ -3,12 +3,19 @@ user without the HIP path would run on the same GPU: the dense torch evaluation 
 device, chunked by molecules to fit memory, under the same sampler.
 
     python tools/bench_2d.py --workload zinc|moses [--batch 2000] [--steps 20] [--warmup 3] [--baseline-steps 3] [--no-baseline]
+                             [--walk directed|pair|both] [--kernel-stats CSV] [--out FILE]
     python tools/bench_2d.py --workload zinc|moses --round [--steps 1000] [--batches 2000,128] [--forms a,b,c,cd] [--repeat 1]
                              [--parent-json FILE] [--out profiles/dgt2d_round_zinc.json]
 
 Atom counts are drawn from the training histogram (tests/golden/n_nodes_2d.json, seed 42).  Timing as bench.py does it: warm-up,
 synchronise, `steps` sampler.step calls, synchronise.  Prints one JSON line: ms/step, molecules/s at 1000 steps, the directed-edge
 count, ns per directed edge per step, and the same for the torch baseline with the ratio.
+
+--walk: the attention walk of the score network.  `directed` (default) is the run described above, unchanged; `pair` sets
+model.pair_attention (the opt-in pair-symmetric walk); `both` alternates directed, pair, directed, pair on the same batch in this one
+process and reports ms/step per form with the spread of its two runs (no torch baseline).  --kernel-stats: the `rocprofv3
+--kernel-trace --stats` kernel table of the `--walk pair` command with the same --steps and --warmup (the profiler wraps the process,
+so that is a run of its own); its k2d_* rows, divided by the sampler steps of that command, become `pair_kernel_ms_per_step`.  --out writes the record.
 
 --round: ONE complete sampling round of `--steps` steps per batch size and form, timed from the initial state to the last step
 (weights packed by a 3-step round before; plan creation and graph capture are inside the timed round):
@@ -73,6 +80,51 @@ def time_steps(sampler, model, z, edge_z, node_mask, edge_mask, warmup, steps):
             st = sampler.step(model, i, st, node_mask, edge_mask, None)
         torch.cuda.synchronize()
     return (time.perf_counter() - t0) / steps * 1e3, st
+
+
+def kernel_split(csv_path, sampler_steps):
+    """k2d_* rows of a rocprofv3 kernel-stats table -> {kernel: ms per sampler step}"""
+    import csv
+    import re
+    known = (('13k2d_attn_pair', 'k2d_attn_pair'), ('k2d_attnILb1E', 'k2d_attn<true>'), ('k2d_attnILb0E', 'k2d_attn<false>'),
+             ('k2d_gemmILi4ELi2E', 'k2d_gemm<4,2>'), ('k2d_gemmILi1ELi1E', 'k2d_gemm<1,1>'))
+    out = {}
+    with open(csv_path) as f:
+        for row in csv.DictReader(f):
+            name = row['Name']
+            if 'k2d_' not in name:
+                continue
+            key = next((nice for tag, nice in known if tag in name), None)         # mangled names (older rocprofv3)
+            if key is None:                                                        # demangled: "... k2d_gemm<4, 2>(...)"
+                m = re.search(r'(k2d_[a-z0-9_]+)(<[^>]*>)?', name)
+                key = m.group(1) + (m.group(2) or '').replace(' ', '') if m else name
+            out[key] = round(out.get(key, 0.0) + float(row['TotalDurationNs']) / sampler_steps * 1e-6, 4)
+    return dict(sorted(out.items(), key=lambda kv: -kv[1]))
+
+
+def walk_leg(args, model, sampler, z, edge_z, node_mask, edge_mask, out):
+    """--walk both: directed, pair, directed, pair on the same batch; --walk pair: the pair form alone."""
+    order = ['directed', 'pair', 'directed', 'pair'] if args.walk == 'both' else ['pair']
+    runs = {w: [] for w in order}
+    walked = {}
+    for w in order:
+        model.pair_attention = (w == 'pair')
+        ms, st = time_steps(sampler, model, z, edge_z, node_mask, edge_mask, args.warmup, args.steps)
+        runs[w].append(round(ms, 4))
+        walked[w] = int(model.last_flags[2].item())
+        out['finite'] = out.get('finite', True) and bool(torch.isfinite(st['x']).all() and torch.isfinite(st['edge_x']).all())
+    model.pair_attention = False
+    out['walk'] = args.walk
+    out['order_of_runs'] = order
+    for w, r in runs.items():
+        out[w] = dict(runs_ms_per_step=r, ms_per_step=round(sum(r) / len(r), 4), spread_ms_per_step=round(max(r) - min(r), 4),
+                      pair_walk_ran=walked[w])
+    if args.walk == 'both':
+        gain = out['directed']['ms_per_step'] - out['pair']['ms_per_step']
+        out['pair_gain_ms_per_step'] = round(gain, 4)
+        out['pair_faster_beyond_directed_spread'] = bool(gain > out['directed']['spread_ms_per_step'])
+        out['step_sampler_calls'] = len(order) * (args.warmup + args.steps)
+    return out
 
 
 def _setup(workload, batch, dev):
@@ -171,6 +223,8 @@ def main():
     ap.add_argument('--baseline-steps', type=int, default=3)
     ap.add_argument('--baseline-chunk', type=int, default=250)
     ap.add_argument('--no-baseline', action='store_true')
+    ap.add_argument('--walk', choices=('directed', 'pair', 'both'), default='directed', help='attention walk of the score network')
+    ap.add_argument('--kernel-stats', default=None, help='rocprofv3 kernel-stats CSV of a run of the same command line')
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 1000 if args.round else 20
@@ -191,6 +245,19 @@ def main():
     ns = NoiseScheduleVP(cfg.sde.schedule, continuous_beta_0=cfg.sde.continuous_beta_0, continuous_beta_1=cfg.sde.continuous_beta_1)
     sampler = AncestralSampler_2D(ns, torch.linspace(ns.T, 1e-3, 1000), True, True)
     directed = sum(n * (n - 1) for n in n_nodes)
+    if args.walk != 'directed':
+        out = dict(workload=args.workload, config=cfg_name, batch=B, max_n=N, atoms=sum(n_nodes), directed_edges=directed, steps=args.steps,
+                   warmup=args.warmup)
+        walk_leg(args, model, sampler, z, edge_z, node_mask, edge_mask, out)
+        if args.kernel_stats:
+            out['pair_kernel_ms_per_step'] = kernel_split(args.kernel_stats, args.warmup + args.steps)
+            out['kernel_stats'] = args.kernel_stats + ' (rocprofv3 --kernel-trace --stats of the --walk pair command, same steps and warm-up)'
+        print(json.dumps(out))
+        if args.out:
+            with open(args.out, 'w') as f:
+                json.dump(out, f, indent=1)
+                f.write('\n')
+        return
     ms, st = time_steps(sampler, model, z, edge_z, node_mask, edge_mask, args.warmup, args.steps)
     out = dict(workload=args.workload, config=cfg_name, batch=B, max_n=N, atoms=sum(n_nodes), directed_edges=directed, steps=args.steps,
                warmup=args.warmup, hip_ms_per_step=round(ms, 4), hip_molecules_per_s_1000_steps=round(B / (ms * 1e-3 * 1000), 2),
