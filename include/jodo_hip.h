@@ -488,6 +488,24 @@ int jodo_sampler_step_2d_rng(int B, int N, int node_feats, int edge_ch, const in
                              const float* coef_tab_dev, const int32_t* step_dev, uint64_t seed, uint32_t draw, const float* x,
                              const float* edge_x, const float* pred, const float* edge_pred, float* x_next, float* edge_next,
                              float* x_mean, float* edge_mean, void* stream);
+/* jodo_dpm_update_2d  <- one update of DPM-Solver++ for the 2-D models (DPM_Solver_2D, jodo_amd/mix_dpm_solver.py): the position-free
+ *                        counterpart of jodo_dpm_update.  Node tensor [B,N,nd] WITHOUT position channels and edge tensor [B,N,N,ch]
+ *                        both take the data-prediction update of mix_dpm_solver.py:61-265
+ *                            out = a * base - b * P - c * (c2 * (DA - DB))
+ *                        (c = 0: first order; single-step second / third order, c < 0 for third; second-order multistep with
+ *                        c2 = 1 / r0), products and sums rounded one by one in the order of the framework expression.  Nothing is
+ *                        drawn.  Coefficients {a, b, c, c2, -, -, -, noise_level}: either 8 host floats, or the 8 columns from tab_col
+ *                        of row *step_dev of a device table (row stride tab_stride floats) for captured hipGraphs; columns 4 - 6 are
+ *                        not read and the noise level of the evaluation sits in column 7, where jodo_step_begin_at fetches it.
+ *                        ONE launch: the edge output is computed once per unordered pair from cell (b, r, c) with r > c and stored
+ *                        to both orientations — symmetric bit for bit, the upper triangle of the inputs is never read; the diagonal,
+ *                        padded atoms and padded cells are written as exact zeros; every output element is written, by one thread.
+ *                        Aliasing: x_out may be any of its node inputs and edge_out any of its edge inputs (in-place update): a
+ *                        thread reads only elements it also writes.  Partial overlap is not allowed. */
+int jodo_dpm_update_2d(int B, int N, int node_feats, int edge_ch, const int32_t* n_nodes_dev, const float* coef8_host,
+                       const float* coef_tab_dev, const int32_t* step_dev, int tab_stride, int tab_col, const float* x_base,
+                       const float* edge_base, const float* P, const float* eP, const float* DA, const float* eDA, const float* DB,
+                       const float* eDB, float* x_out, float* edge_out, void* stream);
 /* jodo_decode_2d  <- post_process_2D sampling.py:100-141 + the inverse scaler utils.py:71-105 for xh [B,N,atom_types(+1)] without
  *                    positions: the scaler in the framework's fp32 operation order (x * norm, then (x + 1) / 2 when centred, then the
  *                    mask), atom type [B,N] u8 = first maximum, formal charge [B,N] i8 = rintf (0 when include_fc = 0), bond type

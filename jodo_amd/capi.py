@@ -37,13 +37,14 @@ def _bind_2d_sampling(L):
     the first sampling step."""
     i, f, p = ctypes.c_int, ctypes.c_float, ctypes.c_void_p
     try:
-        step, dec = L.jodo_sampler_step_2d_rng, L.jodo_decode_2d
+        step, dec, dpm = L.jodo_sampler_step_2d_rng, L.jodo_decode_2d, L.jodo_dpm_update_2d
     except AttributeError as e:
         raise JodoHipError("%s lacks the 2-D sampling exports (%s): rebuild it with python -c 'import __graft_entry__ as g; g.build()'"
                            % (LIB_PATH, e))
     step.argtypes = [i, i, i, i, p, f, f, f, p, p, ctypes.c_uint64, ctypes.c_uint32] + [p] * 9
     dec.argtypes = [i] * 7 + [f, f, f] + [p] * 7
-    step.restype = dec.restype = i
+    dpm.argtypes = [i, i, i, i, p, p, p, p, i, i] + [p] * 11
+    step.restype = dec.restype = dpm.restype = i
 
 
 WALK_DIRECTED, WALK_PAIR = 0, 1                 # enum jodo2d_walk

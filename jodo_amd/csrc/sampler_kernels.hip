@@ -513,6 +513,109 @@ extern "C" int jodo_step_begin_at(int B, const float* coef_tab_dev, const int32_
     return jodo_check_launch("k_step_begin_at");
 }
 
+// ---- DPM-Solver++ update of the 2-D models (jodo_dpm_update_2d): the data-prediction update of jodo_dpm_update on a node tensor
+// [B,N,nd] WITHOUT position channels and the edge tensor [B,N,N,ch]; no ancestral part, so nothing is drawn and the coefficient row
+// {a, b, c, c2, -, -, -, noise_level} has no sigma (noise_level stays in column 7: jodo_step_begin_at reads it unchanged).  ONE launch
+// over two index ranges: a thread of the first owns the four node channels 4q .. 4q+3 of one atom; a thread of the second owns one
+// entry (r >= c) of the lower triangle of one molecule — for r > c it computes every channel ONCE from cell (b, r, c) and stores the
+// value to (b, r, c) and (b, c, r), so the output is symmetric bit for bit whatever the upper triangle of the inputs holds; for r == c it
+// stores the diagonal's zeros.  Padded atoms and cells get exact zeros.  Every output element is written by exactly one thread with
+// plain stores, and a thread reads only elements it also writes: an output may be one of its own inputs (in-place update), hence no
+// __restrict__ on the tensors.
+namespace {
+__device__ __forceinline__ DpmCoef dpm2d_coef(DpmCoef k, const float* __restrict__ tab, const int* __restrict__ step, int stride, int col) {
+    if (tab) {
+        const float* r = tab + (size_t)(*step) * stride + col;
+        k.a = r[0]; k.b = r[1]; k.c = r[2]; k.c2 = r[3];
+    }
+    return k;
+}
+
+// dpm_value with contraction switched off for the function: the __f*_rn intrinsics are plain operators to this compiler (compiled
+// under its default -ffp-contract=fast, so a product may still be fused into the following sum: v_fma_f32); here every product and
+// every sum is rounded on its own, in the order of the framework expression a * base - b * P - c * (c2 * (DA - DB)), so the result equals it bit for bit
+__device__ __forceinline__ float dpm_value_2d(const DpmCoef& k, float base, float p, float da, float db) {
+#pragma clang fp contract(off)
+    const float t0 = k.a * base, t1 = k.b * p;           // plain operators: the pragma governs the operations written in this function
+    float v = t0 - t1;
+    if (k.c != 0.f) {
+        float d = da - db;
+        if (k.c2 != 1.f) d = k.c2 * d;
+        const float t2 = k.c * d;
+        v = v - t2;
+    }
+    return v;
+}
+
+__global__ __launch_bounds__(256) void k_dpm_2d(int B, int N, int nd, int ch, const int* __restrict__ n_nodes, DpmCoef k,
+                                                const float* __restrict__ tab, const int* __restrict__ step, int stride, int col,
+                                                const float* x_base, const float* e_base, const float* P, const float* eP,
+                                                const float* DA, const float* eDA, const float* DB, const float* eDB, float* x_out,
+                                                float* e_out) {
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int nq = (nd + 3) >> 2;
+    const size_t tri = (size_t)N * (N + 1) / 2;
+    const size_t n_quad = (size_t)B * N * nq, n_tri = (size_t)B * tri;
+    if (g >= n_quad + n_tri) return;
+    k = dpm2d_coef(k, tab, step, stride, col);
+    if (g < n_quad) {
+        const int q = (int)(g % nq);
+        const size_t atom = g / nq;
+        const int i = (int)(atom % N), b = (int)(atom / N);
+        const bool real = i < n_nodes[b];
+        const int k1 = min(4 * q + 4, nd);
+        for (int f = 4 * q; f < k1; ++f) {
+            const size_t o = atom * nd + f;
+            x_out[o] = real ? dpm_value_2d(k, x_base[o], P[o], DA[o], DB[o]) : 0.f;
+        }
+    } else {
+        const size_t pg = g - n_quad;
+        const int b = (int)(pg / tri);
+        const size_t t = pg % tri;
+        // row of triangle entry t: the largest r with r (r + 1) / 2 <= t; the float root is corrected to the exact integer
+        int r = (int)((sqrtf(8.f * (float)t + 1.f) - 1.f) * 0.5f);
+        r = min(max(r, 0), N - 1);
+        while ((size_t)r * (r + 1) / 2 > t) --r;
+        while ((size_t)(r + 1) * (r + 2) / 2 <= t) ++r;
+        const int c = (int)(t - (size_t)r * (r + 1) / 2);
+        const int n = n_nodes[b];
+        const size_t lo = (((size_t)b * N + r) * N + c) * ch;           // cell (b, r, c): the one that is read
+        if (r == c) {
+            for (int f = 0; f < ch; ++f) e_out[lo + f] = 0.f;
+            return;
+        }
+        const size_t up = (((size_t)b * N + c) * N + r) * ch;           // its mirror (b, c, r)
+        const bool real = r < n;                                        // c < r
+        for (int f = 0; f < ch; ++f) {
+            const float v = real ? dpm_value_2d(k, e_base[lo + f], eP[lo + f], eDA[lo + f], eDB[lo + f]) : 0.f;
+            e_out[lo + f] = v;
+            e_out[up + f] = v;
+        }
+    }
+}
+}  // namespace
+
+extern "C" int jodo_dpm_update_2d(int B, int N, int node_feats, int edge_ch, const int32_t* n_nodes_dev, const float* coef8_host,
+                                  const float* coef_tab_dev, const int32_t* step_dev, int tab_stride, int tab_col, const float* x_base,
+                                  const float* edge_base, const float* P, const float* eP, const float* DA, const float* eDA,
+                                  const float* DB, const float* eDB, float* x_out, float* edge_out, void* stream) {
+    if (B <= 0 || N <= 0 || node_feats < 1 || edge_ch < 1) return jodo_set_error(JODO_ERR_ARG, "dpm_update_2d: bad shape");
+    if (!n_nodes_dev || !x_base || !edge_base || !P || !eP || !DA || !eDA || !DB || !eDB || !x_out || !edge_out)
+        return jodo_set_error(JODO_ERR_ARG, "dpm_update_2d: null argument");
+    if ((coef8_host == nullptr) == (coef_tab_dev == nullptr) || (coef_tab_dev && !step_dev))
+        return jodo_set_error(JODO_ERR_ARG, "dpm_update_2d: pass either host coefficients or a device table + step counter");
+    if (coef_tab_dev && (tab_stride < 8 || tab_col < 0 || tab_col + 8 > tab_stride))
+        return jodo_set_error(JODO_ERR_ARG, "dpm_update_2d: the 8 columns from tab_col do not fit a table row of tab_stride floats");
+    DpmCoef k{0, 0, 0, 0, 0, 0, 1, 0};
+    if (coef8_host) { k.a = coef8_host[0]; k.b = coef8_host[1]; k.c = coef8_host[2]; k.c2 = coef8_host[3]; }
+    const size_t tot = (size_t)B * N * ((node_feats + 3) / 4) + (size_t)B * ((size_t)N * (N + 1) / 2);
+    if ((tot + 255) / 256 > 0x7fffffffull) return jodo_set_error(JODO_ERR_UNSUPPORTED, "dpm_update_2d: batch too large for one launch");
+    hipLaunchKernelGGL(k_dpm_2d, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, B, N, node_feats, edge_ch,
+                       n_nodes_dev, k, coef_tab_dev, step_dev, tab_stride, tab_col, x_base, edge_base, P, eP, DA, eDA, DB, eDB, x_out,
+                       edge_out);
+    return jodo_check_launch("k_dpm_2d");
+}
+
 extern "C" int jodo_decode(int B, int N, int atom_types, int include_fc, int edge_ch, int compress_edge, int centered,
                            float pos_norm, float atom_norm, float fc_norm, float edge_norm, const int32_t* n_nodes_dev,
                            const float* xh, const float* edge_x, float* pos_out, uint8_t* atom_type_out, int8_t* fc_out,

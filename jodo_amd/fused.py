@@ -1,5 +1,5 @@
-"""Python plumbing for the caller-side HIP kernels (csrc/sampler_kernels.hip): the fused ancestral update
-and the fused decode, for the 3-D + edge models and (the *_2d functions) the 2-D ones.  Device tensors in, device tensors out; raises (no CPU fallback) on CPU tensors —
+"""Python plumbing for the caller-side HIP kernels (csrc/sampler_kernels.hip): the fused ancestral update, the fused DPM-Solver++
+update and the fused decode, for the 3-D + edge models and (the *_2d functions) the 2-D ones.  Device tensors in, device tensors out; raises (no CPU fallback) on CPU tensors —
 the callers in sampling.py pick the framework path themselves when they run on the CPU (host-logic tests).
 """
 import ctypes
@@ -277,5 +277,51 @@ def dpm_update(solver, coef, x_pos, x_base, edge_base, P, DA, DB, PP, n_nodes_de
         capi.check(capi.lib().jodo_dpm_update(
             B, N, F, ch, capi.ptr(n_nodes_dev), c8, None, None, 0, 0, *[capi.ptr(v) for v in t],
             capi.ptr(bufs.eps), capi.ptr(xo), capi.ptr(eo), capi.current_stream_ptr()), 'jodo_dpm_update')
+    del t
+    return xo, eo
+
+
+class _DpmBuffers2D:
+    """_DpmBuffers for the 2-D solver: the same ring of output buffers, no position-noise buffer (nothing is drawn)."""
+
+    def __init__(self, x, edge_x, depth=4):
+        new = lambda t: torch.empty(t.shape, dtype=torch.float32, device=t.device)
+        self.x = [new(x) for _ in range(depth)]
+        self.e = [new(edge_x) for _ in range(depth)]
+        self.cur = 0
+
+
+def dpm_update_2d(solver, coef, x_base, edge_base, P, DA, DB, n_nodes_dev):
+    """jodo_dpm_update_2d (include/jodo_hip.h) in its host-scalar form: coef = [a, b, c, c2, 0, 0, 0, 0]; P / DA / DB are (node prediction,
+    edge prediction) pairs; node tensors [B,N,nd] without position channels, edge tensors [B,N,N,ch]; n_nodes_dev = int32 [B] atom counts
+    of THIS round.  The outputs come from a ring on `solver` (never a tensor the call reads) and are symmetric, with zero padding and
+    diagonal, whatever the inputs hold there.  Returns (x_out, edge_out)."""
+    if x_base.dim() != 3 or edge_base.dim() != 4:
+        raise ValueError("dpm_update_2d: node tensors are [B,N,nd], edge tensors [B,N,N,ch]")
+    B, N, nd = x_base.shape
+    ch = edge_base.shape[-1]
+    if edge_base.shape != (B, N, N, ch) or any(t[0].shape != x_base.shape or t[1].shape != edge_base.shape for t in (P, DA, DB)):
+        raise ValueError("dpm_update_2d: shape mismatch")
+    if len(coef) != 8:
+        raise ValueError("dpm_update_2d: coef holds 8 floats [a, b, c, c2, 0, 0, 0, noise_level]")
+    if n_nodes_dev.shape[0] != B or n_nodes_dev.device != x_base.device or n_nodes_dev.dtype != torch.int32:
+        raise ValueError("dpm_update_2d: n_nodes_dev does not belong to this batch")
+    bufs = getattr(solver, '_dpm_bufs', None)
+    if bufs is None or bufs.x[0].shape != x_base.shape or bufs.e[0].shape != edge_base.shape or bufs.x[0].device != x_base.device:
+        bufs = solver._dpm_bufs = _DpmBuffers2D(x_base, edge_base)
+    live = {t.data_ptr() for t in (x_base, edge_base, P[0], P[1], DA[0], DA[1], DB[0], DB[1])}
+    for _ in range(len(bufs.x)):
+        bufs.cur = (bufs.cur + 1) % len(bufs.x)
+        if bufs.x[bufs.cur].data_ptr() not in live and bufs.e[bufs.cur].data_ptr() not in live:
+            break
+    else:
+        raise RuntimeError("dpm_update_2d: no free output buffer")
+    xo, eo = bufs.x[bufs.cur], bufs.e[bufs.cur]
+    c8 = (ctypes.c_float * 8)(*coef)
+    # contiguous fp32 views stay bound to names until the launch is enqueued (see dpm_update)
+    t = [_f32c(v, n) for v, n in ((x_base, 'x_base'), (edge_base, 'edge_base'), (P[0], 'P'), (P[1], 'eP'), (DA[0], 'DA'), (DA[1], 'eDA'),
+                                  (DB[0], 'DB'), (DB[1], 'eDB'))]
+    capi.check(capi.lib().jodo_dpm_update_2d(B, N, nd, ch, capi.ptr(n_nodes_dev), c8, None, None, 0, 0, *[capi.ptr(v) for v in t],
+                                             capi.ptr(xo), capi.ptr(eo), capi.current_stream_ptr()), 'jodo_dpm_update_2d')
     del t
     return xo, eo

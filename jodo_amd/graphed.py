@@ -1,5 +1,5 @@
 """HIP-graph replay of the ancestral sampling loop ("enables HIP-graph capture of a whole
-step"); GraphedAncestralRound2D below is the same for the 2-D models.  One denoising step — noise level from a device table, score network (~80 launches through the C
+step"); GraphedAncestralRound2D below is the same for the 2-D models, GraphedDPMRound / GraphedDPMRound2D replay the DPM-solvers.  One denoising step — noise level from a device table, score network (~80 launches through the C
 ABI), three normal draws, fused update, state hand-over — is captured ONCE with torch.cuda.graph and
 replayed for every remaining step, which removes the per-step Python / launch overhead (≈ 0.4 ms per step:
 2 % at QM9 B = 2500, 7 % at B = 313).
@@ -368,4 +368,144 @@ class GraphedDPMRound:
             x, edge_x = self.x.clone(), self.e.clone()
         from .models.utils import assert_mean_zero_with_mask
         assert_mean_zero_with_mask(x[:, :, :3], self.node_mask)
+        return x, edge_x
+
+
+class GraphedDPMRound2D:
+    """HIP-graph replay of DPM_Solver_2D (sampling.method 'dpm_2d'; `steps` = NFE).  Two variants:
+
+      single-step, order 2   ONE outer step — two score-network evaluations, two jodo_dpm_update_2d, jodo_step_end — is captured, as in
+                             GraphedDPMRound; table [K][16], two coefficient rows per outer step.  The second update writes the state
+                             in place (the kernel allows its output to be its `base`).
+      multistep, order 2     ONE step — the evaluation at t_j, the update to t_{j+1} from that prediction and the previous one,
+                             jodo_step_end — is captured; table [steps][8].  The previous prediction lives in the static self-conditioning
+                             buffers (cx, cex): the model reads them as cond_x / cond_edge_x, the update reads them as DB, and the new
+                             prediction is copied into them inside the captured step.  Step 0 is the solver's own order-1 warm-up.
+
+    Every per-step scalar sits in the device table ({a, b, c, c2, 0, 0, 0, noise level} per evaluation, jodo_step_begin_at fetches column
+    7) indexed by a device step counter.  The first step (no self-conditioning input yet: another kernel path) runs eagerly through the
+    solver's own methods, one warm-up step runs on a side stream, the rest is replay.  Nothing is drawn, so there is no noise option, and
+    a replayed round ends in the very state of the eager DPM_Solver_2D.sampling: same kernels, same coefficients.  Other variants raise
+    NotImplementedError, as GraphedDPMRound does."""
+
+    @staticmethod
+    def supports(solver):
+        return (solver.method, solver.order) in (('singlestep_fixed', 2), ('multistep', 2))
+
+    def __init__(self, solver, model, node_mask, edge_mask, context=None):
+        if not self.supports(solver):
+            raise NotImplementedError("graph replay of the 2-D DPM-solver covers single-step order 2 and multistep order 2")
+        self.solver, self.model = solver, model
+        self.node_mask, self.edge_mask, self.context = node_mask, edge_mask, context
+        self.single = solver.method == 'singlestep_fixed'
+        ns = solver.noise_schedule
+        row = lambda a, b, c, c2, t: torch.tensor([float(a), float(b), float(c), float(c2), 0.0, 0.0, 0.0, float(ns.get_noiseLevel(t))])
+        if self.single:
+            K = solver.steps // 2
+            outer = solver.get_time_steps('time_uniform', ns.T, 1. / ns.total_N, K, 'cpu')
+            tab = torch.zeros(K, 16, dtype=torch.float32)
+            for k in range(K):
+                ts, te = outer[k], outer[k + 1]
+                c = solver.second_order_coefficients(ts, te, self._r1(ts, te))
+                tab[k, 0:8] = row(c['a1'], c['b1'], 0.0, 1.0, ts)
+                tab[k, 8:16] = row(c['a2'], c['b2'], c['c2'], 1.0, c['s1'])
+        else:
+            K = solver.steps
+            ts = solver.get_time_steps('time_uniform', ns.T, 1. / ns.total_N, K, 'cpu')
+            tab = torch.zeros(K, 8, dtype=torch.float32)
+            for j in range(1, K):                         # row 0 stays unused: step 0 is the eager order-1 warm-up
+                c = solver.multistep_second_coefficients(ts[j - 1], ts[j], ts[j + 1])
+                tab[j] = row(c['a'], c['b'], c['c'], c['c2'], ts[j])
+            self.ts = ts
+        self.K, self.tab_host, self.graph = K, tab, None
+
+    def _r1(self, ts, te):
+        sv = self.solver
+        lam = sv.noise_schedule.marginal_lambda(sv.get_time_steps('time_uniform', ts.item(), te.item(), 2, 'cpu'))
+        return (lam[1] - lam[0]) / (lam[-1] - lam[0])
+
+    def _eval(self, col, x, e):
+        L = capi.lib()
+        capi.check(L.jodo_step_begin_at(self.x.shape[0], capi.ptr(self.tab), capi.ptr(self.step), self.tab.shape[1], col, capi.ptr(self.nl),
+                                        capi.current_stream_ptr()), 'jodo_step_begin_at')
+        return self.model(self.nl, x, self.node_mask, self.edge_mask, edge_x=e, noise_level=self.nl, cond_x=self.cx, cond_edge_x=self.cex,
+                          context=self.context)
+
+    def _up(self, col, P, DA, DB, xo, eo):
+        B, N, nd = self.x.shape
+        tens = [capi.ptr(t) for t in (self.x, self.e, P[0], P[1], DA[0], DA[1], DB[0], DB[1], xo, eo)]
+        capi.check(capi.lib().jodo_dpm_update_2d(B, N, nd, self.e.shape[-1], capi.ptr(self.n_nodes), None, capi.ptr(self.tab),
+                                                 capi.ptr(self.step), self.tab.shape[1], col, *tens, capi.current_stream_ptr()),
+                   'jodo_dpm_update_2d')
+
+    def _step(self):
+        """One captured unit on the static buffers; identical code runs eagerly (warm-up) and under capture."""
+        if self.single:
+            p0 = self._eval(0, self.x, self.e)
+            self.cx.copy_(p0[0]); self.cex.copy_(p0[1])        # self-conditioning input of the next evaluation
+            c0 = (self.cx, self.cex)
+            self._up(0, c0, c0, c0, self.x1, self.e1)
+            p1 = self._eval(8, self.x1, self.e1)
+            self._up(8, c0, p1, c0, self.x, self.e)            # in place: the state is the update's base
+            self.cx.copy_(p1[0]); self.cex.copy_(p1[1])
+        else:
+            p = self._eval(0, self.x, self.e)
+            prev = (self.cx, self.cex)                         # the previous prediction: cond input above, DB here
+            self._up(0, p, p, prev, self.x, self.e)            # in place
+            self.cx.copy_(p[0]); self.cex.copy_(p[1])          # handed over to the next step
+        capi.check(capi.lib().jodo_step_end(capi.ptr(self.step), capi.current_stream_ptr()), 'jodo_step_end')
+
+    def run(self, x, edge_x):
+        """Returns (x, edge_x) at t_end like DPM_Solver_2D.sampling."""
+        from .models.utils import model_hook
+        try:
+            return self._run(x, edge_x)
+        finally:
+            unpin = model_hook(self.model, 'unpin_paths')
+            if unpin is not None:
+                unpin()
+
+    @torch.no_grad()
+    def _run(self, x, edge_x):
+        from .models.utils import model_hook
+        sv, dev = self.solver, x.device
+        ns = sv.noise_schedule
+        sv.cond_x = sv.cond_edge_x = None
+        sv._n_nodes_dev = fused.n_nodes_from_mask(self.node_mask)      # this round's atom counts (the solver serves many rounds)
+        sv._pinned = False
+        model_fn = sv.get_model_fn(self.model)
+        a = (model_fn, x, self.node_mask, self.edge_mask, edge_x, self.context)
+        if self.single:                                    # outer step 0: eager, cond = None
+            outer = sv.get_time_steps('time_uniform', ns.T, 1. / ns.total_N, self.K, 'cpu')
+            x, edge_x = sv.singlestep_dpm_solver_update(*a, outer[0], outer[1], self.K == 1, order=2, r1=self._r1(outer[0], outer[1]))
+        else:                                              # evaluation at t_0 and the order-1 update to t_1
+            m0 = sv._predict(*a, self.ts[0])
+            x, edge_x = sv.multistep_dpm_solver_update(*a, [m0], [self.ts[0]], self.ts[1], last_step=False, order=1)
+        if self.K > 1:
+            new = lambda t: torch.empty(t.shape, dtype=torch.float32, device=dev)
+            self.x, self.e = x.contiguous().clone(), edge_x.contiguous().clone()
+            self.cx, self.cex = sv.cond_x.contiguous().clone(), sv.cond_edge_x.contiguous().clone()
+            if self.single:
+                self.x1, self.e1 = new(self.x), new(self.e)
+            self.nl = torch.empty(self.x.shape[0], device=dev)
+            self.tab = self.tab_host.to(dev)
+            self.step = torch.ones(1, dtype=torch.int32, device=dev)          # next step to run
+            self.n_nodes = sv._n_nodes_dev
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                self._step()                                     # step 1: eager warm-up on the static buffers
+            torch.cuda.current_stream().wait_stream(side)
+            pin = model_hook(self.model, 'pin_paths')
+            if pin is not None:
+                pin()
+            if self.K > 2:
+                self.graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.graph):
+                    self._step()
+                for _ in range(self.K - 2):                # capture records, it does not run: K - 2 steps are left
+                    self.graph.replay()
+            x, edge_x = self.x.clone(), self.e.clone()
+        else:
+            x, edge_x = x.clone(), edge_x.clone()
         return x, edge_x

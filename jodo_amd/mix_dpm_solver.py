@@ -6,6 +6,10 @@ Behaviour of /root/reference/mix_dpm_solver.py: `DPM_Solver_hybrid.sampling` (:3
 update (:44-59), first/second/third-order single-step updates (:61-227), multistep second order
 (:230-265), `get_model_fn` (:296-302).  The score-network call signature is unchanged.
 `steps` counts model evaluations (NFE): K = steps // order outer steps of `order` evaluations each.
+
+`DPM_Solver_2D` (below) is the same solver for the 2-D models, whose node tensor has no position channels: every channel and the edge
+tensor take the data-prediction update and nothing is drawn.  The reference has no such class (its 'fast' on a 2-D state would treat
+the first three atom channels as coordinates); its oracle is the reference's own hybrid solver run with three zero position columns.
 """
 import torch
 
@@ -184,9 +188,14 @@ class DPM_Solver_hybrid:
     # -- order 2, multistep --------------------------------------------------------------------
     def multistep_dpm_solver_second_update(self, model_fn, x, node_mask, edge_mask, edge_x, context,
                                            model_prev_list, t_prev_list, t, last_step):
-        ns = self.noise_schedule
         p_m1, p_m0 = model_prev_list[-2], model_prev_list[-1]
-        t_m1, t_m0 = t_prev_list[-2], t_prev_list[-1]
+        k = self.multistep_second_coefficients(t_prev_list[-2], t_prev_list[-1], t)
+        return self._update(x, x, edge_x, p_m0, p_m0, p_m1, p_m0, node_mask, t_prev_list[-1], t, last_step,
+                            k['a'], k['b'], k['c'], k['c2'])
+
+    def multistep_second_coefficients(self, t_m1, t_m0, t):
+        """(a, b, c, c2) of the second-order multistep update from t_m0 to t with the previous evaluation at t_m1 (:230-265)."""
+        ns = self.noise_schedule
         lam_m1, lam_m0, lam_t = ns.marginal_lambda(t_m1), ns.marginal_lambda(t_m0), ns.marginal_lambda(t)
         sigma_m0, sigma_t = ns.marginal_std(t_m0), ns.marginal_std(t)
         alpha_t = torch.exp(ns.marginal_log_mean_coeff(t))
@@ -194,8 +203,7 @@ class DPM_Solver_hybrid:
         h = lam_t - lam_m0
         r0 = h_0 / h
         phi_1 = torch.expm1(-h)
-        return self._update(x, x, edge_x, p_m0, p_m0, p_m1, p_m0, node_mask, t_prev_list[-1], t, last_step,
-                            sigma_t / sigma_m0, alpha_t * phi_1, 0.5 * (alpha_t * phi_1), 1. / r0)
+        return dict(a=sigma_t / sigma_m0, b=alpha_t * phi_1, c=0.5 * (alpha_t * phi_1), c2=1. / r0)
 
     def singlestep_dpm_solver_update(self, model_fn, x, node_mask, edge_mask, edge_x, context, t_start, t_end,
                                      last_step, order, r1=None, r2=None):
@@ -299,7 +307,74 @@ class DPM_Solver_hybrid:
         else:
             raise ValueError("Get wrong method {}".format(self.method))
 
-        assert_mean_zero_with_mask(x[:, :, :3], node_mask)
+        self._check_end_state(x, node_mask)
         if self.fused and x.is_cuda:
             x, edge_x = x.clone(), edge_x.clone()        # the fused updates write into buffers the solver reuses
         return x, edge_x
+
+    def _check_end_state(self, x, node_mask):
+        assert_mean_zero_with_mask(x[:, :, :3], node_mask)
+
+
+class DPM_Solver_2D(DPM_Solver_hybrid):
+    """DPM-Solver++ for the 2-D models (sampling.method 'dpm_2d'): the hybrid solver without its position part.  The node tensor
+    [B,N,nd] has no position channels; it and the edge tensor [B,N,N,ch] both take the deterministic data-prediction update
+    a * base - b * P - c * (c2 * (DA - DB)) — what DPM_Solver_hybrid does to its non-position channels and edges (mix_dpm_solver.py:61-265).
+    Nothing is drawn after the initial state.  Time grid, coefficient arithmetic, the method / order dispatch and the self-conditioning
+    carried between evaluations (get_model_fn, pin_paths / unpin_paths hooks included) are the base class's own code; this class
+    replaces the update of the state and the end-of-round check only.
+
+    `steps` = NFE.  The 2-D configs carry neither `sampling.dpm_solver_method` nor `sampling.dpm_solver_order` (like the reference's):
+    they default to 'singlestep_fixed' and 2.  Methods: 'singlestep_fixed' at orders 1 - 3, 'multistep' at order 2 (order-1 warm-up).
+    fused=True: on GPU tensors an update is one kernel (jodo_dpm_update_2d); CPU tensors take the op-by-op path (host tests with a
+    CPU model).  `sampling` returns clones, as the 3-D class does."""
+
+    def __init__(self, noise_schedule, config, fused=True):
+        self.noise_schedule = noise_schedule
+        self.device_noise = None          # nothing is drawn: kept for the callers that reset it on every solver
+        self.noise_fn = None
+        self._n_nodes_dev = None
+        self._pinned = False
+        self._noise_calls = 0
+        self.cond_x = None
+        self.cond_edge_x = None
+        self.order = getattr(config.sampling, 'dpm_solver_order', 2)
+        self.steps = config.sampling.steps
+        self.method = getattr(config.sampling, 'dpm_solver_method', 'singlestep_fixed')
+        self.fused = fused
+        assert config.model.pred_data, "Not support in current version."
+        assert config.model.self_cond, "Not support in current version."
+        if self.method == 'singlestep_fixed':
+            if self.order not in (1, 2, 3) or self.steps < self.order:
+                raise ValueError("DPM_Solver_2D: singlestep_fixed takes dpm_solver_order 1, 2 or 3 and steps >= order")
+        elif self.method == 'multistep':
+            if self.order != 2 or self.steps < 2:
+                raise ValueError("DPM_Solver_2D: multistep is built at dpm_solver_order 2 (steps >= 2)")
+        else:
+            raise ValueError("Get wrong method {}".format(self.method))
+
+    def noise_draws_per_round(self):
+        return 0
+
+    def _update(self, x_pos, x_base, edge_base, P, DA, DB, PP, node_mask, t_from, t_to, last_step, a, b, c=None, c2=None):
+        """a * base - b * P - c * (c2 * (DA - DB)) on the node tensor and the edge tensor; x_pos / PP / the times / last_step belong to
+        the base class's position step and are not used.  One kernel on GPU tensors, the framework expression otherwise; the op order
+        of the products is the same in both paths."""
+        if self.fused and x_base.is_cuda:
+            from . import fused
+            coef = [float(a), float(b), 0.0 if c is None else float(c), 1.0 if c2 is None else float(c2), 0.0, 0.0, 0.0, 0.0]
+            if self._n_nodes_dev is None or self._n_nodes_dev.shape[0] != x_base.shape[0]:
+                self._n_nodes_dev = fused.n_nodes_from_mask(node_mask)      # direct callers of the update methods
+            return fused.dpm_update_2d(self, coef, x_base, edge_base, P, DA, DB, self._n_nodes_dev)
+        x = a * x_base - b * P[0]
+        edge = a * edge_base - b * P[1]
+        if c is not None:
+            d_x, d_edge = DA[0] - DB[0], DA[1] - DB[1]
+            if c2 is not None:
+                d_x, d_edge = c2 * d_x, c2 * d_edge
+            x = x - c * d_x
+            edge = edge - c * d_edge
+        return x, edge
+
+    def _check_end_state(self, x, node_mask):
+        pass                                  # no position channels: nothing to centre

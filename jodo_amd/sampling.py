@@ -18,9 +18,13 @@ The 2-D experiments (`config.only_2D`, model DGT_concat_2D): `AncestralSampler_2
 `mol_process_2D` (:35-50) and the 2-D sampling function of `get_sampling_fn` (:234-276), with the reference's RNG use.  The
 additions above exist for the 2-D path on a GPU device: `shard=` (both modes, both assignments), `device_noise=True` (both draws of a
 step inside jodo_sampler_step_2d_rng), `hip_graph=True` (GraphedAncestralRound2D; needs device noise) and the device decode
-(jodo_decode_2d); on a CPU `config.device` they raise NotImplementedError like the model itself (no CPU fallback).  `method='fast'`
-raises: the reference has no DPM-solver for 2-D graphs.  `cpu_noise=True` (2-D only) makes every draw on the CPU generator in the
-reference's shapes and order.
+(jodo_decode_2d); on a CPU `config.device` they raise NotImplementedError like the model itself (no CPU fallback).  `cpu_noise=True`
+(2-D only) makes every draw on the CPU generator in the reference's shapes and order.
+
+`sampling.method = 'dpm_2d'` (2-D only, not in the reference): deterministic DPM-Solver++ for 2-D graphs (mix_dpm_solver.DPM_Solver_2D;
+`sampling.steps` = NFE, `sampling.dpm_solver_method` / `dpm_solver_order` default to 'singlestep_fixed' / 2) in place of the ancestral
+sampler, everything around it unchanged; with `hip_graph=True` GraphedDPMRound2D.  `method='fast'` keeps naming the hybrid solver with
+its position part and raises on a 2-D config: the reference's 'fast' would treat the first three atom channels as coordinates.
 """
 import random
 
@@ -28,7 +32,7 @@ import numpy as np
 import torch
 from torch.nn import functional as F
 
-from .mix_dpm_solver import DPM_Solver_hybrid
+from .mix_dpm_solver import DPM_Solver_2D, DPM_Solver_hybrid
 from .models.utils import (assert_mean_zero_with_mask, model_hook, sample_combined_position_feature_noise,
                            sample_gaussian_with_mask, sample_symmetric_edge_feature_noise)
 from .utils import expand_dims, get_self_cond_fn
@@ -216,7 +220,10 @@ def get_sampling_fn(config, noise_scheduler, nodes_dist, batch_size, n_samples, 
     Returns this rank's molecules; `sampling_fn.last_indices` holds their indices in the global order (rounds *
     batch_size molecules, as the unsharded run generates them) and `sampling_fn.last_decoded` the decoded, padded tensors of
     every round as they left the decode (on the GPU: the outputs of jodo_decode, still on the device) — what the caller's
-    gather sends (jodo_amd/dist.gather_sampled)."""
+    gather sends (jodo_amd/dist.gather_sampled).
+
+    config.sampling.method: 'ancestral' (both kinds of model), 'fast' (the hybrid DPM-Solver++ of the 3-D + edge models; raises on a
+    2-D config) or 'dpm_2d' (2-D configs only: DPM-Solver++ without a position part, see _get_sampling_fn_2d; sampling.steps = NFE)."""
     device = config.device
     steps = config.sampling.steps
     atom_types = config.data.atom_types
@@ -393,11 +400,20 @@ def _get_sampling_fn_2d(config, noise_scheduler, nodes_dist, batch_size, n_sampl
     is ignored on CPU tensors, where an explicit device_noise=True or hip_graph=True is refused — as is every option through the
     public entry on a CPU config.device; this builder takes shard= with torch-drawn noise on the CPU (host tests with a CPU model).
     The initial z / edge_z stay torch draws.  `sampling_fn.last_indices` / `last_decoded` as in the 3-D path; a round's decoded tuple
-    is (None, atom_type [B,N] u8, charge [B,N] i8, bond [B,N,N] u8, n_nodes [B] i32)."""
+    is (None, atom_type [B,N] u8, charge [B,N] i8, bond [B,N,N] u8, n_nodes [B] i32).
+
+    config.sampling.method == 'dpm_2d': DPM_Solver_2D (deterministic DPM-Solver++, sampling.steps = NFE; sampling.dpm_solver_method /
+    dpm_solver_order default to 'singlestep_fixed' / 2) takes the ancestral sampler's place; atom counts, the initial z / edge_z draws
+    (cpu_noise included), sharding, seeding and the decode are the code above.  The solver draws nothing after the initial state: a
+    'parity' rank with an empty share of a round consumes the initial draw only, device_noise has no effect (accepted and ignored; True on
+    a CPU device still raises) and hip_graph=True (GraphedDPMRound2D: single-step order 2 and multistep order 2) goes with any noise
+    option."""
     if config.sampling.method == 'fast':
-        raise NotImplementedError("sampling.method='fast' (DPM-solver) is not implemented for the 2-D sampling path")
-    if config.sampling.method != 'ancestral':
+        raise NotImplementedError("sampling.method='fast' (the hybrid DPM-solver with a position part) is not implemented for the 2-D "
+                                  "sampling path; sampling.method='dpm_2d' is the DPM-solver for 2-D graphs")
+    if config.sampling.method not in ('ancestral', 'dpm_2d'):
         raise ValueError('Invalid sampling method!')
+    dpm = config.sampling.method == 'dpm_2d'
     device = config.device
     on_gpu = torch.device(device).type == 'cuda'
     for name, val in (('hip_graph', bool(hip_graph)), ('device_noise', bool(device_noise))):
@@ -409,13 +425,15 @@ def _get_sampling_fn_2d(config, noise_scheduler, nodes_dist, batch_size, n_sampl
     if shard is not None and not (0 <= shard[0] < shard[1]):
         raise ValueError("shard=(rank, world) with 0 <= rank < world")
     replayed = cpu_noise or (shard is not None and shard_mode == 'parity')
-    if hip_graph and (replayed or (device_noise is not None and not device_noise)):
+    if hip_graph and not dpm and (replayed or (device_noise is not None and not device_noise)):
         raise ValueError("hip_graph=True needs device noise: the captured step draws inside the update kernel (not with "
                          "device_noise=False, cpu_noise=True or shard_mode='parity')")
     if cpu_noise and (shard is not None or device_noise):
         raise ValueError("cpu_noise replays the unsharded run's CPU draws; a sharded run does that with shard_mode='parity'")
     if device_noise is None:
         device_noise = bool(hip_graph) or (shard is not None and shard_mode == 'perf')
+    if dpm:
+        device_noise = False                                   # nothing is drawn after the initial state
     atom_types = config.data.atom_types
     include_fc = config.model.include_fc_charge
     node_nf = atom_types + int(include_fc)
@@ -425,8 +443,15 @@ def _get_sampling_fn_2d(config, noise_scheduler, nodes_dist, batch_size, n_sampl
     rounds = int(np.ceil(n_samples / batch_size))
     round_counter = [0]
     decoded_rounds = []          # per round of a sharded run: (None, atom_type [B,N] u8, charge [B,N] i8, bond [B,N,N] u8, n_nodes [B] i32)
-    time_steps = torch.linspace(noise_scheduler.T, eps, steps)      # host scalars, as in the 3-D path
-    sampler = AncestralSampler_2D(noise_scheduler, time_steps, config.model.pred_data, config.model.self_cond)
+    if dpm:
+        sampler = DPM_Solver_2D(noise_scheduler, config)
+        if hip_graph:
+            from .graphed import GraphedDPMRound2D
+            if not GraphedDPMRound2D.supports(sampler):
+                raise NotImplementedError("hip_graph=True with sampling.method='dpm_2d' covers single-step order 2 and multistep order 2")
+    else:
+        time_steps = torch.linspace(noise_scheduler.T, eps, steps)      # host scalars, as in the 3-D path
+        sampler = AncestralSampler_2D(noise_scheduler, time_steps, config.model.pred_data, config.model.self_cond)
 
     def one_round(model, n_nodes, noise=None):
         """n_nodes molecules (this process's share of a round) -> list of decoded molecule tuples."""
@@ -453,7 +478,10 @@ def _get_sampling_fn_2d(config, noise_scheduler, nodes_dist, batch_size, n_sampl
                                                               shard[0] if shard is not None else 0, round_counter[0])
         round_counter[0] += 1
         try:
-            if hip_graph:
+            if hip_graph and dpm:
+                from .graphed import GraphedDPMRound2D
+                x_node, x_edge = GraphedDPMRound2D(sampler, model, node_mask, edge_mask).run(z, edge_z)
+            elif hip_graph:
                 # one captured HIP graph per round, replayed for every step (jodo_amd/graphed.py)
                 from .graphed import GraphedAncestralRound2D
                 x_node, x_edge = GraphedAncestralRound2D(sampler, model, node_mask, edge_mask).run(z, edge_z)
@@ -523,7 +551,7 @@ def _get_sampling_fn_2d(config, noise_scheduler, nodes_dist, batch_size, n_sampl
                     lo, hi = shard_range(len(n_nodes), rank, world)
                     noise = _ParityNoise2D(n_nodes.tolist(), lo, hi, node_nf, edge_nf, device)
                     if hi == lo:                               # nothing of this round is ours: stay in step with the stream
-                        for _ in range(steps + 1):
+                        for _ in range(1 if dpm else steps + 1):   # (the DPM-solver draws the initial state only)
                             noise.node(); noise.edge()
                         continue
                     mols += one_round(model, n_nodes[lo:hi], noise)

@@ -6,6 +6,8 @@ device, chunked by molecules to fit memory, under the same sampler.
                              [--walk directed|pair|both] [--kernel-stats CSV] [--out FILE]
     python tools/bench_2d.py --workload zinc|moses --round [--steps 1000] [--batches 2000,128] [--forms a,b,c,cd] [--repeat 1]
                              [--parent-json FILE] [--out profiles/dgt2d_round_zinc.json]
+    python tools/bench_2d.py --workload zinc|moses --round --nfe 50 [--dpm-method singlestep_fixed|multistep] [--batches 2000,128]
+                             [--forms d,dg] [--repeat 1] [--out profiles/dgt2d_dpm2d_round_zinc_nfe50.json]
 
 Atom counts are drawn from the training histogram (tests/golden/n_nodes_2d.json, seed 42).  Timing as bench.py does it: warm-up,
 synchronise, `steps` sampler.step calls, synchronise.  Prints one JSON line: ms/step, molecules/s at 1000 steps, the directed-edge
@@ -24,6 +26,11 @@ so that is a run of its own); its k2d_* rows, divided by the sampler steps of th
     b   eager, both draws of a step inside jodo_sampler_step_2d_rng
     c   one captured step replayed (GraphedAncestralRound2D), in-kernel draws
     cd  c plus the device decode (jodo_decode_2d) and the per-molecule host tuples
+    d   DPM-Solver++ for 2-D graphs (sampling.method 'dpm_2d', DPM_Solver_2D, order 2), eager, --nfe evaluations
+    dg  d with one captured step replayed (GraphedDPMRound2D)
+--nfe selects the DPM leg: the forms default to d,dg, the record counts the network evaluations of a round and goes to a file of its own
+(default profiles/dgt2d_dpm2d_round_<workload>_nfe<NFE>.json).  A round of form d / dg costs NFE evaluations where a round of a - cd costs
+--steps of them; the tool measures, it predicts nothing, and it says nothing about sample quality at a given NFE.
 Form a uses nothing newer than the sampler itself, so this file copied into a checkout of an older commit measures that commit
 (`--forms a --repeat 2`); `--parent-json` embeds such a record, with the spread of its runs, next to this run's numbers.
 """
@@ -144,6 +151,8 @@ def _one_round(form, cfg, model, ns, steps, n_nodes, node_mask, edge_mask, z, ed
     """-> (seconds of the loop, seconds of the decode or None, finite)"""
     from jodo_amd import sampling as S
     from jodo_amd.utils import get_data_inverse_scaler
+    if form in ('d', 'dg'):
+        return _one_dpm_round(form, cfg, model, ns, steps, node_mask, edge_mask, z, edge_z)
     sampler = AncestralSampler_2D(ns, torch.linspace(ns.T, 1e-3, steps), True, True)
     if form != 'a':
         from jodo_amd import fused
@@ -172,24 +181,54 @@ def _one_round(form, cfg, model, ns, steps, n_nodes, node_mask, edge_mask, z, ed
     return t1 - t0, dec, bool(torch.isfinite(x).all() and torch.isfinite(e).all())
 
 
+def _one_dpm_round(form, cfg, model, ns, nfe, node_mask, edge_mask, z, edge_z):
+    """One round of DPM_Solver_2D at `nfe` evaluations (cfg carries the method; order 2): eager (d) or graph replay (dg)."""
+    from jodo_amd.mix_dpm_solver import DPM_Solver_2D
+    cfg.sampling.steps = nfe
+    solver = DPM_Solver_2D(ns, cfg)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    if form == 'dg':
+        from jodo_amd.graphed import GraphedDPMRound2D
+        x, e = GraphedDPMRound2D(solver, model, node_mask, edge_mask).run(z, edge_z)
+    else:
+        x, e = solver.sampling(model, z, node_mask, edge_mask, edge_z, None)
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, None, bool(torch.isfinite(x).all() and torch.isfinite(e).all())
+
+
+def dpm_evaluations(method, nfe):
+    """Network evaluations of one order-2 round: the single-step solver makes 2 * (nfe // 2), the multistep one nfe."""
+    return 2 * (nfe // 2) if method == 'singlestep_fixed' else nfe
+
+
 def round_leg(args):
     torch.set_num_threads(8)
     dev = torch.device('cuda:0')
     cfg_name, _ = WORKLOADS[args.workload]
     model = deterministic_init_(get_model_class('DGT_concat_2D')(configs.get(cfg_name)), seed=7).to(dev).eval()
     out = dict(workload=args.workload, config=cfg_name, steps=args.steps, forms={
-        'a': 'eager, torch draws', 'b': 'eager, in-kernel draws', 'c': 'graph replay, in-kernel draws', 'cd': 'c + device decode'}, batches={})
+        'a': 'eager, torch draws', 'b': 'eager, in-kernel draws', 'c': 'graph replay, in-kernel draws', 'cd': 'c + device decode',
+        'd': "DPM-Solver++ 'dpm_2d', eager", 'dg': "DPM-Solver++ 'dpm_2d', graph replay"}, batches={})
+    if args.nfe is not None:
+        out.update(nfe=args.nfe, dpm_solver_method=args.dpm_method, dpm_solver_order=2,
+                   evaluations_per_round=dpm_evaluations(args.dpm_method, args.nfe))
     for batch in [int(b) for b in args.batches.split(',')]:
         cfg, n_nodes, node_mask, edge_mask, z, edge_z = _setup(args.workload, batch, dev)
         ns = NoiseScheduleVP(cfg.sde.schedule, continuous_beta_0=cfg.sde.continuous_beta_0, continuous_beta_1=cfg.sde.continuous_beta_1)
         _one_round('a', cfg, model, ns, 3, n_nodes, node_mask, edge_mask, z, edge_z)           # packs the weights, loads the kernels
+        cfg.sampling['dpm_solver_method'], cfg.sampling['dpm_solver_order'] = args.dpm_method, 2
         rec = {}
         for form in args.forms.split(','):
             runs = []
+            is_dpm = form in ('d', 'dg')
+            if is_dpm and args.nfe is None:
+                raise SystemExit("forms d / dg need --nfe")
+            count = dpm_evaluations(args.dpm_method, args.nfe) if is_dpm else args.steps       # network evaluations of the round
             for _ in range(args.repeat):
-                loop, dec, finite = _one_round(form, cfg, model, ns, args.steps, n_nodes, node_mask, edge_mask, z, edge_z)
+                loop, dec, finite = _one_round(form, cfg, model, ns, args.nfe if is_dpm else args.steps, n_nodes, node_mask, edge_mask, z, edge_z)
                 total = loop + (dec or 0.0)
-                runs.append(dict(ms_per_step=round(loop / args.steps * 1e3, 4), round_s=round(loop, 3),
+                runs.append(dict(ms_per_step=round(loop / count * 1e3, 4), round_s=round(loop, 3),
                                  decode_ms=None if dec is None else round(dec * 1e3, 2), molecules_per_s=round(batch / total, 2), finite=finite))
                 print(json.dumps(dict(batch=batch, form=form, **runs[-1])), flush=True)
             rec[form] = runs[0] if args.repeat == 1 else dict(runs=runs, ms_per_step=round(sum(r['ms_per_step'] for r in runs) / len(runs), 4),
@@ -212,7 +251,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--round', action='store_true', help='time complete sampling rounds in the forms a, b, c, cd (see the module docstring)')
     ap.add_argument('--batches', default='2000,128')
-    ap.add_argument('--forms', default='a,b,c,cd')
+    ap.add_argument('--forms', default=None, help='default a,b,c,cd; d,dg with --nfe')
+    ap.add_argument('--nfe', type=int, default=None, help="--round: the DPM leg (sampling.method 'dpm_2d') at this many network evaluations")
+    ap.add_argument('--dpm-method', choices=('singlestep_fixed', 'multistep'), default='singlestep_fixed', help='order 2 either way')
     ap.add_argument('--repeat', type=int, default=1)
     ap.add_argument('--parent-json', default=None)
     ap.add_argument('--out', default=None)
@@ -228,6 +269,10 @@ def main():
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 1000 if args.round else 20
+    if args.forms is None:
+        args.forms = 'd,dg' if args.nfe is not None else 'a,b,c,cd'
+    if args.round and args.nfe is not None and args.out is None:
+        args.out = os.path.join(ROOT, 'profiles', 'dgt2d_dpm2d_round_%s_nfe%d.json' % (args.workload, args.nfe))
     if args.round:
         return round_leg(args)
     torch.set_num_threads(8)

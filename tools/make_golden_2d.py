@@ -6,6 +6,10 @@ oracle/ref_import.py with 8 torch threads.  Weights are deterministic_init_ (see
   tests/golden/traj2d_zinc_anc5.npz, traj2d_moses_anc5.npz
                                                  AncestralSampler_2D, 5 steps: all draws, every step's inputs and predictions, end
                                                  state, decodes, per-entry decision margins and the share below 1e-3 per kind
+  tests/golden/traj2d_zinc_dpm_{single2,single3,single1,multi2}.npz, traj2d_moses_dpm_single2.npz
+                                                 the reference's DPM_Solver_hybrid (all four solver variants, NFE 4 - 6) around the 2-D model
+                                                 with three zero position columns (dpm_fixture): every evaluation's inputs and
+                                                 prediction, end state, decodes, margins — the oracle of sampling.method 'dpm_2d'
   tests/golden/samplefn2d_zinc.npz               the reference's own get_sampling_fn (2-D), batch 16, 10 steps, seeded; the draws
                                                  are a function of the seed (checksums stored), results before the final shuffle
   tests/golden/grad2d_zinc.npz, grad2d_moses.npz the reference's own get_sde_2D_loss_fn + loss.backward() (eval-mode dropout, self-conditioned
@@ -546,5 +550,93 @@ def main():
             job()
 
 
+DPM_VARIANTS = {            # file suffix -> (dpm_solver_method, dpm_solver_order, NFE): a single-step NFE is a multiple of its order
+    'single2': ('singlestep_fixed', 2, 6),
+    'single3': ('singlestep_fixed', 3, 6),
+    'single1': ('singlestep_fixed', 1, 4),
+    'multi2': ('multistep', 2, 5),
+}
+
+
+def dpm_fixture(ref, which, variant, n_nodes=(38, 1, 2, 17, 9), seed=21, nfe=None):
+    """traj2d_<which>_dpm_<variant>.npz: the reference's own DPM_Solver_hybrid (mix_dpm_solver.py) around its DGT_concat_2D.  The
+    solver wants three position channels in front of the node state; the state gets three zero columns, and the model wrapper strips
+    them from x and cond_x and puts zeros in front of the prediction.  The position branch then turns zeros into centre-of-gravity-free
+    noise that nobody reads; the atom / charge channels and the edge tensor go through the reference's DPM-Solver++ arithmetic
+    untouched.  Recorded: z, edge_z, every evaluation's input state / noise level / prediction, the end state, decodes, decision
+    margins and shares (layout of traj2d_*_anc5.npz).  If a seed fails the margin cap or gives degenerate decodes, pick another one
+    here (it is stored in the file); the cap stays."""
+    method, order, steps = DPM_VARIANTS[variant]
+    steps = steps if nfe is None else nfe
+    cfg, model = build_reference_model(ref, CFG[which], seed, head_gain=HEAD_GAIN_2D)
+    cfg.sampling.method, cfg.sampling.steps = 'fast', steps
+    cfg.sampling.dpm_solver_method, cfg.sampling.dpm_solver_order = method, order
+    n_nodes = [min(n, cfg.data.max_node) for n in n_nodes]
+    assert 1 in n_nodes and 2 in n_nodes and cfg.data.max_node in n_nodes
+    assert method == 'multistep' or steps % order == 0          # single-step: K = steps // order outer steps, NFE = K * order
+    S = ref.sampling
+    ns = ref.diffusion.noise_schedule.NoiseScheduleVP(cfg.sde.schedule, continuous_beta_0=cfg.sde.continuous_beta_0,
+                                                      continuous_beta_1=cfg.sde.continuous_beta_1)
+    B, N = len(n_nodes), max(n_nodes)
+    nm, em = masks(n_nodes)
+    nd = cfg.data.atom_types + int(cfg.model.include_fc_charge)
+    torch.manual_seed(seed)
+    z = S.sample_gaussian_with_mask((B, N, nd), 'cpu', nm)
+    ez = S.sample_symmetric_edge_feature_noise(B, N, cfg.model.edge_ch, em)
+    rec_in = []
+
+    def model3(t, x, node_mask, edge_mask, edge_x=None, noise_level=None, cond_x=None, cond_edge_x=None, context=None):
+        cx = None if cond_x is None else cond_x[:, :, 3:]
+        out = model(t, x[:, :, 3:], node_mask, edge_mask, edge_x=edge_x, noise_level=noise_level, cond_x=cx, cond_edge_x=cond_edge_x)
+        rec_in.append((x[:, :, 3:].clone(), edge_x.clone(), noise_level.clone(), out[0].clone(), out[1].clone()))
+        return torch.cat([torch.zeros(B, N, 3), out[0]], dim=2), out[1]
+
+    solver = ref.mix_dpm_solver.DPM_Solver_hybrid(ns, cfg)
+    x3, e_end = solver.sampling(model3, torch.cat([torch.zeros(B, N, 3), z], dim=2), nm, em, ez, None)
+    x_end = x3[:, :, 3:].contiguous()
+    emd = em.reshape(B, N, N, 1)
+    assert len(rec_in) == steps, "model calls %d != NFE %d" % (len(rec_in), steps)
+    assert torch.equal(e_end, e_end.transpose(1, 2)), "edge end state not symmetric"
+    assert float((x_end * (1 - nm)).abs().max()) == 0.0 and float((e_end * (1 - emd)).abs().max()) == 0.0, "padding not zero"
+    inv = ref.utils.get_data_inverse_scaler(cfg)
+    one_hot, fc, et = S.post_process_2D(x_end.clone(), cfg.data.atom_types, cfg.model.include_fc_charge, nm, inv, e_end.clone(), em,
+                                        cfg.data.compress_edge)
+    margins, shares = decision_margins(cfg, inv, x_end, e_end, nm, em)
+    atoms, bonds = np.unique(one_hot.argmax(2).numpy()[nm[..., 0].numpy() > 0]), np.unique(et.numpy())
+    assert len(atoms) >= 2 and len(bonds) >= 2, "degenerate decodes: atom types %s bond types %s" % (atoms, bonds)
+    for k, s in shares.items():
+        assert s <= MARGIN_CAP, "%s: %.3f of the real entries within %g of a threshold" % (k, s, MARGIN)
+    from oracle.make_golden import savez_stable
+    fname = 'traj2d_%s_dpm_%s.npz' % (which, variant)
+    arrays = dict(torch_num_threads=np.int64(torch.get_num_threads()), cfg_name=np.array(CFG[which]), seed=np.int64(seed),
+                  steps=np.int64(steps), dpm_solver_method=np.array(method), dpm_solver_order=np.int64(order),
+                  head_gain=np.float64(HEAD_GAIN_2D), n_nodes=np.array(n_nodes), z=z.numpy(), edge_z=ez.numpy(),
+                  x_end=x_end.numpy(), edge_x_end=e_end.numpy(),
+                  step_x=torch.stack([r[0] for r in rec_in]).numpy(), step_edge_x=torch.stack([r[1] for r in rec_in]).numpy(),
+                  step_noise_level=torch.stack([r[2] for r in rec_in]).numpy(),
+                  step_pred_x=torch.stack([r[3] for r in rec_in]).numpy(), step_pred_e=torch.stack([r[4] for r in rec_in]).numpy(),
+                  atom_type=one_hot.argmax(2).numpy(), fc=fc.numpy(), edge_type=et.numpy(),
+                  margin_kinds=np.array(sorted(margins)), margin_shares=np.array([shares[k] for k in sorted(margins)]),
+                  margin_cap=np.float64(MARGIN_CAP))
+    for k, v in margins.items():
+        arrays['margin_' + k] = v.numpy()
+    savez_stable(os.path.join(OUT, fname), **arrays)
+    print(fname, 'ok; NFE', steps, 'shares', shares, 'atom types', atoms, 'bond types', bonds, 'bytes',
+          os.path.getsize(os.path.join(OUT, fname)))
+
+
+def main_dpm():
+    """The DPM-Solver++ trajectories of the 2-D model (sampling.method 'dpm_2d'); name prefixes select as in main()."""
+    torch.set_num_threads(THREADS)
+    ref = load_reference()
+    jobs = {'traj2d_zinc_dpm_%s' % v: (lambda v=v: dpm_fixture(ref, 'zinc', v)) for v in DPM_VARIANTS}
+    jobs['traj2d_moses_dpm_single2'] = lambda: dpm_fixture(ref, 'moses', 'single2', nfe=4)
+    want = sys.argv[1:]
+    for name, job in jobs.items():
+        if not want or any(name.startswith(w) for w in want):
+            job()
+
+
 if __name__ == '__main__':
     main()
+    main_dpm()
