@@ -66,6 +66,13 @@ void gemm(hipStream_t, int tA, int tB, int M, int N, int K, const float* A, int 
 }
 }
 
+// the plan itself, for the CPU suite to hold restatements of it against (tests/test_train_gemm_plan.py)
+extern "C" void emul_gemm_plan(int tA, int M, int N, int K, int have_ws, size_t ws_floats, int* nsplit, int* kchunk) {
+    const jt::GemmPlan p = jt::gemm_plan(tA, M, N, K, have_ws != 0, ws_floats);
+    *nsplit = p.nsplit;
+    *kchunk = p.kchunk;
+}
+
 // The fused forward chains (jodo_amd/csrc/train_fused.hip) are matrix-instruction kernels: not available to the host emulation, which
 // runs — and thereby checks — the op-by-op sequence they replace.
 #include "train_fused.h"
