@@ -441,8 +441,9 @@ int jodo_dgt2d_fill_desc(const jodo_cfg2d* cfg, int B, int N, const int32_t* n_n
 /* One evaluation.  xh [B,N,nd], edge_x [B,N,N,ch], cond_x / cond_edge_x both given or both NULL (first step: all-ones adjacency
  * head), noise_level [B] -> out_xh [B,N,nd], out_edge [B,N,N,ch], written fully (zeros on padding and the diagonal).
  * flags_dev int32[8]: [0] = 1 when edge_x and cond_edge_x are symmetric (one pair-update / head evaluation per unordered pair),
- * 0 -> directed fallback; [1] = 1 when all noise levels are equal (one shared modulation row).  force_directed != 0: always the
- * directed fallback (tests).  max_blocks < 0: all blocks. */
+ * 0 -> directed fallback; [1] = 1 when all noise levels are equal (one shared modulation row); [2] see jodo_dgt2d_forward_walk;
+ * [3] = 1 when the split-bf16 form ran (jodo_dgt2d_forward_split), 0 from this entry and from jodo_dgt2d_forward_walk.
+ * force_directed != 0: always the directed fallback (tests).  max_blocks < 0: all blocks. */
 int jodo_dgt2d_forward(const jodo_cfg2d* cfg, int B, int N, const int32_t* n_nodes_host, const void* desc_dev, const float* packed_w,
                        const int64_t* woff, int n_woff, const float* xh, const float* edge_x, const float* cond_x,
                        const float* cond_edge_x, const float* noise_level, float* out_xh, float* out_edge, int32_t* flags_dev,
@@ -469,6 +470,32 @@ int jodo_dgt2d_forward_walk(const jodo_cfg2d* cfg, int B, int N, const int32_t* 
                             const void* pair_desc_dev, int walk, const float* packed_w, const int64_t* woff, int n_woff, const float* xh,
                             const float* edge_x, const float* cond_x, const float* cond_edge_x, const float* noise_level, float* out_xh,
                             float* out_edge, int32_t* flags_dev, void* workspace, int force_directed, int max_blocks, void* stream);
+/* Split-bf16 ("bf16x3") form of the 2-D model's node GEMMs and pair update (opt-in; csrc/dgt2d_forward.hip k2d_gemm_s, k2d_pair_s; the
+ * arithmetic of csrc/dgt_split.h: w x = six bf16 x bf16 products of the hi / mid / lo terms, accumulated in fp32).  Attention, the
+ * edge heads, the embeddings and the one-row time / modulation GEMMs stay exact fp32 and keep reading the fp32 blob, as do all biases.
+ * The weight tape is a function of the packed blob: every covered tiled matrix [nb][nk][8 quads][64 lanes][4] floats becomes
+ *   bf16 [nb][nk * 4 K16 steps][3 terms: hi, mid, lo][64 lanes][8],
+ * element j of lane l in K16 step G of a chunk = the chunk's f32 k-step 8 G + j of the same lane, tile[(8 G + j) / 4][l][(8 G + j) % 4],
+ * every term rounded to nearest even (hi + mid + lo is the float exactly).  Covered slots: per block J2B_QKV_W, J2B_N2E_W, J2B_FF1_W,
+ * J2B_FF2_W, J2B_NRO_W, J2B_FF3_W, J2B_FF4_W, J2B_ERO_W; global J2_NH1_W, J2_NH2_W, J2_NH3_W.
+ * jodo_dgt2d_split_size: *tape_bytes and toff_out[n_woff] = byte offset of every covered slot in the tape (16-byte aligned), indexed
+ * like the woff table, -1 for the slots that are not covered.  n_woff must be the table size of jodo_dgt2d_packed_size.
+ * jodo_dgt2d_pack_split_host: (packed HOST blob, its woff table) -> the tape in HOST memory; the caller uploads it. */
+int jodo_dgt2d_split_size(const jodo_cfg2d* cfg, size_t* tape_bytes, int64_t* toff_out, int n_woff);
+int jodo_dgt2d_pack_split_host(const jodo_cfg2d* cfg, const float* packed_host, const int64_t* woff, int n_woff, void* tape_host,
+                               size_t cap_bytes);
+/* jodo_dgt2d_forward_walk in the split form: tape_dev = device copy of the tape, toff = its HOST offset table.  walk as in
+ * jodo_dgt2d_forward_walk (JODO_2D_WALK_DIRECTED: pair_desc_dev is not read).  Records flags_dev[3] = 1. */
+int jodo_dgt2d_forward_split(const jodo_cfg2d* cfg, int B, int N, const int32_t* n_nodes_host, const void* desc_dev,
+                             const void* pair_desc_dev, int walk, const float* packed_w, const int64_t* woff, int n_woff,
+                             const void* tape_dev, const int64_t* toff, const float* xh, const float* edge_x, const float* cond_x,
+                             const float* cond_edge_x, const float* noise_level, float* out_xh, float* out_edge, int32_t* flags_dev,
+                             void* workspace, int force_directed, int max_blocks, void* stream);
+/* tests: the production row GEMM of the 2-D model on caller-packed device weights, y [rows, n_out] = epi(x [rows, K] W^T + bias),
+ * act 1 = SiLU; K a multiple of 64, n_out of 32.  split = 0: w_dev is the f32 packing (k2d_gemm); 1: the split packing (k2d_gemm_s),
+ * both as jodo_debug_pack_split emits them. */
+int jodo_debug_gemm2d(int split, const float* x, int rows, int K, int n_out, const void* w_dev, const float* bias, int act, float* y,
+                      void* stream);
 /* Ancestral update of the 2-D sampler (sampling.py:637-658) for a node tensor WITHOUT position channels, replayed-draw form:
  * x_mean = cx x + cp pred, x_next = x_mean + sigma eps_node masked to the real atoms (all node channels are plain masked noise);
  * the edge tensors likewise with eps_edge [B,N,N,ch] read from its strict lower triangle for both orientations of a pair (the

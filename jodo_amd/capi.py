@@ -29,6 +29,7 @@ def lib():
         _lib.jodo_last_error.restype = ctypes.c_char_p
         _bind_2d_sampling(_lib)
         _bind_2d_pair(_lib)
+        _bind_2d_split(_lib)
     return _lib
 
 
@@ -63,6 +64,22 @@ def _bind_2d_pair(L):
     fill.argtypes = [p, i, i, p, p, ctypes.c_int64]
     fwd.argtypes = [p, i, i, p, p, p, i, p, p, i] + [p] * 9 + [i, i, p]
     lay.restype = fill.restype = fwd.restype = i
+
+
+def _bind_2d_split(L):
+    """Argument types of the 2-D model's split-bf16 exports (jodo_dgt2d_split_size, jodo_dgt2d_pack_split_host,
+    jodo_dgt2d_forward_split, jodo_debug_gemm2d; include/jodo_hip.h)."""
+    i, p = ctypes.c_int, ctypes.c_void_p
+    try:
+        size, pack, fwd, dbg = L.jodo_dgt2d_split_size, L.jodo_dgt2d_pack_split_host, L.jodo_dgt2d_forward_split, L.jodo_debug_gemm2d
+    except AttributeError as e:
+        raise JodoHipError("%s lacks the 2-D split-bf16 exports (%s): rebuild it with python -c 'import __graft_entry__ as g; g.build()'"
+                           % (LIB_PATH, e))
+    size.argtypes = [p, p, p, i]
+    pack.argtypes = [p, p, p, i, p, ctypes.c_size_t]
+    fwd.argtypes = [p, i, i, p, p, p, i, p, p, i, p, p] + [p] * 9 + [i, i, p]
+    dbg.argtypes = [i, p, i, i, i, p, p, i, p, p]
+    size.restype = pack.restype = fwd.restype = dbg.restype = i
 
 
 def check(code, what=''):
@@ -148,6 +165,21 @@ def pack_weights_2d(cfg_struct, state_dict, device=None):
     check(L.jodo_dgt2d_pack_weights_host(ctypes.byref(cfg_struct), arr, len(keep), ctypes.c_void_p(blob.data_ptr()),
                                          ctypes.c_size_t(n_floats.value), woff, n_woff.value), 'jodo_dgt2d_pack_weights_host')
     return (blob if device is None else blob.to(device)), woff, n_woff.value
+
+
+def split_tape_2d(cfg_struct, blob_host, woff, n_woff, device=None):
+    """The 2-D model's split-bf16 tape, derived from its packed blob (`blob_host`: the CPU blob of pack_weights_2d with its offset
+    table): (tape uint8 tensor on the CPU or uploaded to `device`, toff ctypes int64 array — byte offsets into the tape indexed like
+    `woff`, -1 for the slots that stay fp32) through jodo_dgt2d_split_size / jodo_dgt2d_pack_split_host."""
+    import torch
+    L = lib()
+    total = ctypes.c_size_t()
+    toff = (ctypes.c_int64 * n_woff)()
+    check(L.jodo_dgt2d_split_size(ctypes.byref(cfg_struct), ctypes.byref(total), toff, n_woff), 'jodo_dgt2d_split_size')
+    tape = torch.empty(total.value, dtype=torch.uint8)
+    check(L.jodo_dgt2d_pack_split_host(ctypes.byref(cfg_struct), ctypes.c_void_p(blob_host.data_ptr()), woff, n_woff,
+                                       ctypes.c_void_p(tape.data_ptr()), ctypes.c_size_t(total.value)), 'jodo_dgt2d_pack_split_host')
+    return (tape if device is None else tape.to(device)), toff
 
 
 def pack_split_tape(cfg_struct, state_dict, device=None):

@@ -12,7 +12,7 @@
 // Every projection is exact fp32 on v_mfma_f32_32x32x2_f32 in the strip model of dgt_device.h (32 items per wave, weights as A operand,
 // packed by csrc/dgt2d_pack.cpp).  The two per-edge kernels are persistent: a workgroup of four waves copies the block's weights
 // (128 KiB lin_edge0 | lin_edge1; 72 KiB edge FFN + readout) into LDS once and its waves then walk over the items.
-#include "dgt_device.h"
+#include "dgt_split.h"
 #include <vector>
 #include "jodo_hip_internal.h"
 #include "../../include/jodo_hip.h"
@@ -69,11 +69,13 @@ struct K2 {                      // kernel arguments
     int B, N, Nn, P, nd, ch, layer;
     float th;
     const float* W;
-    const int32_t* flags;        // [0] symmetric inputs, [1] shared noise level
+    const int32_t* flags;        // [0] symmetric inputs, [1] shared noise level, [2] pair walk ran, [3] split-bf16 form ran
     const float *xh, *edge_x, *cond_x, *cond_edge_x, *noise;
     float *out_xh, *out_edge;
     float *hid1, *tembs, *mods, *h, *hm, *qkv, *hn, *u, *f1, *ahid, *nh1, *nh2, *nh3, *e, *ehid;
     int64_t wg[J2_GLOBAL_COUNT], wb[J2B_BLOCK_COUNT];
+    const char* T;               // split tape (bf16x3 form) or NULL; tb: byte offsets of this block's ff_linear3 | ff_linear4 | readout in it
+    int64_t tb[3];
 };
 
 __device__ __forceinline__ float half_max(float v) {          // over the 32 lanes of a half
@@ -105,8 +107,8 @@ __device__ __forceinline__ float half_sum16(const float (&v)[16], int j) {
 }
 
 // ---- prologue ------------------------------------------------------------------------------------------------------------------
-__global__ void k2d_flags_init(int32_t* flags, int force_directed) {
-    if (threadIdx.x == 0) { flags[0] = force_directed ? 0 : 1; flags[1] = 1; }
+__global__ void k2d_flags_init(int32_t* flags, int force_directed, int split) {
+    if (threadIdx.x == 0) { flags[0] = force_directed ? 0 : 1; flags[1] = 1; flags[3] = split; }
 }
 __global__ void k2d_flags(K2 A, int32_t* flags) {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -153,6 +155,36 @@ struct Gemm2 {
     const float* X; int ldx; float* Y; int ldy; const float* W; const float* bias; int rows, nk, NB, act;    // act 1: SiLU
     const float* R; int ldr; const float* gate; int gate_ld; const int* node_b; const int32_t* flags; int uni_rows;
 };
+// bias, SiLU, R + gate y (per-row molecule gate, or the shared row under flags[1]) and the store of a strip's 32 x 32 accumulator images
+template <int NOB, int MT>
+__device__ __forceinline__ void gemm_epilogue(const Gemm2& G, const f32x16 (&acc)[NOB][MT], const int (&row)[MT], int ob0, int h) {
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+        if (row[m] >= G.rows) continue;
+        int mrow = 0;
+        if (G.R && !G.flags[1]) mrow = G.node_b[row[m]] >> 8;
+#pragma unroll
+        for (int o = 0; o < NOB; ++o) {
+            if (ob0 + o >= G.NB) continue;
+            const int col0 = (ob0 + o) * 32 + 16 * h;
+            float v[16], bb[16];
+            if (G.bias) load16(G.bias + col0, bb);
+#pragma unroll
+            for (int s = 0; s < 16; ++s) {
+                v[s] = acc[o][m][s] + (G.bias ? bb[s] : 0.f);
+                if (G.act == 1) v[s] = silu_f(v[s]);
+            }
+            if (G.R) {
+                float rr[16], gg[16];
+                load16(G.R + (size_t)row[m] * G.ldr + col0, rr);
+                load16(G.gate + (size_t)mrow * G.gate_ld + col0, gg);
+#pragma unroll
+                for (int s = 0; s < 16; ++s) v[s] = fmaf(gg[s], v[s], rr[s]);
+            }
+            store16(G.Y + (size_t)row[m] * G.ldy + col0, v);
+        }
+    }
+}
 template <int NOB, int MT>
 __global__ __launch_bounds__(64) void k2d_gemm(Gemm2 G) {
     const int lane = threadIdx.x, j = lane & 31, h = lane >> 5;
@@ -189,32 +221,84 @@ __global__ __launch_bounds__(64) void k2d_gemm(Gemm2 G) {
             }
         }
     }
+    gemm_epilogue<NOB, MT>(G, acc, row, ob0, h);
+}
+
+// ---- row GEMM, split-bf16 form (opt-in; dgt_split.h): same contract, same accumulator image, same epilogue -----------------------------
+// G.W points at the matrix's slot of the split tape (csrc/dgt2d_pack.cpp): [out block][nk * 4 K16 steps][hi, mid, lo][64 lanes][8 bf16].
+// Per K chunk of 64 the activations of a tile become four Split8; a "group" is one (output block, K chunk) = 4 K16 steps = 12 KiB of
+// tape, whose 24 * MT MFMAs run while the next group's twelve 16-byte loads are in flight (WPipeS<4>); the next chunk's activation rows
+// are requested before the chunk's first group.  With MT > 1 neighbouring MFMAs alternate between the tiles.  Output blocks past NB (NB
+// not a multiple of NOB) read the last block's tape again and are dropped by the epilogue.
+// Shape, by measurement (ZINC250k B = 2000, ms per sampling step, exact form 21.5): NOB x MT = 4 x 2 18.33, 8 x 1 17.95 - one tile per wave
+// halves the splits per MFMA and doubles the tape traffic per row, and the splits cost more; 8 x 1 with the next chunk's split issued
+// between the last group's MFMAs (sched_group_barrier) 17.95: nothing, not kept.  DESIGN.md 4j has the kernel tables.
+constexpr int K2S_NOB = 8, K2S_MT = 1;
+template <int NOB, int MT>
+__global__ __launch_bounds__(64) void k2d_gemm_s(Gemm2 G) {
+    const int lane = threadIdx.x, j = lane & 31, h = lane >> 5;
+    const int strip = blockIdx.x, ob0 = blockIdx.y * NOB;
+    f32x16 acc[NOB][MT];
+    int row[MT];
+    const float* xr[MT];
+    float nxt[MT][32];
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
-        if (row[m] >= G.rows) continue;
-        int mrow = 0;
-        if (G.R && !G.flags[1]) mrow = G.node_b[row[m]] >> 8;
+        row[m] = (strip * MT + m) * 32 + j;
+        xr[m] = G.X + (size_t)min(row[m], G.rows - 1) * G.ldx;
+        load_nat<2>(xr[m], h, nxt[m]);
+#pragma unroll
+        for (int o = 0; o < NOB; ++o) acc[o][m] = zero16();
+    }
+    const WSrc ws = make_wsrc(G.W, lane);
+    const unsigned blk = (unsigned)G.nk * 12288u;
+    unsigned boff[NOB];
+#pragma unroll
+    for (int o = 0; o < NOB; ++o) boff[o] = (unsigned)min(ob0 + o, G.NB - 1) * blk;
+    WPipeS<4> wp;
+    wpipe_prime_s(wp, ws, boff[0]);
+    for (int kc = 0; kc < G.nk; ++kc) {
+        Split8 xs[MT][4];
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) xs[m][g] = split8(&nxt[m][8 * g]);
+        if (kc + 1 < G.nk) {
+#pragma unroll
+            for (int m = 0; m < MT; ++m) load_nat<2>(xr[m] + (kc + 1) * 64, h, nxt[m]);
+        }
 #pragma unroll
         for (int o = 0; o < NOB; ++o) {
-            if (ob0 + o >= G.NB) continue;
-            const int col0 = (ob0 + o) * 32 + 16 * h;
-            float v[16], bb[16];
-            if (G.bias) load16(G.bias + col0, bb);
+            u32x4 cur[4][3];
 #pragma unroll
-            for (int s = 0; s < 16; ++s) {
-                v[s] = acc[o][m][s] + (G.bias ? bb[s] : 0.f);
-                if (G.act == 1) v[s] = silu_f(v[s]);
-            }
-            if (G.R) {
-                float rr[16], gg[16];
-                load16(G.R + (size_t)row[m] * G.ldr + col0, rr);
-                load16(G.gate + (size_t)mrow * G.gate_ld + col0, gg);
+            for (int i = 0; i < 4; ++i)
 #pragma unroll
-                for (int s = 0; s < 16; ++s) v[s] = fmaf(gg[s], v[s], rr[s]);
+                for (int t = 0; t < 3; ++t) cur[i][t] = wp.q[i][t];
+            // (behind the last group the ring re-reads that group: a live address, never consumed)
+            const unsigned nof = o + 1 < NOB ? boff[o + 1] + (unsigned)kc * 12288u : boff[0] + (unsigned)min(kc + 1, G.nk - 1) * 12288u;
+            wpipe_prime_s(wp, ws, nof);
+            pipeline_fence();
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const bf16x8 wh = as_bf16x8(cur[i][0]), wm = as_bf16x8(cur[i][1]), wl = as_bf16x8(cur[i][2]);
+                // the six products of mfma_step_s, small terms first, dealt over the tiles
+#pragma unroll
+                for (int m = 0; m < MT; ++m) acc[o][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xs[m][i].l, acc[o][m], 0, 0, 0);
+#pragma unroll
+                for (int m = 0; m < MT; ++m) acc[o][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, xs[m][i].h, acc[o][m], 0, 0, 0);
+#pragma unroll
+                for (int m = 0; m < MT; ++m) acc[o][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wm, xs[m][i].m, acc[o][m], 0, 0, 0);
+#pragma unroll
+                for (int m = 0; m < MT; ++m) acc[o][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xs[m][i].m, acc[o][m], 0, 0, 0);
+#pragma unroll
+                for (int m = 0; m < MT; ++m) acc[o][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wm, xs[m][i].h, acc[o][m], 0, 0, 0);
+#pragma unroll
+                for (int m = 0; m < MT; ++m) acc[o][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xs[m][i].h, acc[o][m], 0, 0, 0);
             }
-            store16(G.Y + (size_t)row[m] * G.ldy + col0, v);
+            pipeline_fence();
         }
     }
+    gemm_epilogue<NOB, MT>(G, acc, row, ob0, h);
 }
 
 // ---- embeddings ------------------------------------------------------------------------------------------------------------------
@@ -680,6 +764,103 @@ __global__ __launch_bounds__(256, 1) void k2d_pair(K2 A) {
     }
 }
 
+// ---- 2-D pair update, split-bf16 form (opt-in): the same item walk, LayerNorm, modulation and in-place update; the nine tiles on the
+// bf16 MFMA from an LDS copy of the block's tape slots (108 KiB: one workgroup of eight waves per compute unit, two waves per SIMD) -----
+__device__ __forceinline__ f32x16 mfma_lds_s(const u32x4* tile, int lane, const Split8* x, f32x16 acc) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const bf16x8 wh = as_bf16x8(tile[(g * 3 + 0) * 64 + lane]), wm = as_bf16x8(tile[(g * 3 + 1) * 64 + lane]);
+        const bf16x8 wl = as_bf16x8(tile[(g * 3 + 2) * 64 + lane]);
+        acc = mfma_step_s(wh, wm, wl, x[g], acc);
+    }
+    return acc;
+}
+constexpr int TS16 = 768;                                    // 16-byte words of a tile in split form (4 K16 steps x 3 terms x 64 lanes)
+
+__global__ __launch_bounds__(512, 1) void k2d_pair_s(K2 A) {
+    __shared__ u32x4 wl[9 * TS16];                           // ff_linear3 (4 tiles) | ff_linear4 (2 x 2 tiles) | readout (1 tile)
+    {
+        const u32x4* s3 = reinterpret_cast<const u32x4*>(A.T + A.tb[0]);
+        const u32x4* s4 = reinterpret_cast<const u32x4*>(A.T + A.tb[1]);
+        const u32x4* sr = reinterpret_cast<const u32x4*>(A.T + A.tb[2]);
+        for (int i = threadIdx.x; i < 4 * TS16; i += 512) { wl[i] = s3[i]; wl[4 * TS16 + i] = s4[i]; }
+        for (int i = threadIdx.x; i < TS16; i += 512) wl[8 * TS16 + i] = sr[i];
+    }
+    __syncthreads();
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
+    const int uni = A.flags[1];
+    const int items = A.flags[0] ? A.P : 2 * A.P;
+    const float* b2e = A.W + A.wb[J2B_N2E_B];
+    const float* b3 = A.W + A.wb[J2B_FF3_B];
+    const float* b4 = A.W + A.wb[J2B_FF4_B];
+    const float* bro = A.W + A.wb[J2B_ERO_B];
+    for (int strip = blockIdx.x * 8 + wave; strip * 32 < items; strip += gridDim.x * 8) {
+        const int item = strip * 32 + j;
+        const bool live = item < items;
+        int b, r, c;
+        item_rc(A, live ? item : items - 1, b, r, c);
+        const int n = A.mol_n[b], noff = A.mol_noff[b];
+        const size_t row = (size_t)A.mol_eoff[b] + (size_t)r * n + c;
+        const float* md = A.mods + (size_t)(uni ? 0 : b) * MODW + (size_t)A.layer * MODB + 6 * D2;
+        float e[32];
+        load_nat<2>(A.e + row * DE, h, e);
+        {
+            float ur[32], uc[32], g[32], bb[32];
+            load_nat<2>(A.u + (size_t)(noff + r) * DE, h, ur);
+            load_nat<2>(A.u + (size_t)(noff + c) * DE, h, uc);
+            lane_vec(md + 2 * DE, h, g);
+            lane_vec(b2e, h, bb);
+#pragma unroll
+            for (int i = 0; i < 32; ++i) e[i] = fmaf(g[i], (ur[i] + uc[i]) + bb[i], e[i]);
+        }
+        layer_norm<32>(e);
+        {
+            float sh[32], sc[32];
+            lane_vec(md + 3 * DE, h, sh);
+            lane_vec(md + 4 * DE, h, sc);
+#pragma unroll
+            for (int i = 0; i < 32; ++i) e[i] = fmaf(e[i], 1.f + sc[i], sh[i]);
+        }
+        Split8 xs[4], hs[8];                                 // the hidden layer's f32 accumulators are split once, block by block
+#pragma unroll
+        for (int g = 0; g < 4; ++g) xs[g] = split8(&e[8 * g]);
+#pragma unroll
+        for (int ob = 0; ob < 4; ++ob) {
+            const f32x16 acc = mfma_lds_s(wl + ob * TS16, lane, xs, zero16());
+            float bb[16], o16[16];
+            load16(b3 + ob * 32 + 16 * h, bb);
+            silu_bias16(acc, bb, o16);
+            hs[2 * ob] = split8(&o16[0]);
+            hs[2 * ob + 1] = split8(&o16[8]);
+            pipeline_fence();
+        }
+        float gm[32];
+        lane_vec(md + 5 * DE, h, gm);
+#pragma unroll
+        for (int ob = 0; ob < 2; ++ob) {
+            f32x16 acc = mfma_lds_s(wl + (4 + ob * 2) * TS16, lane, hs, zero16());
+            acc = mfma_lds_s(wl + (5 + ob * 2) * TS16, lane, hs + 4, acc);
+            float bb[16];
+            load16(b4 + ob * 32 + 16 * h, bb);
+#pragma unroll
+            for (int s = 0; s < 16; ++s) e[ob * 16 + s] = fmaf(gm[ob * 16 + s], acc[s] + bb[s], e[ob * 16 + s]);
+        }
+#pragma unroll
+        for (int g = 0; g < 4; ++g) xs[g] = split8(&e[8 * g]);
+        const f32x16 racc = mfma_lds_s(wl + 8 * TS16, lane, xs, zero16());
+        if (live) {
+            store_nat<2>(A.e + row * DE, h, e);
+            if (h == 0) {
+                float bb[16], o16[16];
+                load16(bro, bb);
+#pragma unroll
+                for (int s = 0; s < 16; ++s) o16[s] = racc[s] + bb[s];
+                store16(A.ehid + row * EHW + DE + 16 * A.layer, o16);
+            }
+        }
+    }
+}
+
 // ---- edge heads: exist / type MLPs on [e0 | 8 readouts] (192), one evaluation per unordered pair (two when directed), 0.5 (E + E^T) --
 __global__ __launch_bounds__(64) void k2d_edge_head(K2 A) {
     const int lane = threadIdx.x, j = lane & 31, h = lane >> 5;
@@ -779,11 +960,19 @@ __global__ void k2d_sampler_step(int B, int N, int nd, int ch, const int32_t* n_
     }
 }
 
+// WS != NULL: the matrix's slot of the split tape, split-bf16 form (never with uni_rows)
 int gemm(hipStream_t st, const float* X, int ldx, float* Y, int ldy, const float* W, const float* bias, int rows, int K, int NB, int act,
-         const K2& A, const float* R = nullptr, int ldr = 0, const float* gate = nullptr, bool uni_rows = false) {
+         const K2& A, const float* R = nullptr, int ldr = 0, const float* gate = nullptr, bool uni_rows = false, const void* WS = nullptr) {
     if (K % 64) return jodo_set_error(JODO_ERR_ARG, "dgt2d gemm: K=%d not a multiple of 64", K);
     Gemm2 G{X, ldx, Y, ldy, W, bias, rows, K / 64, NB, act, R, ldr, gate, MODW, A.node_b, A.flags, uni_rows ? 1 : 0};
-    if (uni_rows) { L2D((k2d_gemm<1, 1>), dim3((rows + 31) / 32, NB), 64, G); }
+    if (WS && !uni_rows) {
+        G.W = static_cast<const float*>(WS);
+        const int strips = (rows + 32 * K2S_MT - 1) / (32 * K2S_MT);
+        if (NB >= 3) { L2D((k2d_gemm_s<K2S_NOB, K2S_MT>), dim3(strips, (NB + K2S_NOB - 1) / K2S_NOB), 64, G); }
+        else if (NB == 2) { L2D((k2d_gemm_s<2, K2S_MT>), dim3(strips, 1), 64, G); }
+        else { L2D((k2d_gemm_s<1, K2S_MT>), dim3(strips, 1), 64, G); }
+    }
+    else if (uni_rows) { L2D((k2d_gemm<1, 1>), dim3((rows + 31) / 32, NB), 64, G); }
     else { L2D((k2d_gemm<4, 2>), dim3((rows + 63) / 64, (NB + 3) / 4), 64, G); }
     return JODO_OK;
 }
@@ -873,7 +1062,8 @@ extern "C" int jodo_dgt2d_fill_desc(const jodo_cfg2d* cfg, int B, int N, const i
 static int forward_2d(const jodo_cfg2d* cfg, int B, int N, const int32_t* n_nodes, const void* desc_dev, const void* pair_desc_dev,
                       const float* packed_w, const int64_t* woff, int n_woff, const float* xh, const float* edge_x, const float* cond_x,
                       const float* cond_edge_x, const float* noise_level, float* out_xh, float* out_edge, int32_t* flags_dev,
-                      void* workspace, int force_directed, int max_blocks, void* stream) {
+                      void* workspace, int force_directed, int max_blocks, void* stream, const void* tape_dev = nullptr,
+                      const int64_t* toff = nullptr) {
     if (!desc_dev || !packed_w || !woff || !xh || !edge_x || !noise_level || !out_xh || !out_edge || !flags_dev || !workspace)
         return jodo_set_error(JODO_ERR_ARG, "dgt2d_forward: null argument");
     if (int rc = jodo_dgt2d_check_cfg(cfg)) return rc;
@@ -881,6 +1071,18 @@ static int forward_2d(const jodo_cfg2d* cfg, int B, int N, const int32_t* n_node
         return jodo_set_error(JODO_ERR_ARG, "dgt2d_forward: cond_x and cond_edge_x must both be given or both NULL");
     if (n_woff != J2_GLOBAL_COUNT + cfg->n_layers * J2B_BLOCK_COUNT)
         return jodo_set_error(JODO_ERR_ARG, "dgt2d_forward: weight table has %d slots, expected %d", n_woff, J2_GLOBAL_COUNT + cfg->n_layers * J2B_BLOCK_COUNT);
+    static const int split_global[] = {J2_NH1_W, J2_NH2_W, J2_NH3_W};
+    static const int split_block[] = {J2B_QKV_W, J2B_N2E_W, J2B_FF1_W, J2B_FF2_W, J2B_NRO_W, J2B_FF3_W, J2B_FF4_W, J2B_ERO_W};
+    if (tape_dev) {                                          // split-bf16 form: every covered slot needs its place in the tape
+        if (!toff) return jodo_set_error(JODO_ERR_ARG, "dgt2d_forward: split tape without its offset table");
+        bool ok = true;
+        for (int s : split_global) ok = ok && toff[s] >= 0 && toff[s] % 16 == 0;
+        for (int lyr = 0; lyr < cfg->n_layers; ++lyr)
+            for (int s : split_block) { const int64_t t = toff[J2_GLOBAL_COUNT + lyr * J2B_BLOCK_COUNT + s]; ok = ok && t >= 0 && t % 16 == 0; }
+        if (!ok) return jodo_set_error(JODO_ERR_ARG, "dgt2d_forward: the split tape's offset table misses a covered slot");
+    }
+    const char* T = static_cast<const char*>(tape_dev);
+    auto TG = [&](int slot) -> const void* { return T ? T + toff[slot] : nullptr; };
     Lay l;
     if (int rc = make_lay(B, N, n_nodes, &l)) return rc;
     Pair2 Q{nullptr, nullptr, 0};
@@ -898,7 +1100,7 @@ static int forward_2d(const jodo_cfg2d* cfg, int B, int N, const int32_t* n_node
     K2 A;
     A.mol_n = dsc + l.off_n; A.mol_noff = dsc + l.off_noff; A.mol_eoff = dsc + l.off_eoff; A.node_b = dsc + l.off_node; A.pair = dsc + l.off_pair;
     A.B = B; A.N = N; A.Nn = l.Nn; A.P = l.P; A.nd = cfg->in_node_dim; A.ch = cfg->edge_ch; A.layer = 0; A.th = cfg->edge_quan_th;
-    A.W = packed_w; A.flags = flags_dev;
+    A.W = packed_w; A.flags = flags_dev; A.T = T; A.tb[0] = A.tb[1] = A.tb[2] = 0;
     A.xh = xh; A.edge_x = edge_x; A.cond_x = cond_x; A.cond_edge_x = cond_edge_x; A.noise = noise_level; A.out_xh = out_xh; A.out_edge = out_edge;
     A.hid1 = ws + l.hid1; A.tembs = ws + l.tembs; A.mods = ws + l.mods; A.h = ws + l.h; A.hm = ws + l.hm; A.qkv = ws + l.qkv; A.hn = ws + l.hn;
     A.u = ws + l.u; A.f1 = ws + l.f1; A.ahid = ws + l.ahid; A.nh1 = ws + l.nh1; A.nh2 = ws + l.nh2; A.nh3 = ws + l.nh3; A.e = ws + l.e; A.ehid = ws + l.ehid;
@@ -910,7 +1112,7 @@ static int forward_2d(const jodo_cfg2d* cfg, int B, int N, const int32_t* n_node
         return jodo_set_error(JODO_ERR_LAUNCH, "dgt2d_forward: clearing the outputs failed");
 
     // ---- flags, time embedding, modulation rows ----
-    L2D(k2d_flags_init, 1, 64, flags_dev, force_directed);
+    L2D(k2d_flags_init, 1, 64, flags_dev, force_directed, T ? 1 : 0);
     L2D(k2d_flags, (unsigned)(((size_t)B * N * N + 255) / 256), 256, A, flags_dev);
     L2D(k2d_time1, B, 256, A);
     int rc;
@@ -924,27 +1126,32 @@ static int forward_2d(const jodo_cfg2d* cfg, int B, int N, const int32_t* n_node
     const int persist = 256;                                 // one workgroup of four waves per compute unit
     for (int lyr = 0; lyr < nblocks; ++lyr) {
         A.layer = lyr;
-        for (int i = 0; i < J2B_BLOCK_COUNT; ++i) A.wb[i] = woff[J2_GLOBAL_COUNT + lyr * J2B_BLOCK_COUNT + i];
+        const int slot0 = J2_GLOBAL_COUNT + lyr * J2B_BLOCK_COUNT;
+        for (int i = 0; i < J2B_BLOCK_COUNT; ++i) A.wb[i] = woff[slot0 + i];
+        if (T) { A.tb[0] = toff[slot0 + J2B_FF3_W]; A.tb[1] = toff[slot0 + J2B_FF4_W]; A.tb[2] = toff[slot0 + J2B_ERO_W]; }
         const float* gate_mlp = A.mods + (size_t)lyr * MODB + 5 * D2;
         L2D(k2d_ln_mod, (l.Nn + 3) / 4, 256, A, A.h, (const float*)nullptr, A.hm, 0, 0, D2);
-        if ((rc = gemm(st, A.hm, D2, A.qkv, 3 * D2, W + A.wb[J2B_QKV_W], W + A.wb[J2B_QKV_B], l.Nn, D2, 24, 0, A))) return rc;
+        if ((rc = gemm(st, A.hm, D2, A.qkv, 3 * D2, W + A.wb[J2B_QKV_W], W + A.wb[J2B_QKV_B], l.Nn, D2, 24, 0, A, nullptr, 0, nullptr, false, TG(slot0 + J2B_QKV_W)))) return rc;
         if (pair_desc_dev) {
             L2D(k2d_attn_pair, persist, 256, A, Q);
             L2D(k2d_attn<true>, persist, 256, A);
         } else {
             L2D(k2d_attn<false>, persist, 256, A);
         }
-        if ((rc = gemm(st, A.hn, D2, A.u, DE, W + A.wb[J2B_N2E_W], nullptr, l.Nn, D2, 2, 0, A))) return rc;
+        if ((rc = gemm(st, A.hn, D2, A.u, DE, W + A.wb[J2B_N2E_W], nullptr, l.Nn, D2, 2, 0, A, nullptr, 0, nullptr, false, TG(slot0 + J2B_N2E_W)))) return rc;
         L2D(k2d_ln_mod, (l.Nn + 3) / 4, 256, A, A.h, (const float*)A.hn, A.hm, 2 * D2, 3 * D2, 4 * D2);
-        if ((rc = gemm(st, A.hm, D2, A.f1, 2 * D2, W + A.wb[J2B_FF1_W], W + A.wb[J2B_FF1_B], l.Nn, D2, 16, 1, A))) return rc;
-        if ((rc = gemm(st, A.f1, 2 * D2, A.h, D2, W + A.wb[J2B_FF2_W], W + A.wb[J2B_FF2_B], l.Nn, 2 * D2, 8, 0, A, A.hm, D2, gate_mlp))) return rc;
-        if ((rc = gemm(st, A.h, D2, A.ahid + D2 + 64 * lyr, NHW, W + A.wb[J2B_NRO_W], W + A.wb[J2B_NRO_B], l.Nn, D2, 2, 0, A))) return rc;
-        if (l.P > 0) L2D(k2d_pair, 2 * persist, 256, A);
+        if ((rc = gemm(st, A.hm, D2, A.f1, 2 * D2, W + A.wb[J2B_FF1_W], W + A.wb[J2B_FF1_B], l.Nn, D2, 16, 1, A, nullptr, 0, nullptr, false, TG(slot0 + J2B_FF1_W)))) return rc;
+        if ((rc = gemm(st, A.f1, 2 * D2, A.h, D2, W + A.wb[J2B_FF2_W], W + A.wb[J2B_FF2_B], l.Nn, 2 * D2, 8, 0, A, A.hm, D2, gate_mlp, false, TG(slot0 + J2B_FF2_W)))) return rc;
+        if ((rc = gemm(st, A.h, D2, A.ahid + D2 + 64 * lyr, NHW, W + A.wb[J2B_NRO_W], W + A.wb[J2B_NRO_B], l.Nn, D2, 2, 0, A, nullptr, 0, nullptr, false, TG(slot0 + J2B_NRO_W)))) return rc;
+        if (l.P > 0) {
+            if (T) L2D(k2d_pair_s, persist, 512, A);
+            else L2D(k2d_pair, 2 * persist, 256, A);
+        }
     }
     // ---- heads ----
-    if ((rc = gemm(st, A.ahid, NHW, A.nh1, D2, W + A.wg[J2_NH1_W], W + A.wg[J2_NH1_B], l.Nn, NHW, 8, 1, A))) return rc;
-    if ((rc = gemm(st, A.nh1, D2, A.nh2, D2 / 2, W + A.wg[J2_NH2_W], W + A.wg[J2_NH2_B], l.Nn, D2, 4, 1, A))) return rc;
-    if ((rc = gemm(st, A.nh2, D2 / 2, A.nh3, 32, W + A.wg[J2_NH3_W], W + A.wg[J2_NH3_B], l.Nn, D2 / 2, 1, 0, A))) return rc;
+    if ((rc = gemm(st, A.ahid, NHW, A.nh1, D2, W + A.wg[J2_NH1_W], W + A.wg[J2_NH1_B], l.Nn, NHW, 8, 1, A, nullptr, 0, nullptr, false, TG(J2_NH1_W)))) return rc;
+    if ((rc = gemm(st, A.nh1, D2, A.nh2, D2 / 2, W + A.wg[J2_NH2_W], W + A.wg[J2_NH2_B], l.Nn, D2, 4, 1, A, nullptr, 0, nullptr, false, TG(J2_NH2_W)))) return rc;
+    if ((rc = gemm(st, A.nh2, D2 / 2, A.nh3, 32, W + A.wg[J2_NH3_W], W + A.wg[J2_NH3_B], l.Nn, D2 / 2, 1, 0, A, nullptr, 0, nullptr, false, TG(J2_NH3_W)))) return rc;
     L2D(k2d_finalize_nodes, (l.Nn * A.nd + 255) / 256, 256, A);
     if (l.P > 0) L2D(k2d_edge_head, (l.P + 31) / 32, 64, A);
     return JODO_OK;
@@ -969,6 +1176,34 @@ extern "C" int jodo_dgt2d_forward_walk(const jodo_cfg2d* cfg, int B, int N, cons
         return jodo_set_error(JODO_ERR_ARG, "dgt2d_forward_walk: the pair walk needs the group descriptor");
     return forward_2d(cfg, B, N, n_nodes, desc_dev, walk == JODO_2D_WALK_PAIR ? pair_desc_dev : nullptr, packed_w, woff, n_woff, xh, edge_x,
                       cond_x, cond_edge_x, noise_level, out_xh, out_edge, flags_dev, workspace, force_directed, max_blocks, stream);
+}
+
+// jodo_dgt2d_forward_walk with the split-bf16 form of the node GEMMs and the pair update: tape_dev / toff from jodo_dgt2d_split_size and
+// jodo_dgt2d_pack_split_host (the device copy of the tape, the host offset table).  Records flags_dev[3] = 1.
+extern "C" int jodo_dgt2d_forward_split(const jodo_cfg2d* cfg, int B, int N, const int32_t* n_nodes, const void* desc_dev,
+                                        const void* pair_desc_dev, int walk, const float* packed_w, const int64_t* woff, int n_woff,
+                                        const void* tape_dev, const int64_t* toff, const float* xh, const float* edge_x, const float* cond_x,
+                                        const float* cond_edge_x, const float* noise_level, float* out_xh, float* out_edge, int32_t* flags_dev,
+                                        void* workspace, int force_directed, int max_blocks, void* stream) {
+    if (walk != JODO_2D_WALK_DIRECTED && walk != JODO_2D_WALK_PAIR)
+        return jodo_set_error(JODO_ERR_ARG, "dgt2d_forward_split: walk %d is neither directed (0) nor pair (1)", walk);
+    if (walk == JODO_2D_WALK_PAIR && !pair_desc_dev)
+        return jodo_set_error(JODO_ERR_ARG, "dgt2d_forward_split: the pair walk needs the group descriptor");
+    if (!tape_dev || !toff) return jodo_set_error(JODO_ERR_ARG, "dgt2d_forward_split: null split tape");
+    return forward_2d(cfg, B, N, n_nodes, desc_dev, walk == JODO_2D_WALK_PAIR ? pair_desc_dev : nullptr, packed_w, woff, n_woff, xh, edge_x,
+                      cond_x, cond_edge_x, noise_level, out_xh, out_edge, flags_dev, workspace, force_directed, max_blocks, stream, tape_dev,
+                      toff);
+}
+
+// tests: the production row GEMM on caller-packed weights, Y [rows, n_out] = epi(X [rows, K] W^T + bias).  split = 0: w_dev is the f32
+// packing, k2d_gemm<4, 2>; split = 1: the split packing (both as jodo_debug_pack_split emits them), k2d_gemm_s as forward_2d launches it.
+extern "C" int jodo_debug_gemm2d(int split, const float* x, int rows, int K, int n_out, const void* w_dev, const float* bias, int act,
+                                 float* y, void* stream) {
+    if (!x || !w_dev || !y || rows <= 0 || K <= 0 || n_out <= 0 || n_out % 32 || (act != 0 && act != 1))
+        return jodo_set_error(JODO_ERR_ARG, "debug_gemm2d: bad argument");
+    K2 A{};
+    return gemm((hipStream_t)stream, x, K, y, n_out, static_cast<const float*>(w_dev), bias, rows, K, n_out / 32, act, A, nullptr, 0, nullptr,
+                false, split ? w_dev : nullptr);
 }
 
 extern "C" int jodo_dgt2d_pair_layout(const jodo_cfg2d* cfg, int B, int N, const int32_t* n_nodes, int64_t* out8) {

@@ -247,3 +247,100 @@ extern "C" int jodo_dgt2d_pack_weights_host(const jodo_cfg2d* cfg, const jodo_te
     std::memcpy(packed_host, blob.data(), need * sizeof(float));
     return JODO_OK;
 }
+
+// ---- split-bf16 ("bf16x3") weight tape of the node GEMMs and the pair update (opt-in form, csrc/dgt2d_forward.hip) --------------------------------------
+// A function of the packed blob: every covered tiled matrix float [nb][nk][8 quads][64 lanes][4] is re-read as
+//     bf16 [nb][nk * 4 K16 steps][3 terms: hi, mid, lo][64 lanes][8]
+// where element j of lane l in K16 step G of a chunk is the chunk's f32 k-step 8 G + j of the same lane, tile[(8 G + j) / 4][l][(8 G + j) % 4]
+// (the relation of csrc/dgt_split.h between the two MFMA forms), so row maps and slot order have no second implementation.  Every term is
+// rounded to nearest even, as split8 rounds the activations; hi + mid + lo is the float exactly.
+namespace {
+
+struct SplitSlot { int slot, nb, nk; };                   // slot: index into the woff table
+
+std::vector<SplitSlot> split_slots(const jodo_cfg2d* c) {
+    const int D = c->nf, De = D / 4, L = c->n_layers, cn = 2 * D / L, KN = D + L * cn;
+    std::vector<SplitSlot> s;
+    for (int l = 0; l < L; ++l) {
+        const int at = J2_GLOBAL_COUNT + l * J2B_BLOCK_COUNT;
+        s.push_back({at + J2B_QKV_W, 3 * D / 32, D / 64});
+        s.push_back({at + J2B_N2E_W, De / 32, D / 64});
+        s.push_back({at + J2B_FF1_W, 2 * D / 32, D / 64});
+        s.push_back({at + J2B_FF2_W, D / 32, 2 * D / 64});
+        s.push_back({at + J2B_NRO_W, (cn + 31) / 32, D / 64});
+        s.push_back({at + J2B_FF3_W, 2 * De / 32, De / 64});
+        s.push_back({at + J2B_FF4_W, De / 32, 2 * De / 64});
+        s.push_back({at + J2B_ERO_W, 1, De / 64});
+    }
+    s.push_back({J2_NH1_W, D / 32, (KN + 63) / 64});
+    s.push_back({J2_NH2_W, D / 2 / 32, D / 64});
+    s.push_back({J2_NH3_W, 1, D / 2 / 64});
+    return s;
+}
+
+uint16_t bf16_rne(float v) {                              // finite inputs (weights); NaN keeps a quiet payload
+    uint32_t u;
+    std::memcpy(&u, &v, 4);
+    if ((u & 0x7f800000u) == 0x7f800000u) return (uint16_t)((u >> 16) | ((u & 0xffffu) ? 0x40u : 0u));
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return (uint16_t)(u >> 16);
+}
+float bf16_f32(uint16_t b) {
+    const uint32_t u = (uint32_t)b << 16;
+    float v;
+    std::memcpy(&v, &u, 4);
+    return v;
+}
+
+}  // namespace
+
+extern "C" int jodo_dgt2d_split_size(const jodo_cfg2d* cfg, size_t* tape_bytes, int64_t* toff_out, int n_woff) {
+    if (!tape_bytes || !toff_out) return jodo_set_error(JODO_ERR_ARG, "dgt2d_split_size: null argument");
+    if (int rc = check_cfg(cfg)) return rc;
+    const int want = J2_GLOBAL_COUNT + cfg->n_layers * J2B_BLOCK_COUNT;
+    if (n_woff != want) return jodo_set_error(JODO_ERR_ARG, "dgt2d_split_size: offset table of %d slots, expected %d", n_woff, want);
+    for (int i = 0; i < n_woff; ++i) toff_out[i] = -1;
+    size_t at = 0;
+    for (const SplitSlot& s : split_slots(cfg)) {
+        toff_out[s.slot] = (int64_t)at;
+        at += (size_t)s.nb * s.nk * 4 * 3072;             // a multiple of 16 bytes: every slot stays 16-byte aligned
+    }
+    *tape_bytes = at;
+    return JODO_OK;
+}
+
+extern "C" int jodo_dgt2d_pack_split_host(const jodo_cfg2d* cfg, const float* packed_host, const int64_t* woff, int n_woff, void* tape_host,
+                                          size_t cap_bytes) {
+    if (!packed_host || !woff || !tape_host) return jodo_set_error(JODO_ERR_ARG, "dgt2d_pack_split: null argument");
+    if (int rc = check_cfg(cfg)) return rc;
+    const int want = J2_GLOBAL_COUNT + cfg->n_layers * J2B_BLOCK_COUNT;
+    if (n_woff != want) return jodo_set_error(JODO_ERR_ARG, "dgt2d_pack_split: offset table of %d slots, expected %d", n_woff, want);
+    std::vector<int64_t> toff((size_t)n_woff);
+    size_t need = 0;
+    if (int rc = jodo_dgt2d_split_size(cfg, &need, toff.data(), n_woff)) return rc;
+    if (cap_bytes < need) return jodo_set_error(JODO_ERR_ARG, "dgt2d_pack_split: buffer of %zu bytes, need %zu", cap_bytes, need);
+    size_t blob_floats = 0;
+    int nw = 0;
+    if (int rc = jodo_dgt2d_packed_size(cfg, &blob_floats, &nw)) return rc;
+    for (const SplitSlot& s : split_slots(cfg)) {
+        const size_t tiles = (size_t)s.nb * s.nk;
+        if (woff[s.slot] < 0 || (size_t)woff[s.slot] + tiles * 2048 > blob_floats)
+            return jodo_set_error(JODO_ERR_ARG, "dgt2d_pack_split: weight offset of slot %d outside the packed blob", s.slot);
+        const float* src = packed_host + woff[s.slot];
+        uint16_t* dst = reinterpret_cast<uint16_t*>(static_cast<char*>(tape_host) + toff[(size_t)s.slot]);
+        for (size_t t = 0; t < tiles; ++t)
+            for (int G = 0; G < 4; ++G)
+                for (int l = 0; l < 64; ++l)
+                    for (int j = 0; j < 8; ++j) {
+                        const int k = 8 * G + j;
+                        const float v = src[t * 2048 + ((size_t)(k / 4) * 64 + l) * 4 + k % 4];
+                        const uint16_t hi = bf16_rne(v);
+                        const float r1 = v - bf16_f32(hi);
+                        const uint16_t mid = bf16_rne(r1);
+                        const float r2 = r1 - bf16_f32(mid);
+                        uint16_t* o = dst + (t * 4 + G) * 1536 + (size_t)l * 8 + j;
+                        o[0] = hi; o[512] = mid; o[1024] = bf16_rne(r2);
+                    }
+    }
+    return JODO_OK;
+}

@@ -7,7 +7,11 @@ the same call as the reference class:
         -> (atom_pred [B,N,nd], edge_pred [B,N,N,ch])
 The arithmetic runs in libjodo_hip.so (csrc/dgt2d_forward.hip, `jodo_dgt2d_forward`) on the current HIP stream: the weights are
 packed once (csrc/dgt2d_pack.cpp), a descriptor and a workspace are built per batch of atom counts.  There is no CPU or eager
-fallback and no split-bf16 form for this model — those raise.
+fallback, and the 3-D models' `split_bf16` switch is not taken by this model — those raise.
+
+`model.bf16x3 = True` (opt-in, runtime state) selects the three-term bf16 form of the node GEMMs and of the pair update
+(`jodo_dgt2d_forward_split`, kernels k2d_gemm_s / k2d_pair_s) from a weight tape derived from the packed blob; attention, the edge
+heads and the one-row time / modulation GEMMs stay exact fp32.  `model.last_flags[3]` tells which form ran.
 
 `model.pair_attention = True` (opt-in, runtime state) selects the pair-symmetric attention walk (`jodo_dgt2d_forward_walk`, kernel
 k2d_attn_pair): with symmetric inputs every unordered pair is evaluated once; `model.last_flags[2]` tells which walk ran.
@@ -95,6 +99,7 @@ class DGT_concat_2D(nn.Module):
 
         # ---- runtime state (not part of state_dict) ----
         self._packed = None           # (version key, device blob, woff ctypes array, n_woff)
+        self._tape = None             # (the _packed it was derived from, device tape, toff ctypes array): valid for that _packed only
         self._plans = {}              # per batch of atom counts: descriptor + workspace, keyed by the mask storage (see _plan)
         self.split_bf16 = False       # the 3-D models' opt-in form; not built for this model (forward raises when set)
         self.force_directed = False   # tests: always the directed fallback
@@ -103,16 +108,36 @@ class DGT_concat_2D(nn.Module):
         self.hip_training = False     # opt-in: grad-enabled calls go through the HIP training path (csrc/dgt2d_train.hip)
         self.pair_attention = False   # opt-in: the pair-symmetric attention walk (k2d_attn_pair) when the inputs are symmetric;
                                       # last_flags[2] tells which walk ran (1 = pair, 0 = directed).  The training path ignores it.
+        self.bf16x3 = False           # opt-in, read per call: the split-bf16 (three-term) form of the node GEMMs and the pair update
+                                      # (k2d_gemm_s, k2d_pair_s); last_flags[3] tells which form ran (1 = split, 0 = exact fp32).
+                                      # Combines with pair_attention / force_directed / max_blocks.  The training path ignores it.
         self.register_load_state_dict_post_hook(_drop_packed_after_load)
 
     # -- weights (same invalidation rules as _DGTBase._weights) ------------------------------------
     def _weights(self, device):
         key = (str(device),) + tuple(p._version for p in self.parameters()) + tuple(p.data_ptr() for p in self.parameters())
         if self._packed is None or self._packed[0] != key:
-            blob, woff_c, n_woff = capi.pack_weights_2d(self._cfg_struct, self.state_dict(), device)
-            self._packed = (key, blob, woff_c, n_woff)
+            self._tape = None
+            host, woff_c, n_woff = capi.pack_weights_2d(self._cfg_struct, self.state_dict(), None)
+            self._packed = (key, host.to(device), woff_c, n_woff)
             self._packed_fingerprint = self._fingerprint()
+            if self.bf16x3:                              # the tape lives and dies with the blob it is derived from
+                self._split_tape(device, host)
         return self._packed
+
+    def _split_tape(self, device, blob_host=None):
+        """(device tape, toff) of the split-bf16 form for the current `_packed`: host conversion of the packed blob + one upload, when
+        the blob is re-packed with the switch on or on the first call with the switch on."""
+        packed, t = self._packed, self._tape
+        if t is None or t[0] is not packed:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("bf16x3 was switched on under graph capture for weights packed without it: run one eager call with "
+                                   "bf16x3 = True first")
+            if blob_host is None:
+                blob_host = packed[1].cpu()
+            tape, toff = capi.split_tape_2d(self._cfg_struct, blob_host, packed[2], packed[3], device)
+            t = self._tape = (packed, tape, toff)
+        return t[1], t[2]
 
     def _fingerprint(self):
         ps = [p.detach() for p in self.parameters()]
@@ -128,6 +153,7 @@ class DGT_concat_2D(nn.Module):
         """Drop the packed kernel weights; the next forward re-packs from the current parameters (needed after in-place `.data`
         updates that bump no tensor version, e.g. the reference's ExponentialMovingAverage.copy_to / restore)."""
         self._packed = None
+        self._tape = None
 
     # -- per-batch descriptor and workspace -----------------------------------------------------------
     def _plan(self, node_mask, edge_mask, device, validate=True):
@@ -225,18 +251,29 @@ class DGT_concat_2D(nn.Module):
         out_x = torch.empty_like(xh_)
         out_e = torch.empty_like(ex_)
         n_ptr = plan['n_nodes'].ctypes.data_as(ctypes.c_void_p)
-        tail = (capi.ptr(blob), woff_c, n_woff, capi.ptr(xh_), capi.ptr(ex_), capi.ptr(cx_), capi.ptr(cex_), capi.ptr(nl_), capi.ptr(out_x),
+        wts = (capi.ptr(blob), woff_c, n_woff)
+        tail = (capi.ptr(xh_), capi.ptr(ex_), capi.ptr(cx_), capi.ptr(cex_), capi.ptr(nl_), capi.ptr(out_x),
                 capi.ptr(out_e), capi.ptr(plan['flags']), capi.ptr(plan['ws']), int(bool(self.force_directed)), int(self.max_blocks),
                 capi.current_stream_ptr())
-        if self.pair_attention:
+        if not self.pair_attention and plan.get('walk_slot_used'):   # flags[2] still holds an earlier pair-walk call's record
+            plan['flags'][2:3].zero_()
+            plan['walk_slot_used'] = False
+        if self.bf16x3:
+            tape, toff = self._split_tape(dev)
+            pair = self.pair_attention
+            capi.check(capi.lib().jodo_dgt2d_forward_split(ctypes.byref(self._cfg_struct), B, N, n_ptr, capi.ptr(plan['desc']),
+                                                           capi.ptr(self._pair_desc(plan, dev)) if pair else None,
+                                                           capi.WALK_PAIR if pair else capi.WALK_DIRECTED, *wts, capi.ptr(tape), toff, *tail),
+                       'jodo_dgt2d_forward_split')
+            if pair:
+                plan['walk_slot_used'] = True
+        elif self.pair_attention:
             capi.check(capi.lib().jodo_dgt2d_forward_walk(ctypes.byref(self._cfg_struct), B, N, n_ptr, capi.ptr(plan['desc']),
-                                                          capi.ptr(self._pair_desc(plan, dev)), capi.WALK_PAIR, *tail), 'jodo_dgt2d_forward_walk')
+                                                          capi.ptr(self._pair_desc(plan, dev)), capi.WALK_PAIR, *wts, *tail),
+                       'jodo_dgt2d_forward_walk')
             plan['walk_slot_used'] = True
         else:
-            if plan.get('walk_slot_used'):               # flags[2] still holds an earlier pair-walk call's record
-                plan['flags'][2:3].zero_()
-                plan['walk_slot_used'] = False
-            capi.check(capi.lib().jodo_dgt2d_forward(ctypes.byref(self._cfg_struct), B, N, n_ptr, capi.ptr(plan['desc']), *tail),
+            capi.check(capi.lib().jodo_dgt2d_forward(ctypes.byref(self._cfg_struct), B, N, n_ptr, capi.ptr(plan['desc']), *wts, *tail),
                        'jodo_dgt2d_forward')
         self.last_flags = plan['flags']
         self._last_plan = plan

@@ -4,6 +4,8 @@ device, chunked by molecules to fit memory, under the same sampler.
 
     python tools/bench_2d.py --workload zinc|moses [--batch 2000] [--steps 20] [--warmup 3] [--baseline-steps 3] [--no-baseline]
                              [--walk directed|pair|both] [--kernel-stats CSV] [--out FILE]
+    python tools/bench_2d.py --workload zinc|moses --split exact|split|both [--walk directed|pair] [--kernel-stats CSV]
+                             [--kernel-stats-exact CSV] [--out profiles/dgt2d_zinc_b2000_split.json]
     python tools/bench_2d.py --workload zinc|moses --round [--steps 1000] [--batches 2000,128] [--forms a,b,c,cd] [--repeat 1]
                              [--parent-json FILE] [--out profiles/dgt2d_round_zinc.json]
     python tools/bench_2d.py --workload zinc|moses --round --nfe 50 [--dpm-method singlestep_fixed|multistep] [--batches 2000,128]
@@ -18,6 +20,13 @@ model.pair_attention (the opt-in pair-symmetric walk); `both` alternates directe
 process and reports ms/step per form with the spread of its two runs (no torch baseline).  --kernel-stats: the `rocprofv3
 --kernel-trace --stats` kernel table of the `--walk pair` command with the same --steps and --warmup (the profiler wraps the process,
 so that is a run of its own); its k2d_* rows, divided by the sampler steps of that command, become `pair_kernel_ms_per_step`.  --out writes the record.
+
+--split: the arithmetic of the node GEMMs and the pair update.  `exact` (default) changes nothing; `split` sets model.bf16x3 (the opt-in
+three-term bf16 form); `both` alternates exact, split, exact, split on the same batch in this one process, exactly as `--walk both` does
+for the attention walk, and reports ms/step per form, both exact legs and their spread (no torch baseline).  It combines with
+`--walk directed|pair` (not `both`: one comparison per command) and with `--round` (every form of the round is then run exact, split,
+exact, split).  --kernel-stats / --kernel-stats-exact: the rocprofv3 kernel tables of the `--split split` / `--split exact` command with
+the same --walk, --steps and --warmup; their k2d_* rows per sampler step become `split_kernel_ms_per_step` / `exact_kernel_ms_per_step`.
 
 --round: ONE complete sampling round of `--steps` steps per batch size and form, timed from the initial state to the last step
 (weights packed by a 3-step round before; plan creation and graph capture are inside the timed round):
@@ -94,7 +103,8 @@ def kernel_split(csv_path, sampler_steps):
     import csv
     import re
     known = (('13k2d_attn_pair', 'k2d_attn_pair'), ('k2d_attnILb1E', 'k2d_attn<true>'), ('k2d_attnILb0E', 'k2d_attn<false>'),
-             ('k2d_gemmILi4ELi2E', 'k2d_gemm<4,2>'), ('k2d_gemmILi1ELi1E', 'k2d_gemm<1,1>'))
+             ('k2d_gemmILi4ELi2E', 'k2d_gemm<4,2>'), ('k2d_gemmILi1ELi1E', 'k2d_gemm<1,1>'), ('k2d_gemm_sILi4ELi2E', 'k2d_gemm_s<4,2>'),
+             ('k2d_gemm_sILi2ELi2E', 'k2d_gemm_s<2,2>'), ('k2d_gemm_sILi1ELi2E', 'k2d_gemm_s<1,2>'), ('10k2d_pair_s', 'k2d_pair_s'))
     out = {}
     with open(csv_path) as f:
         for row in csv.DictReader(f):
@@ -130,6 +140,33 @@ def walk_leg(args, model, sampler, z, edge_z, node_mask, edge_mask, out):
         gain = out['directed']['ms_per_step'] - out['pair']['ms_per_step']
         out['pair_gain_ms_per_step'] = round(gain, 4)
         out['pair_faster_beyond_directed_spread'] = bool(gain > out['directed']['spread_ms_per_step'])
+        out['step_sampler_calls'] = len(order) * (args.warmup + args.steps)
+    return out
+
+
+def split_leg(args, model, sampler, z, edge_z, node_mask, edge_mask, out):
+    """--split both: exact, split, exact, split on the same batch; --split split: the split form alone.  --walk picks the attention walk
+    of every leg."""
+    order = ['exact', 'split', 'exact', 'split'] if args.split == 'both' else ['split']
+    runs = {w: [] for w in order}
+    ran = {}
+    model.pair_attention = (args.walk == 'pair')
+    for w in order:
+        model.bf16x3 = (w == 'split')
+        ms, st = time_steps(sampler, model, z, edge_z, node_mask, edge_mask, args.warmup, args.steps)
+        runs[w].append(round(ms, 4))
+        ran[w] = dict(split_form_ran=int(model.last_flags[3].item()), pair_walk_ran=int(model.last_flags[2].item()))
+        out['finite'] = out.get('finite', True) and bool(torch.isfinite(st['x']).all() and torch.isfinite(st['edge_x']).all())
+    model.bf16x3 = model.pair_attention = False
+    out['split'] = args.split
+    out['walk'] = args.walk
+    out['order_of_runs'] = order
+    for w, r in runs.items():
+        out[w] = dict(runs_ms_per_step=r, ms_per_step=round(sum(r) / len(r), 4), spread_ms_per_step=round(max(r) - min(r), 4), **ran[w])
+    if args.split == 'both':
+        gain = out['exact']['ms_per_step'] - out['split']['ms_per_step']
+        out['split_gain_ms_per_step'] = round(gain, 4)
+        out['split_faster_beyond_exact_spread'] = bool(gain > out['exact']['spread_ms_per_step'])
         out['step_sampler_calls'] = len(order) * (args.warmup + args.steps)
     return out
 
@@ -207,7 +244,7 @@ def round_leg(args):
     dev = torch.device('cuda:0')
     cfg_name, _ = WORKLOADS[args.workload]
     model = deterministic_init_(get_model_class('DGT_concat_2D')(configs.get(cfg_name)), seed=7).to(dev).eval()
-    out = dict(workload=args.workload, config=cfg_name, steps=args.steps, forms={
+    out = dict(workload=args.workload, config=cfg_name, steps=args.steps, split=args.split, walk=args.walk, forms={
         'a': 'eager, torch draws', 'b': 'eager, in-kernel draws', 'c': 'graph replay, in-kernel draws', 'cd': 'c + device decode',
         'd': "DPM-Solver++ 'dpm_2d', eager", 'dg': "DPM-Solver++ 'dpm_2d', graph replay"}, batches={})
     if args.nfe is not None:
@@ -219,20 +256,40 @@ def round_leg(args):
         _one_round('a', cfg, model, ns, 3, n_nodes, node_mask, edge_mask, z, edge_z)           # packs the weights, loads the kernels
         cfg.sampling['dpm_solver_method'], cfg.sampling['dpm_solver_order'] = args.dpm_method, 2
         rec = {}
+        model.pair_attention = (args.walk == 'pair')
         for form in args.forms.split(','):
-            runs = []
             is_dpm = form in ('d', 'dg')
             if is_dpm and args.nfe is None:
                 raise SystemExit("forms d / dg need --nfe")
             count = dpm_evaluations(args.dpm_method, args.nfe) if is_dpm else args.steps       # network evaluations of the round
-            for _ in range(args.repeat):
+
+            def one(tag):
                 loop, dec, finite = _one_round(form, cfg, model, ns, args.nfe if is_dpm else args.steps, n_nodes, node_mask, edge_mask, z, edge_z)
                 total = loop + (dec or 0.0)
-                runs.append(dict(ms_per_step=round(loop / count * 1e3, 4), round_s=round(loop, 3),
-                                 decode_ms=None if dec is None else round(dec * 1e3, 2), molecules_per_s=round(batch / total, 2), finite=finite))
-                print(json.dumps(dict(batch=batch, form=form, **runs[-1])), flush=True)
-            rec[form] = runs[0] if args.repeat == 1 else dict(runs=runs, ms_per_step=round(sum(r['ms_per_step'] for r in runs) / len(runs), 4),
-                                                               spread_ms_per_step=round(max(r['ms_per_step'] for r in runs) - min(r['ms_per_step'] for r in runs), 4))
+                r = dict(ms_per_step=round(loop / count * 1e3, 4), round_s=round(loop, 3),
+                         decode_ms=None if dec is None else round(dec * 1e3, 2), molecules_per_s=round(batch / total, 2), finite=finite)
+                print(json.dumps(dict(batch=batch, form=form, **tag, **r)), flush=True)
+                return r
+
+            def summary(runs):
+                return dict(runs=runs, ms_per_step=round(sum(r['ms_per_step'] for r in runs) / len(runs), 4),
+                            spread_ms_per_step=round(max(r['ms_per_step'] for r in runs) - min(r['ms_per_step'] for r in runs), 4))
+            if args.split == 'exact':
+                runs = [one({}) for _ in range(args.repeat)]
+                rec[form] = runs[0] if args.repeat == 1 else summary(runs)
+                continue
+            order = ['exact', 'split', 'exact', 'split'] if args.split == 'both' else ['split']
+            legs = {w: [] for w in order}
+            for w in order * args.repeat:
+                model.bf16x3 = (w == 'split')
+                legs[w].append(dict(one(dict(split=w)), split_form_ran=int(model.last_flags[3].item())))
+            model.bf16x3 = False
+            rec[form] = dict(order_of_runs=order * args.repeat, **{w: summary(r) for w, r in legs.items()})
+            if args.split == 'both':
+                gain = rec[form]['exact']['ms_per_step'] - rec[form]['split']['ms_per_step']
+                rec[form].update(split_gain_ms_per_step=round(gain, 4),
+                                 split_faster_beyond_exact_spread=bool(gain > rec[form]['exact']['spread_ms_per_step']))
+        model.pair_attention = False
         if 'a' in rec and 'c' in rec:
             rec['c_over_a'] = round(rec['c']['ms_per_step'] / rec['a']['ms_per_step'], 4)
         out['batches'][str(batch)] = dict(max_n=max(n_nodes), atoms=sum(n_nodes), **rec)
@@ -266,7 +323,14 @@ def main():
     ap.add_argument('--no-baseline', action='store_true')
     ap.add_argument('--walk', choices=('directed', 'pair', 'both'), default='directed', help='attention walk of the score network')
     ap.add_argument('--kernel-stats', default=None, help='rocprofv3 kernel-stats CSV of a run of the same command line')
+    ap.add_argument('--split', choices=('exact', 'split', 'both'), default='exact',
+                    help='arithmetic of the node GEMMs and the pair update: exact fp32 (default), the opt-in split-bf16 form (model.bf16x3), or both alternated')
+    ap.add_argument('--kernel-stats-exact', default=None, help='--split: rocprofv3 kernel-stats CSV of the --split exact run of the same command line')
     args = ap.parse_args()
+    if args.split != 'exact' and args.walk == 'both':
+        ap.error('--split %s goes with --walk directed or --walk pair: one comparison per command' % args.split)
+    if args.round and args.walk == 'both':
+        ap.error('--round goes with --walk directed or --walk pair')
     if args.steps is None:
         args.steps = 1000 if args.round else 20
     if args.forms is None:
@@ -290,6 +354,20 @@ def main():
     ns = NoiseScheduleVP(cfg.sde.schedule, continuous_beta_0=cfg.sde.continuous_beta_0, continuous_beta_1=cfg.sde.continuous_beta_1)
     sampler = AncestralSampler_2D(ns, torch.linspace(ns.T, 1e-3, 1000), True, True)
     directed = sum(n * (n - 1) for n in n_nodes)
+    if args.split != 'exact':
+        out = dict(workload=args.workload, config=cfg_name, batch=B, max_n=N, atoms=sum(n_nodes), directed_edges=directed, steps=args.steps,
+                   warmup=args.warmup)
+        split_leg(args, model, sampler, z, edge_z, node_mask, edge_mask, out)
+        for key, path in (('split', args.kernel_stats), ('exact', args.kernel_stats_exact)):
+            if path:
+                out[key + '_kernel_ms_per_step'] = kernel_split(path, args.warmup + args.steps)
+                out[key + '_kernel_stats'] = path + ' (rocprofv3 --kernel-trace --stats of the --split %s command, same walk, steps and warm-up)' % key
+        print(json.dumps(out))
+        if args.out:
+            with open(args.out, 'w') as f:
+                json.dump(out, f, indent=1)
+                f.write('\n')
+        return
     if args.walk != 'directed':
         out = dict(workload=args.workload, config=cfg_name, batch=B, max_n=N, atoms=sum(n_nodes), directed_edges=directed, steps=args.steps,
                    warmup=args.warmup)
