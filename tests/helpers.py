@@ -255,6 +255,43 @@ def check_decodes(cfg, fx, x_mean, e_mean, nm, em, margin=1e-3):
     assert np.abs(pos.numpy() - fx['pos']).max() < 1e-4
 
 
+# ---- the gradient rule of the 3-D training tests (tests/test_train_gpu.py, test_train_scale_gpu.py, test_train_emul.py) ------------
+def oracle_param_grads(model, hp, xh, nm, em, ex, cx, cex, nl, ctx, d_x, d_e, dtype=torch.float64):
+    """(pred, edge_pred, {name: d <d_out, outputs> / d parameter}) by autograd through oracle.forward_dense on the CPU."""
+    sd = {k: v.detach().cpu().to(dtype).clone().requires_grad_(True) for k, v in model.state_dict().items()}
+    c = lambda t: None if t is None else t.detach().cpu().to(dtype)
+    px, pe = O.forward_dense(sd, hp, c(xh), c(nm), c(em), c(ex), c(cx), c(cex), c(nl), c(ctx))
+    ((px * c(d_x)).sum() + (pe * c(d_e)).sum()).backward()
+    return px.detach(), pe.detach(), {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in sd.items()}
+
+
+def compare_grads(named_grads, want, rel_tol, want32=None, k32=16.0, what=''):
+    """Every parameter's gradient against float64 autograd through the oracle: |got - want| <= rel_tol x max |want|, widened to
+    k32 x the distance of FLOAT32 autograd through the same oracle from float64 where that is larger (the yardstick of the forward
+    tests, close64: a deep fp32 backward cannot be closer to float64 than fp32 arithmetic itself).  k32 = 16: measured worst
+    12 x, on the Gaussian-layer parameters of the first block at trunk gain 1.5 (GEOM nf 128 / 6 blocks), where float32 autograd
+    itself is 1.4e-3 relative: those gradients amplify forward rounding ~1e4 times, and the kernels' forward is 1.6e-6 from float64
+    where torch's CPU float32 is 6e-7.  On the reference's own training step (default initialisation) every
+    recorded gradient is within 2e-4 (test_loss_backward_on_the_module_reproduces_the_reference_gradients).
+    Returns (worst err / bound over the tensors, names of the tensors on which the widening is the active bound)."""
+    bad, worst, ratio, widened = [], 0.0, 0.0, []
+    for k, g in named_grads:
+        w = want[k].double()
+        scale, err = float(w.abs().max()), float((g.detach().cpu().double() - w).abs().max())
+        e32 = float((want32[k].double() - w).abs().max()) if want32 is not None else 0.0
+        base = rel_tol * max(scale, 1e-12)
+        bound = max(base, k32 * e32)
+        worst = max(worst, err / max(scale, 1e-12))
+        ratio = max(ratio, err / bound)
+        if k32 * e32 > base:
+            widened.append(k)
+        if not err <= bound + 1e-12:
+            bad.append("%s: err %.3e scale %.3e (float32 autograd %.3e)" % (k, err, scale, e32))
+    print("%sworst relative gradient error %.2e, worst err / bound %.4f, widened bounds active on %d tensors" % (what and what + ': ', worst, ratio, len(widened)))
+    assert not bad, "%d parameter gradients differ:\n  %s" % (len(bad), "\n  ".join(bad[:40]))
+    return ratio, widened
+
+
 def grad_fixture_batch(cfg, n_nodes, seed):
     """The synthetic training batch of oracle/make_golden.py grad_fixture (same generator calls, same order) and the python-random
     seed whose first draw takes the self-conditioning branch of losses.py:335 — what the reference's loss_fn was given when

@@ -94,7 +94,7 @@ def test_training_step_reproduces_the_reference_backward(emul, which):
     C.compare_grads(zip(names, grads), want, want32=want32, what='grad2d_%s' % which)
 
 
-@pytest.mark.parametrize('which,selfcond', [('zinc', False), ('zinc', True), ('moses', False), ('moses', True)])
+@pytest.mark.parametrize('which,selfcond', [('zinc', False), ('zinc', True), ('moses', False), ('moses', True), ('zinc_chunks', False), ('zinc_chunks', True)])
 def test_all_parameter_gradients_match_autograd_through_the_oracle(emul, which, selfcond):
     """(b) First-step call (no conditioning input: all-ones adjacency head) and self-conditioned call, all 235 gradients."""
     c, sd, (px, pe, want), (_, _, want32) = C.random_case_yardsticks(which, selfcond)

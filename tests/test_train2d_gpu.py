@@ -149,7 +149,7 @@ def test_recorded_moses_step_through_the_engine():
     C.compare_grads(zip(names, grads), want, want32=want32, what='grad2d_moses')
 
 
-@pytest.mark.parametrize('which,selfcond', [('zinc', False), ('zinc', True), ('moses', False), ('moses', True)])
+@pytest.mark.parametrize('which,selfcond', [('zinc', False), ('zinc', True), ('moses', False), ('moses', True), ('zinc_chunks', False), ('zinc_chunks', True)])
 def test_all_parameter_gradients_match_autograd_through_the_oracle(which, selfcond):
     """(b) First-step and self-conditioned call through the module (eval mode: no dropout), all 235 gradients; a no-grad call of the
     same module in eval mode goes to the inference kernels and agrees."""

@@ -109,6 +109,42 @@ def test_all_parameter_gradients_match_autograd_through_the_oracle(emul, cfg_nam
     compare_all(names, grads, want, 3e-4)
 
 
+# ---- the batch sizes at which the backward's reductions change form (tests/train_scale_common.py) ---------------------
+@pytest.mark.parametrize("case,passes", [
+    ('ABOVE_64K', (None, 3, 0)),        # R = 67 663: second-level chunk 34, the Gaussian layer's colsum in two levels; bulk | last | first molecule
+    ('CHUNK_EDGES', (None,)),           # per-molecule edge chunks of 34 | 32 | 64 rows
+    ('GBF_BY_SIZE', (3,)),              # R = 131 044: both colsum levels behind 4 096 chunk rows; the last molecule alone
+])
+def test_size_selected_reductions_match_autograd_through_the_oracle(emul, case, passes):
+    """The colsum levels, the FinJob queue and the per-molecule chunk tables of csrc/dgt_train.hip, run on the host from the same source,
+    against float64 autograd through the oracle by the gradient rule (3e-4 of the tensor's scale, widened to 16 x the float32-autograd
+    distance).  One forward serves every pass.  Passes confined to one molecule: train_scale_common.UNWIDENED says what they assert of the
+    widened bounds.  tests/test_train_scale_gpu.py repeats the cases on the device."""
+    import time
+    import train_scale_common as S
+    from helpers import compare_grads
+    n_nodes = getattr(S, case)
+    xh, ex, nl, nm, em, _, _ = S.batch(n_nodes)
+    t0 = time.time()
+    eng, names, params = S.make_engine(n_nodes, 'cpu', lib=emul)
+    out_x, out_e = eng.forward(params, xh, ex, None, None, nl, None, 0.0, 0)
+    assert eng.flags.tolist()[0] == 0 and eng.flags.tolist()[3] == 0
+    t_eng = time.time() - t0
+    for local in passes:
+        d_x, d_e = S.out_grads(n_nodes, local)
+        t0 = time.time()
+        grads = eng.backward(params, nl, d_x, d_e, 0.0, 0)
+        t_eng += time.time() - t0
+        px, pe, want = S.yardstick(n_nodes, local)
+        want32 = S.yardstick(n_nodes, local, torch.float32)[2]
+        assert (out_x.double() - px).abs().max() < 2e-5 and (out_e.double() - pe).abs().max() < 2e-5
+        S.assert_reduced_nonzero(want, '%s pass %s' % (case, local))
+        what = '%s, output gradient on %s' % (case, 'every molecule' if local is None else 'molecule %d' % local)
+        ratio, widened = compare_grads(zip(names, grads), want, S.GRAD_REL, want32, S.K32, what=what)
+        S.check_widening(n_nodes, local, widened, what)
+    print('%s: forward + %d backwards through the emulation build %.1f s' % (case, len(passes), t_eng))
+
+
 def test_dropout_masks_are_shared_by_forward_and_backward(emul):
     """With dropout on, the backward must differentiate the function the forward evaluated: directional finite differences of
     <d_out, forward(theta + eps v)> at a fixed seed against <grads, v>; another seed gives another function; p = 0 is the eval path."""

@@ -8,7 +8,8 @@ import torch
 from oracle import dgt_oracle as O
 from oracle import train_ref as T
 
-from helpers import load_fixture, make_config, make_model, masks
+from helpers import compare_grads, load_fixture, make_config, make_model, masks
+from helpers import oracle_param_grads as _oracle_param_grads
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -61,32 +62,9 @@ def test_train_gemm_matches_float64(tA, tB, M, N, K, acc, bias, pad):
     close(got[:, :N], want, atol=2e-6 * (K ** 0.5) * 4, rtol=2e-5)
 
 
-def _oracle_param_grads(model, hp, xh, nm, em, ex, cx, cex, nl, ctx, d_x, d_e, dtype=torch.float64):
-    sd = {k: v.detach().cpu().to(dtype).clone().requires_grad_(True) for k, v in model.state_dict().items()}
-    c = lambda t: None if t is None else t.detach().cpu().to(dtype)
-    px, pe = O.forward_dense(sd, hp, c(xh), c(nm), c(em), c(ex), c(cx), c(cex), c(nl), c(ctx))
-    ((px * c(d_x)).sum() + (pe * c(d_e)).sum()).backward()
-    return px.detach(), pe.detach(), {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in sd.items()}
-
-
 def _compare_grads(model, want, rel_tol, want32=None, k32=16.0):
-    """Every parameter's gradient against float64 autograd through the oracle: |got - want| <= rel_tol x max |want|, widened to
-    k32 x the distance of FLOAT32 autograd through the same oracle from float64 where that is larger (the yardstick of the forward
-    tests, helpers.close64: a deep fp32 backward cannot be closer to float64 than fp32 arithmetic itself).  k32 = 16: measured worst
-    12 x, on the Gaussian-layer parameters of the first block at trunk gain 1.5 (GEOM nf 128 / 6 blocks), where float32 autograd
-    itself is 1.4e-3 relative: those gradients amplify forward rounding ~1e4 times, and the kernels' forward is 1.6e-6 from float64
-    where torch's CPU float32 is 6e-7.  On the reference's own training step (default initialisation) every
-    recorded gradient is within 2e-4 (test_loss_backward_on_the_module_reproduces_the_reference_gradients)."""
-    bad, worst = [], 0.0
-    for k, p in model.named_parameters():
-        w = want[k]
-        scale, err = float(w.abs().max()), float((p.grad.detach().cpu().double() - w).abs().max())
-        e32 = float((want32[k].double() - w).abs().max()) if want32 is not None else 0.0
-        worst = max(worst, err / max(scale, 1e-12))
-        if not err <= max(rel_tol * max(scale, 1e-12), k32 * e32) + 1e-12:
-            bad.append("%s: err %.3e scale %.3e (float32 autograd %.3e)" % (k, err, scale, e32))
-    print("worst relative gradient error %.2e" % worst)
-    assert not bad, "%d parameter gradients differ:\n  %s" % (len(bad), "\n  ".join(bad[:40]))
+    """The gradient rule (helpers.compare_grads) on a module's .grad fields."""
+    return compare_grads([(k, p.grad) for k, p in model.named_parameters()], want, rel_tol, want32, k32)
 
 
 def test_loss_backward_on_the_module_reproduces_the_reference_gradients():

@@ -6,6 +6,11 @@ Shapes — the smallest at which the training kernels can go wrong:
                            boundary, sum n^2 = 2 628 (no multiple of 32), several molecules with different modulation rows inside one
                            32-row strip, n = 33 (more than one 32-source chunk), n = 38 (the config's maximum)
   MOSES (nd = 7, ch = 3)   n_nodes = [2, 5, 27]
+  ZINC model, chunk edges  n_nodes = [46, 45, 64, 1] ('zinc_chunks'): the per-molecule edge chunks of the two-level sums are
+                           max(32, ceil(n^2 / 64)) rows long (dgt2d_train.hip jodo_train2d_create) — 34 rows for n = 46 (n^2 = 2 116, the
+                           last chunk 8 rows), 32 for n = 45 (2 025, the last one 9), 64 for n = 64 (the widest molecule the engine
+                           and the inference kernels take), one row for n = 1.  Beyond the config's own maximum of 38 atoms, where no
+                           chunk is longer than 32 rows
 Per-molecule noise levels throughout; trunk gain 1.5 and the fixtures' head gain so that no gradient vanishes.
 
 Tolerances are the project's own: forward 2e-5 + 1e-4 |x| (the 2-D suite's fwd_close); recorded reference gradients 2e-4 relative;
@@ -19,8 +24,8 @@ import oracle2d as O2
 import oracle2d_train as O2T
 from helpers import make_config, make_model, masks
 
-CFG = {'zinc': 'vpsde_zinc_2d_jodo', 'moses': 'vpsde_moses_2d_jodo'}
-TRAIN_NODES = {'zinc': [1, 2, 3, 9, 33, 38], 'moses': [2, 5, 27]}
+CFG = {'zinc': 'vpsde_zinc_2d_jodo', 'moses': 'vpsde_moses_2d_jodo', 'zinc_chunks': 'vpsde_zinc_2d_jodo'}
+TRAIN_NODES = {'zinc': [1, 2, 3, 9, 33, 38], 'moses': [2, 5, 27], 'zinc_chunks': [46, 45, 64, 1]}
 GAIN, HEAD_GAIN = 1.5, 8.0
 ATOL, RTOL = 2e-5, 1e-4
 GRAD_REL, GRAD_REF_REL, K32 = 3e-4, 2e-4, 16.0
