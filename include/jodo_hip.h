@@ -571,6 +571,45 @@ int jodo_train2d_backward(jodo_train2d* t, const void* desc_dev, const float* co
                           const float* noise_level, const float* d_out_xh, const float* d_out_edge, float dropout_p, uint64_t seed,
                           void* workspace, void* stream);
 
+/* ---- property classifier: the masked EGNN of the conditional evaluation (cond_gen/model.py: EGNN / E_GCL_mask) ---------------------
+ * One float per molecule from atom features h0 [B,N,in_node_nf] and positions x [B,N,3]; positions are never updated, the radial
+ * |x_i - x_j|^2 is the same in every layer.  Stateless like the 2-D section: explicit stream, caller-owned memory.  Exact fp32 on
+ * v_mfma_f32_32x32x2_f32 (csrc/egnn_forward.hip): real atoms compact at noff_b + i, prefix masks, no scatter, no atomics, the per-edge
+ * message never reaches memory.  Supported: hidden_nf a multiple of 64 in [64, 256], n_layers 1..16, in_node_nf 1..16, attention and
+ * node_attr 0 / 1, SiLU, no edge attributes, padded width N <= 255; anything else -> JODO_ERR_UNSUPPORTED naming the setting.
+ * The state_dict (80 tensors at 7 layers with attention) is packed by name (a leading "module." is accepted; a missing or mis-sized
+ * tensor is JODO_ERR_ARG with its name in jodo_last_error()).  Slot tables: offsets in floats into the packed blob; the table holds
+ * JE_GLOBAL_COUNT global slots, then JEL_LAYER_COUNT per layer.  "Tiled" weights as in the 2-D section.
+ *   JEL_P_W: edge_mlp.0 hoisted to the nodes, rows [W_src ; W_tgt] (2 nf x nf), JEL_P_B = [b1 ; 0]; JEL_WR = its radial column;
+ *   JEL_N0_W: node_mlp.0 over [h | agg (| h0)], K = 2 nf (+ in_node_nf with node_attr, zero-padded to a K chunk). */
+typedef struct {
+    int32_t hidden_nf, n_layers, in_node_nf, attention, node_attr;
+} jodo_egnn_cfg;
+enum jodo_egnn_wslot_global {
+    JE_EMB_W = 0, JE_EMB_B, JE_ND0_W, JE_ND0_B, JE_ND2_W, JE_ND2_B, JE_GD0_W, JE_GD0_B, JE_GD2_W, JE_GD2_B,
+    JE_GLOBAL_COUNT
+};
+enum jodo_egnn_wslot_layer {
+    JEL_P_W = 0, JEL_P_B, JEL_WR, JEL_W2, JEL_B2, JEL_ATT_W, JEL_ATT_B, JEL_N0_W, JEL_N0_B, JEL_N2_W, JEL_N2_B,
+    JEL_LAYER_COUNT
+};
+/* JODO_OK, or JODO_ERR_UNSUPPORTED naming the setting outside the supported set */
+int jodo_egnn_check_cfg(const jodo_egnn_cfg* cfg);
+int jodo_egnn_packed_size(const jodo_egnn_cfg* cfg, size_t* n_floats, int* n_woff);
+int jodo_egnn_pack_weights_host(const jodo_egnn_cfg* cfg, const jodo_tensor* tensors, int n_tensors, float* packed_host,
+                                size_t cap_floats, int64_t* woff_out, int n_woff);
+/* jodo_egnn_layout: out[0] = int32 words of the descriptor, out[1] = workspace bytes, out[2] = real atoms Nn, out[3] = byte offset of
+ * the hidden state h [Nn, hidden_nf] in the workspace (molecule b's atom i in row noff_b + i), out[4..7] = reserved (0).
+ * jodo_egnn_fill_desc writes the descriptor into HOST memory: n_b [B], noff_b [B], then (b << 8) | i per real atom; the caller
+ * copies it to the device. */
+int jodo_egnn_layout(const jodo_egnn_cfg* cfg, int B, int N, const int32_t* n_nodes_host, int64_t* out8);
+int jodo_egnn_fill_desc(const jodo_egnn_cfg* cfg, int B, int N, const int32_t* n_nodes_host, int32_t* desc_host, int64_t n_words);
+/* One evaluation: out [B].  max_layers < 0: all layers and the readout.  max_layers >= 0 (tests): stops after that many layers, leaves
+ * h in the workspace (out8[3] of jodo_egnn_layout) and does not write `out`. */
+int jodo_egnn_forward(const jodo_egnn_cfg* cfg, int B, int N, const int32_t* n_nodes_host, const void* desc_dev, const float* packed_w,
+                      const int64_t* woff, int n_woff, const float* h0, const float* x, float* out, void* workspace, int max_layers,
+                      void* stream);
+
 const char* jodo_last_error(void);
 
 /* measurement helper (synchronises, default stream): fp32 MFMA throughput of the box in TFLOP/s from a

@@ -573,13 +573,11 @@ def full_edge_index(n_nodes, batch_size, device):
     return [rows.reshape(-1), cols.reshape(-1)]
 
 
-def get_cond_sampling_eval_fn(config, noise_scheduler, nodes_dist, batch_size, n_samples, inverse_scaler, eps=1e-3,
-                              prop_dist=None, prop_norm=None):
-    """sampling.py:283-392: conditional sampling scored by a property classifier.  Returns sampling_fn(model, classifier) ->
-    (molecules[:n_samples], mean |classifier(sample) - target| * outputNorm[cond_property]) like the reference; the classifier is the
-    caller's (the reference's pretrained EGNN, cond_gen/ — out of this path's scope) and is called with the reference's keywords
-    (h0, x, edges, edge_attr, node_mask, edge_mask, n_nodes).  The score network runs through the HIP kernels as in get_sampling_fn;
-    the round's RNG use (atom counts, context, initial noise, per-step draws) is the reference's."""
+def _cond_eval_rounds(config, noise_scheduler, nodes_dist, batch_size, n_samples, inverse_scaler, eps, prop_dist, model, classifiers,
+                      check_context):
+    """The rounds shared by get_cond_sampling_eval_fn and get_cond_multi_sampling_eval_fn (sampling.py:307-389 / :420-514): atom
+    counts, context, masks, initial noise, ancestral sampling, decode, then every classifier on the decoded (one-hot atoms, positions)
+    with the reference's keywords.  Returns (molecules, contexts per round, per classifier the predictions per round)."""
     device = config.device
     steps = config.sampling.steps
     atom_types = config.data.atom_types
@@ -587,53 +585,104 @@ def get_cond_sampling_eval_fn(config, noise_scheduler, nodes_dist, batch_size, n
     node_nf = atom_types + int(include_fc)
     edge_nf = config.model.edge_ch
     compress_edge = config.data.compress_edge
-    if config.only_2D or not config.pred_edge:
-        raise NotImplementedError("only the 3-D + edge (vpsde_edge) sampling path is in scope")
-    if config.sampling.method != 'ancestral':
-        raise ValueError('Invalid sampling method!')                  # sampling.py:305
-    prop = config.cond_property
-    mean, mad = prop_norm[prop]['mean'], prop_norm[prop]['mad']
-    output_norm = {'mu': 1., 'alpha': 1, 'homo': 1000., 'lumo': 1000., 'gap': 1000, 'Cv': 1.}
     rounds = int(np.ceil(n_samples / batch_size))
     time_steps = torch.linspace(noise_scheduler.T, eps, steps)
     sampler = AncestralSampler(noise_scheduler, time_steps, config.model.pred_data, config.pred_edge, config.model.self_cond,
                                get_self_cond_fn(config))
+    model.eval()
+    for classifier in classifiers:
+        classifier.eval()
+    mols, contexts, preds = [], [], [[] for _ in classifiers]
+    with torch.no_grad():
+        n_nodes_all = nodes_dist.sample(rounds * batch_size)
+        for r in range(rounds):
+            n_nodes = n_nodes_all[r * batch_size:(r + 1) * batch_size]
+            max_n = int(max(n_nodes))
+            context = prop_dist.sample_batch(n_nodes).to(device) if prop_dist is not None else None
+            check_context(context)
+            node_mask, edge_mask = build_masks(n_nodes, max_n, device)
+            z = sample_combined_position_feature_noise(batch_size, max_n, node_nf, node_mask)
+            assert_mean_zero_with_mask(z[:, :, :3], node_mask)
+            edge_z = sample_symmetric_edge_feature_noise(batch_size, max_n, edge_nf, edge_mask)
+            try:
+                x_node, x_edge = sampler.sampling(model, z, node_mask, edge_mask, edge_z, context)
+            finally:
+                unpin = model_hook(model, 'unpin_paths')
+                if unpin is not None:
+                    unpin()
+            _warn_nan(model)
+            pos, one_hot, fc, edge_types = post_process(x_node, atom_types, include_fc, node_mask, inverse_scaler, x_edge,
+                                                        edge_mask, compress_edge)
+            assert_mean_zero_with_mask(pos, node_mask)
+            bs, b_node, _ = pos.size()
+            edges = full_edge_index(b_node, batch_size, device)
+            for k, classifier in enumerate(classifiers):
+                preds[k].append(classifier(h0=one_hot.reshape(bs * b_node, -1), x=pos.reshape(bs * b_node, -1), edges=edges,
+                                           edge_attr=None, node_mask=node_mask.reshape(bs * b_node, -1), edge_mask=edge_mask,
+                                           n_nodes=b_node))
+            contexts.append(context)
+            mols += mol_process(one_hot, pos, fc, n_nodes, edge_types)
+            print('Generate {}, Total {}.'.format(len(mols), n_samples))
+    return mols, contexts, preds
+
+
+_OUTPUT_NORM = {'mu': 1., 'alpha': 1, 'homo': 1000., 'lumo': 1000., 'gap': 1000, 'Cv': 1.}
+
+
+def _check_cond_eval_config(config):
+    if config.only_2D or not config.pred_edge:
+        raise NotImplementedError("only the 3-D + edge (vpsde_edge) sampling path is in scope")
+    if config.sampling.method != 'ancestral':
+        raise ValueError('Invalid sampling method!')                  # sampling.py:305
+
+
+def get_cond_sampling_eval_fn(config, noise_scheduler, nodes_dist, batch_size, n_samples, inverse_scaler, eps=1e-3,
+                              prop_dist=None, prop_norm=None):
+    """sampling.py:283-392: conditional sampling scored by a property classifier.  Returns sampling_fn(model, classifier) ->
+    (molecules[:n_samples], mean |classifier(sample) - target| * outputNorm[cond_property]) like the reference; the classifier
+    (jodo_amd.cond_gen.EGNN, the reference's pretrained EGNN on the HIP kernels, or any module with its call) is called with the
+    reference's keywords (h0, x, edges, edge_attr, node_mask, edge_mask, n_nodes).  The score network runs through the HIP kernels as in
+    get_sampling_fn; the round's RNG use (atom counts, context, initial noise, per-step draws) is the reference's."""
+    _check_cond_eval_config(config)
+    prop = config.cond_property
+    mean, mad = prop_norm[prop]['mean'], prop_norm[prop]['mad']
+
+    def one_column(context):
+        assert context.size(-1) == 1
 
     def sampling_fn(model, classifier):
-        model.eval()
-        classifier.eval()
-        mols, maes = [], []
-        with torch.no_grad():
-            n_nodes_all = nodes_dist.sample(rounds * batch_size)
-            for r in range(rounds):
-                n_nodes = n_nodes_all[r * batch_size:(r + 1) * batch_size]
-                max_n = int(max(n_nodes))
-                context = prop_dist.sample_batch(n_nodes).to(device) if prop_dist is not None else None
-                node_mask, edge_mask = build_masks(n_nodes, max_n, device)
-                z = sample_combined_position_feature_noise(batch_size, max_n, node_nf, node_mask)
-                assert_mean_zero_with_mask(z[:, :, :3], node_mask)
-                edge_z = sample_symmetric_edge_feature_noise(batch_size, max_n, edge_nf, edge_mask)
-                try:
-                    x_node, x_edge = sampler.sampling(model, z, node_mask, edge_mask, edge_z, context)
-                finally:
-                    unpin = model_hook(model, 'unpin_paths')
-                    if unpin is not None:
-                        unpin()
-                _warn_nan(model)
-                pos, one_hot, fc, edge_types = post_process(x_node, atom_types, include_fc, node_mask, inverse_scaler, x_edge,
-                                                            edge_mask, compress_edge)
-                assert_mean_zero_with_mask(pos, node_mask)
-                bs, b_node, _ = pos.size()
-                pred = classifier(h0=one_hot.reshape(bs * b_node, -1), x=pos.reshape(bs * b_node, -1),
-                                  edges=full_edge_index(b_node, batch_size, device), edge_attr=None,
-                                  node_mask=node_mask.reshape(bs * b_node, -1), edge_mask=edge_mask, n_nodes=b_node)
-                assert context.size(-1) == 1
-                target = context.clone().squeeze(-1) * mad + mean
-                maes.append((pred * mad + mean - target).abs())
-                mols += mol_process(one_hot, pos, fc, n_nodes, edge_types)
-                print('Generate {}, Total {}.'.format(len(mols), n_samples))
+        mols, contexts, (preds,) = _cond_eval_rounds(config, noise_scheduler, nodes_dist, batch_size, n_samples, inverse_scaler, eps,
+                                                     prop_dist, model, [classifier], one_column)
+        maes = [(pred * mad + mean - (context.clone().squeeze(-1) * mad + mean)).abs() for pred, context in zip(preds, contexts)]
         mae = torch.cat(maes)[:n_samples]
-        return mols[:n_samples], mae.mean().item() * output_norm[prop]
+        return mols[:n_samples], mae.mean().item() * _OUTPUT_NORM[prop]
+
+    return sampling_fn
+
+
+def get_cond_multi_sampling_eval_fn(config, noise_scheduler, nodes_dist, batch_size, n_samples, inverse_scaler, eps=1e-3,
+                                    prop_dist=None, prop_norm=None):
+    """sampling.py:394-516: conditional sampling on two properties, each scored by its own classifier.  Column k of the context is
+    property k (config.cond_property1, config.cond_property2).  Returns sampling_fn(model, classifier1, classifier2) ->
+    (molecules[:n_samples], mae1 * outputNorm[property 1], mae2 * outputNorm[property 2]); rounds, RNG use, masks and classifier
+    keywords are those of get_cond_sampling_eval_fn."""
+    _check_cond_eval_config(config)
+    props = (config.cond_property1, config.cond_property2)
+    stats = [(prop_norm[p]['mean'], prop_norm[p]['mad']) for p in props]
+
+    def two_columns(context):
+        if context is None or context.dim() != 2 or context.size(-1) != 2:
+            raise ValueError("get_cond_multi_sampling_eval_fn needs a two-column context [B, 2] (one column per property), got %s"
+                             % (None if context is None else tuple(context.shape),))
+
+    def sampling_fn(model, classifier1, classifier2):
+        mols, contexts, preds = _cond_eval_rounds(config, noise_scheduler, nodes_dist, batch_size, n_samples, inverse_scaler, eps,
+                                                  prop_dist, model, [classifier1, classifier2], two_columns)
+        scores = []
+        for k, (mean, mad) in enumerate(stats):
+            maes = [(pred * mad + mean - (context[:, k].clone() * mad + mean)).abs() for pred, context in zip(preds[k], contexts)]
+            scores.append(torch.cat(maes)[:n_samples].mean().item() * _OUTPUT_NORM[props[k]])
+        return mols[:n_samples], scores[0], scores[1]
 
     return sampling_fn
 
