@@ -610,6 +610,35 @@ int jodo_egnn_forward(const jodo_egnn_cfg* cfg, int B, int N, const int32_t* n_n
                       const int64_t* woff, int n_woff, const float* h0, const float* x, float* out, void* workspace, int max_layers,
                       void* stream);
 
+/* ---- evaluation: atom and molecule stability of decoded molecules (csrc/eval_kernels.hip; evaluation/stability.py:17-161 of the
+ * reference: check_stability, and check_2D_stability for molecules without aromatic bonds) ----
+ * Inputs are the decode's device tensors (jodo_decode): pos f32 [B,N,3], atom_type u8 [B,N], fc i8 [B,N], edge_type u8 [B,N,N],
+ * n_nodes i32 [B].  Atoms at index >= n_nodes[b] do not exist, whatever the padding holds; a molecule with n_nodes <= 0 gets a zero row
+ * and counts in no total.  N <= 256, T <= 255 (JODO_ERR_UNSUPPORTED beyond).  The rule tables are the caller's DATA:
+ *   thr_dev        i32 [T][T][3]: single / double / triple thresholds of the ORDERED type pair in integer picometres, margins included,
+ *                  0 = no such bond; not symmetric.  pair_order says which ordered pair is looked up for atoms i < j:
+ *                  JODO_PAIR_BY_INDEX (type[i], type[j]), JODO_PAIR_BY_TYPE (the smaller type index first).
+ *                  Order of a pair at d = sqrtf(dx^2 + dy^2 + dz^2): 0 unless 100 d < t1; then 1 unless t2 > 0 and 100 d < t2; then 2
+ *                  unless t3 > 0 and 100 d < t3; then 3.
+ *   allowed_dev    u32 [T]: bit v set = valence v is allowed for the type (valence >= 32: unstable)
+ *   allowed_fc_dev u32 [T][fc_hi - fc_lo + 1]: the same per (type, formal charge), fc_lo <= 0 <= fc_hi; a charge outside the range reads
+ *                  the column of charge 0
+ * jodo_stability_3d: valence = integer sum of the pair orders.  order_out (optional, may be NULL): u8 [B,N,N] pair orders, symmetric,
+ *   zero on the diagonal and outside the molecule.
+ * jodo_stability_bonds: valence of atom i = sum over j of edge_type[min(i,j)][max(i,j)] (the upper triangle only is read) for orders 1-3;
+ *   an entry above 3 (4 = aromatic) is counted once in the molecule's needs_kekulize column and enters no valence.
+ * per_mol_out  i32 [B][4]: stable atoms, atoms, fragments, needs_kekulize (always 0 for the 3-D rule).  Fragments = connected components
+ *   over the bonds of order > 0 (derived orders / edge_type entries), an isolated atom being one.
+ * totals_out   i64 [4]: stable molecules, stable atoms, atoms, connected molecules (one fragment); zeroed by the call, then reduced
+ *   with integer atomics.  No host synchronisation; both calls may be captured into a graph. */
+enum jodo_pair_order { JODO_PAIR_BY_INDEX = 0, JODO_PAIR_BY_TYPE = 1 };
+int jodo_stability_3d(int B, int N, int T, int pair_order, const int32_t* thr_dev, const uint32_t* allowed_dev, const int32_t* n_nodes_dev,
+                      const float* pos, const uint8_t* atom_type, int32_t* per_mol_out, uint8_t* order_out, int64_t* totals_out,
+                      void* stream);
+int jodo_stability_bonds(int B, int N, int T, int fc_lo, int fc_hi, const uint32_t* allowed_fc_dev, const int32_t* n_nodes_dev,
+                         const uint8_t* atom_type, const int8_t* fc, const uint8_t* edge_type, int32_t* per_mol_out, int64_t* totals_out,
+                         void* stream);
+
 const char* jodo_last_error(void);
 
 /* measurement helper (synchronises, default stream): fp32 MFMA throughput of the box in TFLOP/s from a

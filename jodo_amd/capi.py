@@ -31,6 +31,7 @@ def lib():
         _bind_2d_pair(_lib)
         _bind_2d_split(_lib)
         _bind_egnn(_lib)
+        _bind_eval(_lib)
     return _lib
 
 
@@ -99,6 +100,22 @@ def _bind_egnn(L):
     fill.argtypes = [p, i, i, p, p, ctypes.c_int64]
     fwd.argtypes = [p, i, i, p, p, p, p, i, p, p, p, p, i, p]
     chk.restype = size.restype = pack.restype = lay.restype = fill.restype = fwd.restype = i
+
+
+PAIR_BY_INDEX, PAIR_BY_TYPE = 0, 1              # enum jodo_pair_order
+
+
+def _bind_eval(L):
+    """Argument types of the stability exports (jodo_stability_3d, jodo_stability_bonds; include/jodo_hip.h, section "evaluation")."""
+    i, p = ctypes.c_int, ctypes.c_void_p
+    try:
+        s3, sb = L.jodo_stability_3d, L.jodo_stability_bonds
+    except AttributeError as e:
+        raise JodoHipError("%s lacks the stability exports (%s): rebuild it with python -c 'import __graft_entry__ as g; g.build()'"
+                           % (LIB_PATH, e))
+    s3.argtypes = [i, i, i, i] + [p] * 9
+    sb.argtypes = [i, i, i, i, i] + [p] * 8
+    s3.restype = sb.restype = i
 
 
 def check(code, what=''):

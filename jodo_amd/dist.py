@@ -134,6 +134,20 @@ def gather_sampled(decoded, indices, device=None, group=None, with_pos=True):
     return [out[k] for k in torch.argsort(order).tolist()]
 
 
+def allreduce_counts(counts, device=None, group=None):
+    """Sum integer counters over the ranks with ONE small all-reduce: `counts` is a dict of ints (sampling_fn.last_stability: every rank
+    holds the totals of its own molecules) or a sequence of ints; returns the same structure with the global sums on every rank.
+    device: where the int64 buffer lives (a GPU with the "nccl" backend, the CPU with gloo; default: the CPU).  Without an initialised
+    process group the counts come back as they are."""
+    keys = sorted(counts) if isinstance(counts, dict) else None
+    vals = [int(counts[k]) for k in keys] if keys is not None else [int(v) for v in counts]
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+        buf = torch.tensor(vals, dtype=torch.int64, device=torch.device(device or 'cpu'))
+        dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=group)
+        vals = [int(v) for v in buf.cpu().tolist()]
+    return dict(zip(keys, vals)) if keys is not None else vals
+
+
 # ---- training (SURVEY.md §8f row 4 on more than one GPU) ------------------------------------------------------------------------
 def allreduce_gradients(params, weight=None, group=None):
     """Data-parallel training step, one process per GPU: every rank has run the step's forward / backward on ITS molecules, and the

@@ -197,7 +197,7 @@ class _ParityNoise2D(_ParityNoise):
 
 def get_sampling_fn(config, noise_scheduler, nodes_dist, batch_size, n_samples, inverse_scaler, eps=1e-3,
                     prop_dist=None, shard=None, return_raw=False, fused_decode=True, hip_graph=False,
-                    shard_mode='perf', shard_assign='contiguous', seed=None, device_noise=None, cpu_noise=False):
+                    shard_mode='perf', shard_assign='contiguous', seed=None, device_noise=None, cpu_noise=False, stability=None):
     """sampling.py:148-232.  Without `shard` this is the reference's procedure, RNG use included.
 
     shard=(rank, world) — one process per GPU (replaces nn.DataParallel).  Seeding contract: every rank passes the SAME
@@ -222,6 +222,12 @@ def get_sampling_fn(config, noise_scheduler, nodes_dist, batch_size, n_samples, 
     every round as they left the decode (on the GPU: the outputs of jodo_decode, still on the device) — what the caller's
     gather sends (jodo_amd/dist.gather_sampled).
 
+    stability — None (default): nothing changes.  A function of jodo_amd.evaluation.get_stability_fn: every round of the 3-D path hands
+    it the decode's device tensors, and `sampling_fn.last_stability` holds the integer totals of this call's rounds ('n_mol_stable',
+    'n_atom_stable', 'n_atoms', 'n_connected', 'n_mols'; one small device->host copy per round).  With `shard` they are this rank's:
+    the caller sums them over the ranks (jodo_amd/dist.allreduce_counts).  Needs the fused device decode (a GPU config.device,
+    fused_decode=True and the package's inverse scaler); anything else is refused, here or at the first round.
+
     config.sampling.method: 'ancestral' (both kinds of model), 'fast' (the hybrid DPM-Solver++ of the 3-D + edge models; raises on a
     2-D config) or 'dpm_2d' (2-D configs only: DPM-Solver++ without a position part, see _get_sampling_fn_2d; sampling.steps = NFE)."""
     device = config.device
@@ -234,6 +240,14 @@ def get_sampling_fn(config, noise_scheduler, nodes_dist, batch_size, n_samples, 
     compress_edge = config.data.compress_edge
     if not pred_edge:
         raise NotImplementedError("only the edge-predicting sampling paths (3-D + edge, 2-D) are in scope")
+    if stability is not None:
+        if config.only_2D:
+            raise NotImplementedError("stability= belongs to the 3-D sampling path; config.only_2D is set")
+        if not callable(stability):
+            raise TypeError("stability is a function of jodo_amd.evaluation.get_stability_fn")
+        if not fused_decode or not getattr(inverse_scaler, 'from_config', False):
+            raise ValueError("stability= works on the fused device decode: fused_decode=True and the inverse scaler of "
+                             "utils.get_data_inverse_scaler (there is no CPU fallback)")
     if config.only_2D:
         if torch.device(device).type != 'cuda':
             # DGT_concat_2D has no CPU fallback, and neither have the round's options that exist for it
@@ -310,7 +324,14 @@ def get_sampling_fn(config, noise_scheduler, nodes_dist, batch_size, n_samples, 
             dec = fused.decode(config, x_node, x_edge, nd)
             if shard is not None:                              # the gather takes the decoded DEVICE tensors as they are (dist.gather_sampled)
                 decoded_rounds.append(dec + (nd,))
+            if stability is not None:
+                res = stability(*dec, nd)
+                for k in stability_totals:
+                    stability_totals[k] += int(res[k])
             return fused.mols_from_decoded(*dec, n_nodes)
+        if stability is not None:
+            raise NotImplementedError("stability= works on the fused device decode, and this round ran on %s: there is no CPU fallback"
+                                      % x_node.device)
         pos, one_hot, fc, edge_types = post_process(x_node, atom_types, include_fc, node_mask, inverse_scaler, x_edge,
                                                     edge_mask, compress_edge)
         assert_mean_zero_with_mask(pos, node_mask)
@@ -321,12 +342,18 @@ def get_sampling_fn(config, noise_scheduler, nodes_dist, batch_size, n_samples, 
         return mol_process(one_hot, pos, fc, n_nodes, edge_types)
 
     decoded_rounds = []          # per round of a sharded run: (pos [B,N,3] f32, atom_type [B,N] u8, charge [B,N] i8, bond [B,N,N] u8, n_nodes [B] i32)
+    stability_totals = {}        # with stability=: the integer totals of the current call's rounds
 
     def sampling_fn(model):
         model.eval()
         mols = []
         del decoded_rounds[:]
         sampling_fn.last_decoded = decoded_rounds
+        if stability is not None:
+            from .evaluation import COUNT_KEYS
+            stability_totals.clear()
+            stability_totals.update({k: 0 for k in COUNT_KEYS})
+            sampling_fn.last_stability = stability_totals
         total = rounds * batch_size
         with torch.no_grad():
             if shard is None:                                  # the reference's procedure
@@ -383,6 +410,7 @@ def get_sampling_fn(config, noise_scheduler, nodes_dist, batch_size, n_samples, 
 
     sampling_fn.last_indices = None
     sampling_fn.last_decoded = decoded_rounds
+    sampling_fn.last_stability = None
     return sampling_fn
 
 
