@@ -639,6 +639,43 @@ int jodo_stability_bonds(int B, int N, int T, int fc_lo, int fc_hi, const uint32
                          const uint8_t* atom_type, const int8_t* fc, const uint8_t* edge_type, int32_t* per_mol_out, int64_t* totals_out,
                          void* stream);
 
+/* ---- evaluation: sub-structure geometry and its MMD (csrc/geometry_kernels.hip; evaluation/cal_geometry.py and evaluation/mmd.py of the
+ * reference) ----
+ * Extraction.  Inputs are the decode's device tensors as above (pos, atom_type, edge_type, n_nodes); keep (optional, may be NULL) u8 [B]:
+ * 0 = the molecule contributes nothing.  The molecule is the one check_2D_stability builds: a bond (i < j) for every nonzero
+ * edge_type[i][j] of the upper triangle, in row-major order; bond code 1, 2, 3, or 12 for edge_type 4.  Classes are integer tuples
+ * (atom-type index, code, atom-type index per bond): cls_b i32 [Cb][3], cls_a i32 [Ca][6], cls_d i32 [Cd][9], at most
+ * JODO_GEOMETRY_MAX_CLASSES per group; whole tuples are compared, the forward tuple first, then the reversed one.  Enumeration and
+ * multiplicities are cal_bond_distance / cal_bond_angle / cal_dihedral_angle's.  Values are float32: length in Angstrom,
+ * angle in degrees [0, 180], dihedral in degrees, signed; a non-finite value is dropped and counted.  N <= 256 (JODO_ERR_UNSUPPORTED).
+ * jodo_geometry_count: counts_out i32 [Cb+Ca+Cd][B] values per (class, molecule); offsets_out i64 [Cb+Ca+Cd][B] their exclusive scan
+ *   per group (class-major, molecule-minor: where a molecule's values of a class start in the group's array); sizes_out i64 [Cb+Ca+Cd]
+ *   values per class; dropped_out i64 [3] non-finite values per group.
+ * jodo_geometry_write: the same inputs and the offsets; out_b / out_a / out_d f32 of n_b / n_a / n_d values (the sums of sizes_out per
+ *   group; a pointer may be NULL when its size is 0).  The order inside a molecule is the reference's, the whole output is a function of
+ *   the input alone.  No host synchronisation in either call. */
+#define JODO_GEOMETRY_MAX_CLASSES 32
+int jodo_geometry_count(int B, int N, int Cb, int Ca, int Cd, const int32_t* cls_b_dev, const int32_t* cls_a_dev, const int32_t* cls_d_dev,
+                        const int32_t* n_nodes_dev, const uint8_t* keep, const float* pos, const uint8_t* atom_type,
+                        const uint8_t* edge_type, int32_t* counts_out, int64_t* offsets_out, int64_t* sizes_out, int64_t* dropped_out,
+                        void* stream);
+int jodo_geometry_write(int B, int N, int Cb, int Ca, int Cd, const int32_t* cls_b_dev, const int32_t* cls_a_dev, const int32_t* cls_d_dev,
+                        const int32_t* n_nodes_dev, const uint8_t* keep, const float* pos, const uint8_t* atom_type,
+                        const uint8_t* edge_type, const int64_t* offsets, float* out_b, float* out_a, float* out_d, int64_t n_b, int64_t n_a,
+                        int64_t n_d, void* stream);
+
+/* compute_mmd(source, target, kernel_mul, kernel_num, fix_sigma) of the reference for S segments in three launches.
+ * seg_dev i64 [S][4]: source offset, n_s, target offset, n_t (offsets into src / tgt, f32).  tiles_dev i32 [T][4]: segment, kind
+ * (0 source x source, 1 target x target, 2 source x target), x0, y0 — every JODO_MMD_TILE x JODO_MMD_TILE tile of kind 2, and of kinds
+ * 0 / 1 the tiles with y0 >= x0 (x0, y0 multiples of JODO_MMD_TILE; a tile above the diagonal is doubled), the tiles of a segment
+ * contiguous; tile_start_dev i32 [S+1] their ranges.  params_ws f32 [S][12], partials_ws f64 [T].  out_dev f64 [S]:
+ * XX / n_s^2 + YY / n_t^2 - 2 XY / (n_s n_t), diagonals included; NaN for an empty side or a zero bandwidth, as in the reference.
+ * fix_sigma 0 = the bandwidth of the data.  kernel_num 1 .. 8.  Bit-identical from run to run (no float atomics). */
+#define JODO_MMD_TILE 1024
+int jodo_mmd_batched(int S, int T, const int64_t* seg_dev, const int32_t* tiles_dev, const int32_t* tile_start_dev, const float* src,
+                     const float* tgt, double kernel_mul, int kernel_num, double fix_sigma, float* params_ws, double* partials_ws,
+                     double* out_dev, void* stream);
+
 const char* jodo_last_error(void);
 
 /* measurement helper (synchronises, default stream): fp32 MFMA throughput of the box in TFLOP/s from a

@@ -32,6 +32,7 @@ def lib():
         _bind_2d_split(_lib)
         _bind_egnn(_lib)
         _bind_eval(_lib)
+        _bind_geometry(_lib)
     return _lib
 
 
@@ -116,6 +117,24 @@ def _bind_eval(L):
     s3.argtypes = [i, i, i, i] + [p] * 9
     sb.argtypes = [i, i, i, i, i] + [p] * 8
     s3.restype = sb.restype = i
+
+
+GEOMETRY_MAX_CLASSES, MMD_TILE = 32, 1024       # JODO_GEOMETRY_MAX_CLASSES, JODO_MMD_TILE
+
+
+def _bind_geometry(L):
+    """Argument types of the geometry exports (jodo_geometry_count, jodo_geometry_write, jodo_mmd_batched; include/jodo_hip.h, section
+    "sub-structure geometry")."""
+    i, p, d, q = ctypes.c_int, ctypes.c_void_p, ctypes.c_double, ctypes.c_int64
+    try:
+        cnt, wr, mmd = L.jodo_geometry_count, L.jodo_geometry_write, L.jodo_mmd_batched
+    except AttributeError as e:
+        raise JodoHipError("%s lacks the geometry exports (%s): rebuild it with python -c 'import __graft_entry__ as g; g.build()'"
+                           % (LIB_PATH, e))
+    cnt.argtypes = [i] * 5 + [p] * 13
+    wr.argtypes = [i] * 5 + [p] * 12 + [q, q, q, p]
+    mmd.argtypes = [i, i] + [p] * 5 + [d, i, d] + [p] * 4
+    cnt.restype = wr.restype = mmd.restype = i
 
 
 def check(code, what=''):

@@ -197,7 +197,7 @@ class _ParityNoise2D(_ParityNoise):
 
 def get_sampling_fn(config, noise_scheduler, nodes_dist, batch_size, n_samples, inverse_scaler, eps=1e-3,
                     prop_dist=None, shard=None, return_raw=False, fused_decode=True, hip_graph=False,
-                    shard_mode='perf', shard_assign='contiguous', seed=None, device_noise=None, cpu_noise=False, stability=None):
+                    shard_mode='perf', shard_assign='contiguous', seed=None, device_noise=None, cpu_noise=False, stability=None, geometry=None):
     """sampling.py:148-232.  Without `shard` this is the reference's procedure, RNG use included.
 
     shard=(rank, world) — one process per GPU (replaces nn.DataParallel).  Seeding contract: every rank passes the SAME
@@ -228,6 +228,11 @@ def get_sampling_fn(config, noise_scheduler, nodes_dist, batch_size, n_samples, 
     the caller sums them over the ranks (jodo_amd/dist.allreduce_counts).  Needs the fused device decode (a GPU config.device,
     fused_decode=True and the package's inverse scaler); anything else is refused, here or at the first round.
 
+    geometry — None (default): nothing changes.  A function of jodo_amd.evaluation.get_geometry_fn: every round of the 3-D path hands it
+    the decode's device tensors, and `sampling_fn.last_geometry` holds its result over this call's rounds ('values': per symbol one
+    device f32 tensor, the rounds concatenated; 'counts', 'dropped', 'n_mols' summed) — what sub_geometry_metric takes.  With `shard`
+    it is this rank's.  The same needs and refusals as stability=.
+
     config.sampling.method: 'ancestral' (both kinds of model), 'fast' (the hybrid DPM-Solver++ of the 3-D + edge models; raises on a
     2-D config) or 'dpm_2d' (2-D configs only: DPM-Solver++ without a position part, see _get_sampling_fn_2d; sampling.steps = NFE)."""
     device = config.device
@@ -247,6 +252,14 @@ def get_sampling_fn(config, noise_scheduler, nodes_dist, batch_size, n_samples, 
             raise TypeError("stability is a function of jodo_amd.evaluation.get_stability_fn")
         if not fused_decode or not getattr(inverse_scaler, 'from_config', False):
             raise ValueError("stability= works on the fused device decode: fused_decode=True and the inverse scaler of "
+                             "utils.get_data_inverse_scaler (there is no CPU fallback)")
+    if geometry is not None:
+        if config.only_2D:
+            raise NotImplementedError("geometry= belongs to the 3-D sampling path; config.only_2D is set (a 2-D molecule has no positions)")
+        if not callable(geometry):
+            raise TypeError("geometry is a function of jodo_amd.evaluation.get_geometry_fn")
+        if not fused_decode or not getattr(inverse_scaler, 'from_config', False):
+            raise ValueError("geometry= works on the fused device decode: fused_decode=True and the inverse scaler of "
                              "utils.get_data_inverse_scaler (there is no CPU fallback)")
     if config.only_2D:
         if torch.device(device).type != 'cuda':
@@ -328,9 +341,15 @@ def get_sampling_fn(config, noise_scheduler, nodes_dist, batch_size, n_samples, 
                 res = stability(*dec, nd)
                 for k in stability_totals:
                     stability_totals[k] += int(res[k])
+            if geometry is not None:
+                from .evaluation.geometry import merge_results
+                merge_results(geometry_acc, geometry(dec[0], dec[1], dec[3], nd))
             return fused.mols_from_decoded(*dec, n_nodes)
         if stability is not None:
             raise NotImplementedError("stability= works on the fused device decode, and this round ran on %s: there is no CPU fallback"
+                                      % x_node.device)
+        if geometry is not None:
+            raise NotImplementedError("geometry= works on the fused device decode, and this round ran on %s: there is no CPU fallback"
                                       % x_node.device)
         pos, one_hot, fc, edge_types = post_process(x_node, atom_types, include_fc, node_mask, inverse_scaler, x_edge,
                                                     edge_mask, compress_edge)
@@ -343,6 +362,7 @@ def get_sampling_fn(config, noise_scheduler, nodes_dist, batch_size, n_samples, 
 
     decoded_rounds = []          # per round of a sharded run: (pos [B,N,3] f32, atom_type [B,N] u8, charge [B,N] i8, bond [B,N,N] u8, n_nodes [B] i32)
     stability_totals = {}        # with stability=: the integer totals of the current call's rounds
+    geometry_acc = {}            # with geometry=: the merged results of the current call's rounds
 
     def sampling_fn(model):
         model.eval()
@@ -354,6 +374,9 @@ def get_sampling_fn(config, noise_scheduler, nodes_dist, batch_size, n_samples, 
             stability_totals.clear()
             stability_totals.update({k: 0 for k in COUNT_KEYS})
             sampling_fn.last_stability = stability_totals
+        if geometry is not None:
+            geometry_acc.clear()
+            sampling_fn.last_geometry = geometry_acc
         total = rounds * batch_size
         with torch.no_grad():
             if shard is None:                                  # the reference's procedure
@@ -411,6 +434,7 @@ def get_sampling_fn(config, noise_scheduler, nodes_dist, batch_size, n_samples, 
     sampling_fn.last_indices = None
     sampling_fn.last_decoded = decoded_rounds
     sampling_fn.last_stability = None
+    sampling_fn.last_geometry = None
     return sampling_fn
 
 
