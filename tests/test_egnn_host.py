@@ -106,6 +106,41 @@ def test_unsupported_settings_raise_and_name_the_setting():
     assert 'padded width' in L.jodo_last_error().decode()
 
 
+def test_descriptor_words_at_the_widest_layout_and_its_refusals():
+    """jodo_egnn_layout + jodo_egnn_fill_desc at B = 5000, N = 255 (molecule index 4999 and atom slot 254 share one word as
+    (b << 8) | i): counts, exclusive prefix sums and every atom word against a numpy restatement; then what the layout refuses."""
+    L = capi.lib()
+    cfg = ctypes.byref(_CfgEGNN(128, 7, 5, 1, 0))
+    ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    B, N = 5000, 255
+    n = np.array([[255, 1, 181, 2, 224][b % 5] for b in range(B)], dtype=np.int32)
+    Nn = int(n.sum())
+    lay = (ctypes.c_int64 * 8)()
+    assert L.jodo_egnn_layout(cfg, B, N, ptr(n), lay) == 0
+    assert lay[2] == Nn == 1000 * 663 and lay[0] == 2 * B + Nn
+    desc = np.full(int(lay[0]) + 1, -7, dtype=np.int32)
+    assert L.jodo_egnn_fill_desc(cfg, B, N, ptr(n), ptr(desc), ctypes.c_int64(int(lay[0]))) == 0
+    assert desc[-1] == -7                                     # nothing behind the words asked for
+    noff = np.concatenate([[0], np.cumsum(n)[:-1]])
+    assert np.array_equal(desc[:B], n) and np.array_equal(desc[B:2 * B], noff)
+    words = desc[2 * B:-1]
+    mol = np.repeat(np.arange(B), n)
+    assert np.array_equal(words >> 8, mol) and np.array_equal(words & 255, np.arange(Nn) - noff[mol])
+    assert int((words & 255).max()) == 254 and int((words >> 8).max()) == B - 1
+    # refusals
+    assert L.jodo_egnn_fill_desc(cfg, B, N, ptr(n), ptr(desc), ctypes.c_int64(int(lay[0]) - 1)) == -1      # JODO_ERR_ARG
+    assert 'words' in L.jodo_last_error().decode()
+    for idx, bad in ((3, 0), (4998, N + 1)):
+        m = n.copy()
+        m[idx] = bad
+        assert L.jodo_egnn_layout(cfg, B, N, ptr(m), lay) == -1                                         # JODO_ERR_ARG
+        assert 'n_nodes[%d]=%d' % (idx, bad) in L.jodo_last_error().decode()
+    small = np.array([255, 3], dtype=np.int32)
+    assert L.jodo_egnn_layout(cfg, 2, 256, ptr(small), lay) == -3                                       # JODO_ERR_UNSUPPORTED
+    assert 'padded width' in L.jodo_last_error().decode()
+    assert L.jodo_egnn_layout(cfg, 2, 255, ptr(small), lay) == 0 and lay[2] == 258
+
+
 def test_cpu_grad_enabled_and_sparse_calls_raise_with_directions():
     from jodo_amd.sampling import build_masks, full_edge_index
     m = EGNN(5, 0, 64, n_layers=1).eval()
