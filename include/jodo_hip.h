@@ -581,7 +581,9 @@ int jodo_train2d_backward(jodo_train2d* t, const void* desc_dev, const float* co
  * tensor is JODO_ERR_ARG with its name in jodo_last_error()).  Slot tables: offsets in floats into the packed blob; the table holds
  * JE_GLOBAL_COUNT global slots, then JEL_LAYER_COUNT per layer.  "Tiled" weights as in the 2-D section.
  *   JEL_P_W: edge_mlp.0 hoisted to the nodes, rows [W_src ; W_tgt] (2 nf x nf), JEL_P_B = [b1 ; 0]; JEL_WR = its radial column;
- *   JEL_N0_W: node_mlp.0 over [h | agg (| h0)], K = 2 nf (+ in_node_nf with node_attr, zero-padded to a K chunk). */
+ *   JEL_N0_W: node_mlp.0 over [h | agg (| h0)], K = 2 nf (+ in_node_nf with node_attr, zero-padded to a K chunk).
+ * These entry points are the inference side; fitting the classifier is the next section (jodo_egnn_train_*), whose forward runs the
+ * same kernels on a blob it rebuilds on the device. */
 typedef struct {
     int32_t hidden_nf, n_layers, in_node_nf, attention, node_attr;
 } jodo_egnn_cfg;
@@ -609,6 +611,34 @@ int jodo_egnn_fill_desc(const jodo_egnn_cfg* cfg, int B, int N, const int32_t* n
 int jodo_egnn_forward(const jodo_egnn_cfg* cfg, int B, int N, const int32_t* n_nodes_host, const void* desc_dev, const float* packed_w,
                       const int64_t* woff, int n_woff, const float* h0, const float* x, float* out, void* workspace, int max_layers,
                       void* stream);
+
+/* ---- training the property classifier (csrc/egnn_train.hip) ----------------------------------------------------------------------------
+ * jodo_egnn_train_* mirror jodo_train2d_* one for one: parameters by name in their PyTorch layouts at create (every tensor of the
+ * state_dict; a leading "module." is accepted), params_dev / grads_dev pointer tables in that order, explicit stream, caller-owned
+ * workspace that carries the kept tensors from forward to backward, gradients fully written (gaps under 16 bytes between two gradient
+ * buffers included) in a fixed launch order without atomics.  The supported set is jodo_egnn_check_cfg's, N <= 255.
+ * Forward: the kernels of jodo_egnn_forward in the same order, each layer's per-atom tensors kept (O(L Nn nf) floats, no per-edge
+ * tensor); the tiled weight image is rebuilt on the device from params_dev on every call, so out [B] is bit-identical to
+ * jodo_egnn_forward on the same weights and follows any in-place update of them.
+ * Backward: d <d_out, out> / d parameter for d_out [B]; nothing with respect to h0 or x.  The message is recomputed per edge by the fused
+ * kernel kegnn_edge_bwd, which writes 3 hidden_nf floats per edge (a, dz2, dz1: compact edge rows, reused by every layer).
+ * jodo_egnn_train_set_option: option 2 only (accepted for parity with jodo_train2d_set_option; the forward keeps the same tensors either
+ * way).  jodo_egnn_train_debug_locate: 0 = h_layer [Nn, nf] (layer 0 .. n_layers), 1 = P [Nn, 2 nf], 2 = agg [Nn, nf],
+ * 3 = SiLU(node_mlp.0 .) [Nn, nf]. */
+typedef struct jodo_egnn_train jodo_egnn_train;
+int jodo_egnn_train_create(const jodo_egnn_cfg* cfg, int B, int N, const int32_t* n_nodes_host, const jodo_tensor* params, int n_params,
+                           jodo_egnn_train** out);
+void jodo_egnn_train_destroy(jodo_egnn_train* t);
+size_t jodo_egnn_train_desc_bytes(const jodo_egnn_train* t);
+size_t jodo_egnn_train_workspace_bytes(const jodo_egnn_train* t);
+const void* jodo_egnn_train_desc_host(const jodo_egnn_train* t);
+int jodo_egnn_train_upload(jodo_egnn_train* t, void* desc_dev, void* stream);
+int jodo_egnn_train_set_option(jodo_egnn_train* t, int option, int value);
+int jodo_egnn_train_debug_locate(const jodo_egnn_train* t, int what, int layer, size_t* byte_offset, size_t* count);
+int jodo_egnn_train_forward(jodo_egnn_train* t, const void* desc_dev, const float* const* params_dev, int n_params, const float* h0,
+                            const float* x, float* out, void* workspace, void* stream);
+int jodo_egnn_train_backward(jodo_egnn_train* t, const void* desc_dev, const float* const* params_dev, float* const* grads_dev, int n_params,
+                             const float* d_out, void* workspace, void* stream);
 
 /* ---- evaluation: atom and molecule stability of decoded molecules (csrc/eval_kernels.hip; evaluation/stability.py:17-161 of the
  * reference: check_stability, and check_2D_stability for molecules without aromatic bonds) ----

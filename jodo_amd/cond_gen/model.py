@@ -8,6 +8,10 @@ which is the call jodo_amd.sampling.get_cond_sampling_eval_fn / get_cond_multi_s
 libjodo_hip.so (csrc/egnn_forward.hip, `jodo_egnn_forward`) on the current HIP stream: the first edge layer is hoisted to the atoms, the
 per-edge message lives in registers only, and real atoms are compact (the result on real atoms does not depend on padding).  There is
 no CPU or eager fallback: tests/oracle_egnn.py is the CPU checker.
+
+Training is opt-in: with `classifier.hip_training = True` (jodo_amd.cond_gen.get_classifier_step_fn sets it) a grad-enabled call runs
+csrc/egnn_train.hip through jodo_amd.train.TrainEngineEGNN and `loss.backward()` fills every parameter's gradient; a default module keeps
+refusing grad-enabled calls.
 """
 import ctypes
 import pickle
@@ -70,6 +74,7 @@ class EGNN(nn.Module):
         self._plans = {}              # per (B, N, atom counts): descriptor + workspace
         self.validate_masks = True    # one device pass per call: prefix node_mask, edge_mask = its off-diagonal outer product
         self.max_layers = -1          # tests: stop after this many layers; forward then returns the hidden state [Nn, hidden_nf]
+        self.hip_training = False     # opt-in: grad-enabled calls go through the HIP training path (csrc/egnn_train.hip)
         self.register_load_state_dict_post_hook(_drop_packed_after_load)
         self.to(self.device)
 
@@ -97,7 +102,8 @@ class EGNN(nn.Module):
             "weights belong to one device.  DataParallel(model, device_ids=[one device]) is supported." % type(self).__name__)
 
     # -- per-batch descriptor and workspace -----------------------------------------------------------
-    def _plan(self, node_mask, edge_mask, B, N, device):
+    def _counts(self, node_mask, edge_mask, B, N):
+        """Atom counts on the host (int32 [B]); with validate_masks the two mask checks ride on the same transfer."""
         nm = node_mask.reshape(B, N)
         n_nodes = nm.sum(1).round().to(torch.int32)
         if self.validate_masks:
@@ -115,6 +121,10 @@ class EGNN(nn.Module):
             n_host = np.ascontiguousarray(host[:B], dtype=np.int32)
         else:
             n_host = np.ascontiguousarray(n_nodes.cpu().numpy(), dtype=np.int32)
+        return n_host
+
+    def _plan(self, node_mask, edge_mask, B, N, device):
+        n_host = self._counts(node_mask, edge_mask, B, N)
         key = (str(device), B, N, n_host.tobytes())
         plan = self._plans.pop(key, None)
         if plan is None:
@@ -134,9 +144,14 @@ class EGNN(nn.Module):
 
     # -- forward -------------------------------------------------------------------------------
     def forward(self, h0, x, edges, edge_attr, node_mask, edge_mask, n_nodes):
-        if torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters()) or h0.requires_grad or x.requires_grad):
-            raise NotImplementedError("jodo_amd EGNN is inference only: call it under torch.no_grad() (training the classifier is not "
-                                      "implemented)")
+        wants_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        inputs_want_grad = torch.is_grad_enabled() and (h0.requires_grad or x.requires_grad)
+        if not self.hip_training and (wants_grad or inputs_want_grad):
+            raise NotImplementedError("jodo_amd EGNN is inference only by default: call it under torch.no_grad().  Training is opt-in: "
+                                      "set `hip_training = True` (jodo_amd.cond_gen.get_classifier_step_fn does) for parameter gradients")
+        if inputs_want_grad:
+            raise NotImplementedError("the HIP classifier returns parameter gradients only: input gradients (with respect to h0 or x) "
+                                      "are not computed; detach the inputs")
         if edge_attr is not None:
             raise NotImplementedError("edge_attr must be None: the HIP classifier takes no edge attributes (in_edge_nf = 0)")
         N = int(n_nodes)
@@ -152,6 +167,8 @@ class EGNN(nn.Module):
             raise NotImplementedError("jodo_amd EGNN runs on an MI355X only (got a %s tensor); there is no CPU fallback — use "
                                       "tests/oracle_egnn.py for CPU checks, or move the module and its inputs to the GPU" % h0.device)
         dev = h0.device
+        if wants_grad:
+            return self._forward_train(h0, x, node_mask, edge_mask, B, N, dev)
         plan = self._plan(node_mask, edge_mask, B, N, dev)
         _, blob, woff_c, n_woff = self._weights(dev)
         h0_ = h0.detach().to(torch.float32).contiguous()
@@ -165,6 +182,34 @@ class EGNN(nn.Module):
             nf = self.hidden_nf
             return plan['ws'][plan['h_off']:plan['h_off'] + plan['Nn'] * nf * 4].view(torch.float32).reshape(plan['Nn'], nf).clone()
         return out
+
+    # -- training path (opt-in: hip_training) ------------------------------------------------------------
+    def _train_engine(self, node_mask, edge_mask, B, N, device):
+        """One TrainEngineEGNN (jodo_egnn_train handle + device tables) per set of atom counts, in a bounded cache like `_plans`; all
+        engines of the module share its two workspaces."""
+        from ..train import TrainEngineEGNN
+        n_host = self._counts(node_mask, edge_mask, B, N)
+        key = (str(device), B, N, n_host.tobytes())
+        cache = self.__dict__.setdefault('_train_engines', {})
+        eng = cache.pop(key, None)
+        if eng is None:
+            named = self.__dict__.get('_train_named')
+            if named is None:
+                named = self.__dict__['_train_named'] = TrainEngineEGNN.named_table([(k, tuple(v.shape)) for k, v in self.named_parameters()])
+            pool = self.__dict__.setdefault('_train_pool', TrainEngineEGNN.new_pool())
+            eng = TrainEngineEGNN(self._cfg_struct, n_host, N, named, device, pool=pool)
+            while len(cache) >= 8:
+                cache.pop(next(iter(cache)))
+        cache[key] = eng                                         # most recently used last
+        return eng
+
+    def _forward_train(self, h0, x, node_mask, edge_mask, B, N, dev):
+        from ..train import egnn_autograd
+        if self.max_layers >= 0:
+            raise NotImplementedError("max_layers is a switch of the inference forward")
+        eng = self._train_engine(node_mask, edge_mask, B, N, dev)
+        return egnn_autograd(eng, h0.detach().to(torch.float32).contiguous(), x.detach().to(torch.float32).contiguous(),
+                             list(self.parameters()))
 
 
 def get_model(args):

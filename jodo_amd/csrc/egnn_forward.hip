@@ -15,8 +15,10 @@
 #include "../../include/jodo_hip.h"
 #include "jodo_hip_internal.h"
 #include "dgt_device.h"
+#include "egnn_internal.h"
 
 using namespace jd;
+using jegnn::half_sum16;
 
 namespace {
 
@@ -137,21 +139,6 @@ __global__ __launch_bounds__(64) void kegnn_gemm(EGemm G) {
 }
 
 // ---- fused edge kernel ----------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float half_sum16(const float (&v)[16], int j) {     // as in csrc/dgt2d_forward.hip: lane j ends with the total of
-    float a[16];                                                               // value j % 16 over the 32 lanes of its half
-#pragma unroll
-    for (int s = 0; s < 16; ++s) a[s] = v[s] + __shfl_xor(v[s], 16);
-    float b8[8], b4[4], b2[2];
-    const bool u8 = (j & 8) != 0, u4 = (j & 4) != 0, u2 = (j & 2) != 0, u1 = (j & 1) != 0;
-#pragma unroll
-    for (int s = 0; s < 8; ++s) b8[s] = (u8 ? a[s + 8] : a[s]) + __shfl_xor(u8 ? a[s] : a[s + 8], 8);
-#pragma unroll
-    for (int s = 0; s < 4; ++s) b4[s] = (u4 ? b8[s + 4] : b8[s]) + __shfl_xor(u4 ? b8[s] : b8[s + 4], 4);
-#pragma unroll
-    for (int s = 0; s < 2; ++s) b2[s] = (u2 ? b4[s + 2] : b4[s]) + __shfl_xor(u2 ? b4[s] : b4[s + 2], 2);
-    return (u1 ? b2[1] : b2[0]) + __shfl_xor(u1 ? b2[0] : b2[1], 1);
-}
-
 struct EEdge {
     const int *mol_n, *mol_noff, *node_b;
     int Nn;
@@ -303,7 +290,7 @@ int gemm(hipStream_t st, EGemm G) {
 
 template <int NB, bool LDSW>
 int edge_launch(hipStream_t st, const EEdge& A) {
-    const int grid = (A.Nn + 3) / 4 < 512 ? (A.Nn + 3) / 4 : 512;      // persistent: a workgroup stages W2 once and walks its atoms
+    const int grid = (A.Nn + 3) / 4 < jegnn::EDGE_GRID_MAX ? (A.Nn + 3) / 4 : jegnn::EDGE_GRID_MAX;      // persistent: a workgroup stages W2 once and walks its atoms
     LEG((kegnn_edge<NB, LDSW>), grid, 256, A);
     return JODO_OK;
 }
@@ -336,22 +323,18 @@ extern "C" int jodo_egnn_fill_desc(const jodo_egnn_cfg* cfg, int B, int N, const
     return JODO_OK;
 }
 
-extern "C" int jodo_egnn_forward(const jodo_egnn_cfg* cfg, int B, int N, const int32_t* n_nodes, const void* desc_dev, const float* packed_w,
-                                 const int64_t* woff, int n_woff, const float* h0, const float* x, float* out, void* workspace,
-                                 int max_layers, void* stream) {
-    if (!desc_dev || !packed_w || !woff || !h0 || !x || !workspace || (max_layers < 0 && !out))
-        return jodo_set_error(JODO_ERR_ARG, "egnn_forward: null argument");
-    if (int rc = jodo_egnn_check_cfg(cfg)) return rc;
-    if (n_woff != JE_GLOBAL_COUNT + cfg->n_layers * JEL_LAYER_COUNT)
-        return jodo_set_error(JODO_ERR_ARG, "egnn_forward: offset table of %d slots, expected %d", n_woff, JE_GLOBAL_COUNT + cfg->n_layers * JEL_LAYER_COUNT);
-    Lay l;
-    if (int rc = make_lay(cfg, B, N, n_nodes, &l)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const int nf = cfg->hidden_nf, NB = nf / 32, NK = nf / 64, Nn = l.Nn;
-    float* ws = (float*)workspace;
+int jegnn::row_gemm(hipStream_t st, const float* X0, int ld0, int nk0, const float* X1, int ld1, int nk1, const float* X2, int ld2, int nk2, float* Y,
+                    int ldy, const float* W, const float* bias, int rows, int nb, int act, const float* R) {
+    EGemm G{X0, X1, X2, ld0, ld1, ld2, nk0, nk1, nk2, Y, ldy, W, bias, rows, nb, act, R, ldy};
+    return gemm(st, G);
+}
+
+int jegnn::run(const jodo_egnn_cfg* cfg, int B, int N, int Nn, const void* desc_dev, const float* packed_w, const int64_t* woff, const float* h0,
+               const float* x, float* out, const Bufs& bf, int max_layers, hipStream_t st) {
+    const int nf = cfg->hidden_nf, NB = nf / 32, NK = nf / 64;
     const int* desc = (const int*)desc_dev;
     const int *mol_n = desc, *mol_noff = desc + B, *node_b = desc + 2 * B;
-    float *h = ws + l.h, *p = ws + l.p, *agg = ws + l.agg, *t = ws + l.t, *a0 = ws + l.a0, *xc = ws + l.xc, *g = ws + l.g, *g1 = ws + l.g1;
+    float *a0 = bf.a0, *xc = bf.xc;
     auto W = [&](int64_t off) { return packed_w + off; };
 
     LEG(kegnn_gather, (unsigned)(((size_t)Nn * 64 + 255) / 256), 256, node_b, Nn, N, cfg->in_node_nf, h0, x, a0, xc);
@@ -360,10 +343,12 @@ extern "C" int jodo_egnn_forward(const jodo_egnn_cfg* cfg, int B, int N, const i
         EGemm G{X0, X1, X2, ld0, ld1, ld2, nk0, nk1, nk2, Y, ldy, W(w), W(bias), rows, nb, act, R, ldy};
         return gemm(st, G);
     };
-    if (int rc = row_gemm(a0, 64, 1, nullptr, 0, 0, nullptr, 0, 0, h, nf, woff[JE_EMB_W], woff[JE_EMB_B], Nn, NB, 0, nullptr)) return rc;
+    if (int rc = row_gemm(a0, 64, 1, nullptr, 0, 0, nullptr, 0, 0, bf.h[0], nf, woff[JE_EMB_W], woff[JE_EMB_B], Nn, NB, 0, nullptr)) return rc;
     const int layers = max_layers < 0 || max_layers > cfg->n_layers ? cfg->n_layers : max_layers;
     for (int ly = 0; ly < layers; ++ly) {
         const int64_t* wl = woff + JE_GLOBAL_COUNT + (size_t)ly * JEL_LAYER_COUNT;
+        const float* h = bf.h[ly];
+        float *p = bf.p[ly], *agg = bf.agg[ly], *t = bf.t[ly];
         if (int rc = row_gemm(h, nf, NK, nullptr, 0, 0, nullptr, 0, 0, p, 2 * nf, wl[JEL_P_W], wl[JEL_P_B], Nn, 2 * NB, 0, nullptr)) return rc;
         EEdge E{mol_n, mol_noff, node_b, Nn, p, xc, W(wl[JEL_WR]), W(wl[JEL_W2]), W(wl[JEL_B2]),
                 cfg->attention ? W(wl[JEL_ATT_W]) : nullptr, cfg->attention ? W(wl[JEL_ATT_B]) : nullptr, agg};
@@ -376,13 +361,33 @@ extern "C" int jodo_egnn_forward(const jodo_egnn_cfg* cfg, int B, int N, const i
         }
         if (rc) return rc;
         if (int rc2 = row_gemm(h, nf, NK, agg, nf, NK, a0, 64, cfg->node_attr ? 1 : 0, t, nf, wl[JEL_N0_W], wl[JEL_N0_B], Nn, NB, 1, nullptr)) return rc2;
-        if (int rc2 = row_gemm(t, nf, NK, nullptr, 0, 0, nullptr, 0, 0, h, nf, wl[JEL_N2_W], wl[JEL_N2_B], Nn, NB, 0, h)) return rc2;
+        if (int rc2 = row_gemm(t, nf, NK, nullptr, 0, 0, nullptr, 0, 0, bf.h[ly + 1], nf, wl[JEL_N2_W], wl[JEL_N2_B], Nn, NB, 0, h)) return rc2;
     }
     if (max_layers >= 0) return JODO_OK;
-    if (int rc = row_gemm(h, nf, NK, nullptr, 0, 0, nullptr, 0, 0, t, nf, woff[JE_ND0_W], woff[JE_ND0_B], Nn, NB, 1, nullptr)) return rc;
-    if (int rc = row_gemm(t, nf, NK, nullptr, 0, 0, nullptr, 0, 0, agg, nf, woff[JE_ND2_W], woff[JE_ND2_B], Nn, NB, 0, nullptr)) return rc;
-    LEG(kegnn_molsum, B, 64, mol_n, mol_noff, B, nf, agg, g);
-    if (int rc = row_gemm(g, nf, NK, nullptr, 0, 0, nullptr, 0, 0, g1, nf, woff[JE_GD0_W], woff[JE_GD0_B], B, NB, 1, nullptr)) return rc;
-    LEG(kegnn_out, B, 64, B, nf, g1, W(woff[JE_GD2_W]), W(woff[JE_GD2_B]), out);
+    const float* h = bf.h[layers];
+    if (int rc = row_gemm(h, nf, NK, nullptr, 0, 0, nullptr, 0, 0, bf.tnd, nf, woff[JE_ND0_W], woff[JE_ND0_B], Nn, NB, 1, nullptr)) return rc;
+    if (int rc = row_gemm(bf.tnd, nf, NK, nullptr, 0, 0, nullptr, 0, 0, bf.hd, nf, woff[JE_ND2_W], woff[JE_ND2_B], Nn, NB, 0, nullptr)) return rc;
+    LEG(kegnn_molsum, B, 64, mol_n, mol_noff, B, nf, bf.hd, bf.g);
+    if (int rc = row_gemm(bf.g, nf, NK, nullptr, 0, 0, nullptr, 0, 0, bf.g1, nf, woff[JE_GD0_W], woff[JE_GD0_B], B, NB, 1, nullptr)) return rc;
+    LEG(kegnn_out, B, 64, B, nf, bf.g1, W(woff[JE_GD2_W]), W(woff[JE_GD2_B]), out);
     return JODO_OK;
+}
+
+extern "C" int jodo_egnn_forward(const jodo_egnn_cfg* cfg, int B, int N, const int32_t* n_nodes, const void* desc_dev, const float* packed_w,
+                                 const int64_t* woff, int n_woff, const float* h0, const float* x, float* out, void* workspace,
+                                 int max_layers, void* stream) {
+    if (!desc_dev || !packed_w || !woff || !h0 || !x || !workspace || (max_layers < 0 && !out))
+        return jodo_set_error(JODO_ERR_ARG, "egnn_forward: null argument");
+    if (int rc = jodo_egnn_check_cfg(cfg)) return rc;
+    if (n_woff != JE_GLOBAL_COUNT + cfg->n_layers * JEL_LAYER_COUNT)
+        return jodo_set_error(JODO_ERR_ARG, "egnn_forward: offset table of %d slots, expected %d", n_woff, JE_GLOBAL_COUNT + cfg->n_layers * JEL_LAYER_COUNT);
+    Lay l;
+    if (int rc = make_lay(cfg, B, N, n_nodes, &l)) return rc;
+    float* ws = (float*)workspace;
+    jegnn::Bufs bf;                                          // inference: one array of each kind, every layer overwrites the last one's
+    bf.a0 = ws + l.a0; bf.xc = ws + l.xc;
+    for (int ly = 0; ly <= cfg->n_layers; ++ly) bf.h[ly] = ws + l.h;
+    for (int ly = 0; ly < cfg->n_layers; ++ly) { bf.p[ly] = ws + l.p; bf.agg[ly] = ws + l.agg; bf.t[ly] = ws + l.t; }
+    bf.tnd = ws + l.t; bf.hd = ws + l.agg; bf.g = ws + l.g; bf.g1 = ws + l.g1;
+    return jegnn::run(cfg, B, N, l.Nn, desc_dev, packed_w, woff, h0, x, out, bf, max_layers, (hipStream_t)stream);
 }

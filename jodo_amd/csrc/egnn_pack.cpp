@@ -139,6 +139,19 @@ extern "C" int jodo_egnn_packed_size(const jodo_egnn_cfg* cfg, size_t* n_floats,
     return JODO_OK;
 }
 
+// the slot table alone (the training path rebuilds the blob on the device from the live parameters: egnn_train.hip)
+extern "C" int jodo_egnn_packed_layout(const jodo_egnn_cfg* cfg, int64_t* woff_out, int n_woff, size_t* n_floats) {
+    if (!woff_out || !n_floats) return jodo_set_error(JODO_ERR_ARG, "egnn_packed_layout: null argument");
+    if (int rc = check_cfg(cfg)) return rc;
+    if (n_woff != JE_GLOBAL_COUNT + cfg->n_layers * JEL_LAYER_COUNT)
+        return jodo_set_error(JODO_ERR_ARG, "egnn_packed_layout: table of %d slots, expected %d", n_woff, JE_GLOBAL_COUNT + cfg->n_layers * JEL_LAYER_COUNT);
+    Packer P;
+    P.blob = nullptr;
+    if (int rc = run(cfg, P, woff_out)) return rc;
+    *n_floats = P.pos;
+    return JODO_OK;
+}
+
 extern "C" int jodo_egnn_pack_weights_host(const jodo_egnn_cfg* cfg, const jodo_tensor* tensors, int n_tensors, float* packed_host,
                                            size_t cap_floats, int64_t* woff_out, int n_woff) {
     if (!tensors || !packed_host || !woff_out) return jodo_set_error(JODO_ERR_ARG, "egnn_pack_weights: null argument");

@@ -1,6 +1,7 @@
 """Python plumbing of the training side behind the C ABI; device tensors in, device tensors out, no CPU
 fallback.
 
+  TrainEngineEGNN / egnn_autograd  the same for the property classifier (csrc/egnn_train.hip), behind cond_gen/model.py when `hip_training` is set
   TrainEngine2D / dgt2d_autograd   the same for DGT_concat_2D (csrc/dgt2d_train.hip), behind models/dgt2d.py when `hip_training` is set
   TrainEngine / dgt_autograd   the whole score network under autograd: jodo_train_forward keeps the activations,
                                jodo_train_backward returns the gradient of every parameter (csrc/dgt_train.hip, train_ops.h,
@@ -24,7 +25,7 @@ class TrainEngine:
     passes them and always runs libjodo_hip.so on the current HIP stream.
 
     The pool / slot / pinned-ring code is shared by every engine class: a subclass names its family of C entry points in `_abi`
-    (TrainEngine2D below: jodo_train2d_*, which mirror jodo_train_* one for one)."""
+    (TrainEngine2D and TrainEngineEGNN below: jodo_train2d_* / jodo_egnn_train_*, which mirror jodo_train_* one for one)."""
 
     _abi = 'jodo_train'
 
@@ -216,6 +217,47 @@ class TrainEngine2D(TrainEngine):
     _abi = 'jodo_train2d'
 
 
+class TrainEngineEGNN(TrainEngine):
+    """The same for the property classifier (cond_gen EGNN, csrc/egnn_train.hip): `cfg_struct` is a jodo_egnn_cfg, the inputs are
+    h0 [B, N, in_node_nf] and x [B, N, 3], the output is one float per molecule.  Pool, slots and the pinned staging ring are
+    TrainEngine's.  debug_fetch selectors: 0 = h_layer [Nn, nf] (layer 0 .. n_layers), 1 = P [Nn, 2 nf], 2 = agg [Nn, nf],
+    3 = SiLU(node_mlp.0 .) [Nn, nf]."""
+
+    _abi = 'jodo_egnn_train'
+
+    def forward(self, params, h0, x, keep=False):
+        """params: contiguous float32 tensors in the order of `named_shapes`; h0, x: contiguous float32.  Returns out [B]; the kept
+        tensors stay in a workspace slot of the pool (self.stamp names it)."""
+        assert len(params) == self.n_params
+        slot = self._take_slot(h0.device, keep)
+        self._slot, self.stamp = slot, slot['stamp']
+        out = torch.empty(self.B, dtype=torch.float32, device=h0.device)
+        self._check(self._fn('forward')(self.handle, capi.ptr(self.desc), self._ptrs(params), self.n_params, capi.ptr(h0), capi.ptr(x),
+                                        capi.ptr(out), capi.ptr(slot['buf']), self._stream()), self._abi + '_forward')
+        return out
+
+    def backward(self, params, d_out, stamp=None):
+        """Gradients of every parameter for d_out [B] and the forward `stamp` (default: this engine's last forward)."""
+        slot = self.slot_of(self.stamp if stamp is None else stamp)
+        if slot is None:
+            raise RuntimeError("the activations of this forward were overwritten by later training-path forwards of the same module "
+                               "(%d activation workspaces per module, INTEGRATION.md §5); call backward earlier" % len(self.pool['slots']))
+        from .optim import carve, slice_offsets
+        lay = self.__dict__.get('_grad_layout')
+        if lay is None:
+            offs, total = slice_offsets([p.numel() for p in params])
+            lay = self._grad_layout = ([tuple(p.shape) for p in params], offs, total)
+        flat = torch.empty(lay[2], dtype=torch.float32, device=params[0].device)
+        tail = lay[1][-1] + params[-1].numel()
+        if tail != lay[2]:
+            flat[tail:].zero_()
+        grads = carve(flat, lay[0], lay[1])
+        self._check(self._fn('backward')(self.handle, capi.ptr(self.desc), self._ptrs(params), self._ptrs(grads), self.n_params,
+                                         capi.ptr(d_out), capi.ptr(slot['buf']), self._stream()), self._abi + '_backward')
+        slot['live'] = False
+        return grads
+
+
 def release_slot(pool, stamp):
     for s_ in pool['slots']:
         if s_['stamp'] == stamp:
@@ -262,3 +304,26 @@ def dgt_autograd(engine, dropout_p, seed, xh, edge_x, cond_x, cond_edge_x, noise
 def dgt2d_autograd(engine, dropout_p, seed, xh, edge_x, cond_x, cond_edge_x, noise_level, params):
     """The 2-D score network (a TrainEngine2D) as the same autograd node: no context."""
     return _DGTTrainFn.apply(engine, dropout_p, seed, xh, edge_x, cond_x, cond_edge_x, noise_level, None, *params)
+
+
+class _EGNNTrainFn(torch.autograd.Function):
+    """The property classifier as one autograd node: out [B] from h0, x (no gradient) and the parameters, whose gradients come from
+    jodo_egnn_train_backward."""
+
+    @staticmethod
+    def forward(ctx, engine, h0, x, *params):
+        ps = [p.detach().contiguous() for p in params]
+        out = engine.forward(ps, h0, x, keep=True)
+        ctx.engine, ctx.ps, ctx.stamp = engine, ps, engine.stamp
+        ctx.slot_guard = _SlotGuard(engine.pool, engine.stamp)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        grads = ctx.engine.backward(ctx.ps, d_out.to(torch.float32).contiguous(), stamp=ctx.stamp)
+        return (None,) * 3 + tuple(grads)
+
+
+def egnn_autograd(engine, h0, x, params):
+    """out [B] of a TrainEngineEGNN under autograd; h0 [B, N, in_node_nf], x [B, N, 3] contiguous float32 device tensors."""
+    return _EGNNTrainFn.apply(engine, h0, x, *params)
