@@ -757,6 +757,49 @@ int jodo_debug_chain(int mode, int K, int tiles, const float* x, int rows, const
 int jodo_debug_mlp(const float* x, int rows, const float* w1, const float* b1, const float* w2,
                    const float* b2, float* y, void* stream);
 
+/* ---- CDGS: the 2-D graph noise-prediction network (reference models/cdgs.py; csrc/cdgs_forward.hip, csrc/cdgs_pack.cpp) ----
+ * Inference only, exact fp32 (fp32 MFMA for every projection), no float atomics: two calls on the same inputs give the same bits.
+ * Supported: nf 256, n_heads 16, 1 <= n_layers <= 16, atom_ch 1..16, edge_ch 2 | 3, rw_depth 1..16, padded width N <= 181
+ * (JODO_CDGS_MAX_N); anything else -> JODO_ERR_UNSUPPORTED naming the setting.
+ * Weights: the reference's state_dict by name (`all_modules.<i>...`; 4-D [out, in, 1, 1] conv weights accepted as matrices), plus one
+ * caller-made tensor "time_freq" [nf / 2] (the sinusoid's frequencies, which the reference computes per call).  Slot tables: offsets in
+ * floats into the packed blob; the table holds JCG_GLOBAL_COUNT + n_layers * JCB_BLOCK_COUNT entries.
+ * Widths: cat = 2 nf / n_layers readout channels per block, stored at a stride of catp = cat rounded up to 32.  The node head reads rows
+ * [hids (n_layers catp) | atom_cate (154)] and the edge heads [hids | dense_cate (77, at +0) | dense_exist (77, at +96)], each padded to a
+ * multiple of 64; the packer permutes and zero-pads the first head layers' columns accordingly.
+ * Layout: real atoms compact (row noff_b + i); the edge state keeps n_b^2 rows of nf floats per molecule, row eoff_b + r n_b + c, the
+ * diagonal rows included (they are zero between blocks and carry FF(2 h_i) inside the edge GroupNorm statistics).
+ * jodo_cdgs_layout: out[0] = int32 words of the descriptor, out[1] = workspace bytes, out[2] = Nn, out[3] = R = sum n_b^2, byte offsets
+ * into the workspace of out[4] = h [Nn, nf], out[5] = e [R, nf], out[6] = the distance codes (int32 [R]), out[7] = the landing
+ * probabilities (float [Nn, 16], the first rw_depth live).  The workspace must be zero when first used and is the caller's.
+ * jodo_cdgs_fill_desc writes the descriptor into HOST memory: n_b [B], noff_b [B], eoff_b [B], b per real atom [Nn], b per edge row [R].
+ * jodo_cdgs_forward: t [B], x [B, N, atom_ch], edge_x [B, N, N, edge_ch] -> out_x [B, N, atom_ch], out_e [B, N, N, edge_ch], masked.
+ * max_blocks in [0, n_layers]: stop after that many blocks (0: after the embeddings) with h and e in the workspace; the outputs are then
+ * not written. */
+#define JODO_CDGS_MAX_N 181
+typedef struct {
+    int32_t nf, n_layers, n_heads, atom_ch, edge_ch, rw_depth;
+} jodo_cdgs_cfg;
+enum jodo_cdgs_wslot_global {
+    JCG_FREQ, JCG_T1_W, JCG_T1_B, JCG_T2_W, JCG_T2_B, JCG_TMOD_W, JCG_TMOD_B, JCG_EC_W, JCG_EC_B, JCG_EX_W, JCG_EX_B, JCG_SPD_W, JCG_SPD_B,
+    JCG_EEMB_W, JCG_EEMB_B, JCG_AD_W, JCG_AD_B, JCG_AC_W, JCG_AC_B, JCG_AR_W, JCG_AR_B, JCG_NEMB_W, JCG_NEMB_B, JCG_AH1_W, JCG_AH1_B,
+    JCG_AH2_W, JCG_AH2_B, JCG_AH3_W, JCG_AH3_B, JCG_EH1_W, JCG_EH1_B, JCG_EH2_W, JCG_EH2_B, JCG_EH3_W, JCG_EH3_B, JCG_GLOBAL_COUNT
+};
+enum jodo_cdgs_wslot_block {
+    JCB_EPS, JCB_GIN1_W, JCB_GIN1_B, JCB_GIN2_W, JCB_GIN2_B, JCB_QKV_W, JCB_QKV_B, JCB_E01_W, JCB_NL_G, JCB_NL_B, JCB_NA_G, JCB_NA_B,
+    JCB_FF1_W, JCB_FF1_B, JCB_FF2_W, JCB_FF2_B, JCB_NN_G, JCB_NN_B, JCB_FF3_W, JCB_FF3_B, JCB_FF4_W, JCB_FF4_B, JCB_NE_G, JCB_NE_B,
+    JCB_RN_W, JCB_RN_B, JCB_RE_W, JCB_RE_B, JCB_BLOCK_COUNT
+};
+int jodo_cdgs_check_cfg(const jodo_cdgs_cfg* cfg);
+int jodo_cdgs_packed_size(const jodo_cdgs_cfg* cfg, size_t* n_floats, int* n_woff);
+int jodo_cdgs_pack_weights_host(const jodo_cdgs_cfg* cfg, const jodo_tensor* tensors, int n_tensors, float* packed_host,
+                                size_t capacity_floats, int64_t* woff, int n_woff);
+int jodo_cdgs_layout(const jodo_cdgs_cfg* cfg, int B, int N, const int32_t* n_nodes_host, int64_t* out8);
+int jodo_cdgs_fill_desc(const jodo_cdgs_cfg* cfg, int B, int N, const int32_t* n_nodes_host, int32_t* desc_host, int64_t n_words);
+int jodo_cdgs_forward(const jodo_cdgs_cfg* cfg, int B, int N, const int32_t* n_nodes_host, const void* desc_dev, const float* packed_w,
+                      const int64_t* woff, int n_woff, const float* t, const float* x, const float* edge_x, float* out_x, float* out_e,
+                      void* workspace, int max_blocks, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,7 @@ def lib():
         _bind_egnn(_lib)
         _bind_eval(_lib)
         _bind_geometry(_lib)
+        _bind_cdgs(_lib)
     return _lib
 
 
@@ -135,6 +136,24 @@ def _bind_geometry(L):
     wr.argtypes = [i] * 5 + [p] * 12 + [q, q, q, p]
     mmd.argtypes = [i, i] + [p] * 5 + [d, i, d] + [p] * 4
     cnt.restype = wr.restype = mmd.restype = i
+
+
+def _bind_cdgs(L):
+    """Argument types of the CDGS exports (jodo_cdgs_*; include/jodo_hip.h, section "CDGS")."""
+    i, p = ctypes.c_int, ctypes.c_void_p
+    try:
+        chk, size, pack, lay, fill, fwd = (L.jodo_cdgs_check_cfg, L.jodo_cdgs_packed_size, L.jodo_cdgs_pack_weights_host, L.jodo_cdgs_layout,
+                                           L.jodo_cdgs_fill_desc, L.jodo_cdgs_forward)
+    except AttributeError as e:
+        raise JodoHipError("%s lacks the CDGS exports (%s): rebuild it with python -c 'import __graft_entry__ as g; g.build()'"
+                           % (LIB_PATH, e))
+    chk.argtypes = [p]
+    size.argtypes = [p, p, p]
+    pack.argtypes = [p, p, i, p, ctypes.c_size_t, p, i]
+    lay.argtypes = [p, i, i, p, p]
+    fill.argtypes = [p, i, i, p, p, ctypes.c_int64]
+    fwd.argtypes = [p, i, i, p, p, p, p, i] + [p] * 6 + [i, p]
+    chk.restype = size.restype = pack.restype = lay.restype = fill.restype = fwd.restype = i
 
 
 def check(code, what=''):
@@ -241,6 +260,28 @@ def pack_weights_egnn(cfg_struct, state_dict, device=None):
     blob = torch.empty(n_floats.value, dtype=torch.float32)
     check(L.jodo_egnn_pack_weights_host(ctypes.byref(cfg_struct), arr, len(keep), ctypes.c_void_p(blob.data_ptr()),
                                         ctypes.c_size_t(n_floats.value), woff, n_woff.value), 'jodo_egnn_pack_weights_host')
+    return (blob if device is None else blob.to(device)), woff, n_woff.value
+
+
+def pack_weights_cdgs(cfg_struct, state_dict, device=None):
+    """The CDGS state_dict (plus the caller's 'time_freq') -> (blob, woff ctypes int64 array, n_woff) through
+    jodo_cdgs_pack_weights_host; device=None keeps the blob on the CPU, otherwise it is copied to `device`."""
+    import numpy as np
+    import torch
+    L = lib()
+    keep, arr = [], (JodoTensor * len(state_dict))()
+    for i, (k, v) in enumerate(state_dict.items()):
+        t = np.ascontiguousarray(v.detach().float().cpu().numpy())
+        shp = (ctypes.c_int64 * max(t.ndim, 1))(*t.shape)
+        name = k.encode()
+        keep.append((t, shp, name))
+        arr[i] = JodoTensor(name, t.ctypes.data_as(ctypes.c_void_p), shp, t.ndim)
+    n_floats, n_woff = ctypes.c_size_t(), ctypes.c_int()
+    check(L.jodo_cdgs_packed_size(ctypes.byref(cfg_struct), ctypes.byref(n_floats), ctypes.byref(n_woff)), 'jodo_cdgs_packed_size')
+    woff = (ctypes.c_int64 * n_woff.value)()
+    blob = torch.empty(n_floats.value, dtype=torch.float32)
+    check(L.jodo_cdgs_pack_weights_host(ctypes.byref(cfg_struct), arr, len(keep), ctypes.c_void_p(blob.data_ptr()),
+                                        ctypes.c_size_t(n_floats.value), woff, n_woff.value), 'jodo_cdgs_pack_weights_host')
     return (blob if device is None else blob.to(device)), woff, n_woff.value
 
 

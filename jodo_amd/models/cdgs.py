@@ -1,0 +1,254 @@
+"""MI355X-native noise-prediction network for 2-D graphs, registered under the reference's name 'CDGS'
+(reference: models/cdgs.py; the configs vpsde_qm9_2d_cdgs and vpsde_geom_2d_cdgs).
+
+Same constructor argument, parameter names / shapes / registration order (one `all_modules` list: state_dict keys, EMA order,
+`strict=True` loading, the 4-D conv weights and the GINE `eps` buffers included) and the same call as the reference class:
+    model(t, x, node_mask, edge_mask, context=None, edge_x=...) -> (atom_score [B,N,atom_types], bond_score [B,N,N,edge_ch])
+The arithmetic runs in libjodo_hip.so (csrc/cdgs_forward.hip, `jodo_cdgs_forward`) on the current HIP stream: the weights are packed
+once (csrc/cdgs_pack.cpp), a descriptor and a workspace are built per batch of atom counts.  Inference only, exact fp32; there is no
+CPU or eager fallback, no training path, no split-bf16 form and no graph replay — those raise.
+
+The edge GroupNorm of the reference normalises the dense padded tensor, so a molecule's scores depend on the width N the caller
+padded the batch to; the kernels reproduce that from the tensors' N.
+"""
+import ctypes
+import math
+
+import numpy as np
+import torch
+from torch import nn
+
+from .. import capi
+from . import utils
+from .dgt import _drop_packed_after_load
+
+MAX_N = 181                                     # JODO_CDGS_MAX_N (include/jodo_hip.h): the GEOM config's max_node
+
+
+class _Cfg(ctypes.Structure):                   # jodo_cdgs_cfg (include/jodo_hip.h)
+    _fields_ = [('nf', ctypes.c_int32), ('n_layers', ctypes.c_int32), ('n_heads', ctypes.c_int32), ('atom_ch', ctypes.c_int32),
+                ('edge_ch', ctypes.c_int32), ('rw_depth', ctypes.c_int32)]
+
+
+class _GINEParams(nn.Module):
+    """GINEConv(nn, train_eps=False): the two PyG Linears of `nn` and the `eps` buffer [1]."""
+
+    def __init__(self, dim):
+        super().__init__()
+        self.nn = nn.Sequential(nn.Linear(dim, dim), nn.ReLU(), nn.Linear(dim, dim))
+        self.register_buffer('eps', torch.zeros(1))
+
+
+class _GateTransParams(nn.Module):
+    """EdgeGateTransLayer (models/layers.py): parameters only, reference registration order."""
+
+    def __init__(self, dim):
+        super().__init__()
+        self.lin_key = nn.Linear(dim, dim)
+        self.lin_query = nn.Linear(dim, dim)
+        self.lin_value = nn.Linear(dim, dim)
+        self.lin_edge0 = nn.Linear(dim, dim, bias=False)
+        self.lin_edge1 = nn.Linear(dim, dim, bias=False)
+
+
+class _HybridBlockParams(nn.Module):
+    """HybridMPBlock(dim, 'GINE', 'FullTrans_1'): parameters only, reference registration order."""
+
+    def __init__(self, dim):
+        super().__init__()
+        groups = min(dim // 4, 32)
+        self.t_node = nn.Linear(dim, dim)
+        self.t_edge = nn.Linear(dim, dim)
+        self.local_model = _GINEParams(dim)
+        self.self_attn = _GateTransParams(dim)
+        self.norm1_local = nn.GroupNorm(groups, dim, eps=1e-6)
+        self.norm1_attn = nn.GroupNorm(groups, dim, eps=1e-6)
+        self.ff_linear1 = nn.Linear(dim, dim * 2)
+        self.ff_linear2 = nn.Linear(dim * 2, dim)
+        self.norm2_node = nn.GroupNorm(groups, dim, eps=1e-6)
+        self.ff_linear3 = nn.Linear(dim, dim * 2)
+        self.ff_linear4 = nn.Linear(dim * 2, dim)
+        self.norm2_edge = nn.GroupNorm(groups, dim, eps=1e-6)
+
+
+def _conv1x1(cin, cout):
+    return nn.Conv2d(cin, cout, kernel_size=1)
+
+
+@utils.register_model(name='CDGS')
+class CDGS(nn.Module):
+    """Graph noise-prediction model: GINE + edge-gated full attention blocks over random-walk features (HIP)."""
+
+    depends_on_padded_width = True    # the dense edge GroupNorm: read by the sampling function's parity shards (jodo_amd/sampling.py)
+
+    def __init__(self, config):
+        super().__init__()
+        m, d = config.model, config.data
+        for key, want in (('nf', 256), ('n_heads', 16), ('cond_time', True)):
+            if getattr(m, key, None) != want:
+                raise NotImplementedError("config.model.%s=%r: the CDGS HIP path implements %r only" % (key, getattr(m, key, None), want))
+        if not getattr(d, 'centered', False):
+            raise NotImplementedError("config.data.centered=%r: the CDGS HIP path implements True only" % (getattr(d, 'centered', None),))
+        if m.edge_ch not in (2, 3):
+            raise NotImplementedError("config.model.edge_ch=%r: the CDGS HIP path implements 2 and 3" % (m.edge_ch,))
+        if not 1 <= d.atom_types <= 16:
+            raise NotImplementedError("config.data.atom_types=%r: the CDGS HIP path takes 1..16 atom channels" % (d.atom_types,))
+        if not 1 <= m.rw_depth <= 16:
+            raise NotImplementedError("config.model.rw_depth=%r: the CDGS HIP path implements 1..16" % (m.rw_depth,))
+        if not 1 <= m.n_layers <= 16:
+            raise NotImplementedError("config.model.n_layers=%r: the CDGS HIP path implements 1..16" % (m.n_layers,))
+        nf, L, rw = m.nf, m.n_layers, m.rw_depth
+        self.nf, self.n_layers, self.rw_depth = nf, L, rw
+        self.atom_ch, self.edge_ch = int(d.atom_types), int(m.edge_ch)
+        self.dropout_p = m.dropout                # identity at inference; kept for config parity
+        self._cfg_struct = _Cfg(nf, L, m.n_heads, self.atom_ch, self.edge_ch, rw)
+
+        # ---- parameter tree: one list, reference construction order ----
+        bond_se, atom_se = int(nf * 0.4), int(nf * 0.2)
+        bond_type, atom_type = int(0.5 * (nf - bond_se)), nf - 2 * atom_se
+        cat = (nf * 2) // L
+        mods = [nn.Linear(nf, nf * 2), nn.Linear(nf * 2, nf),
+                _conv1x1(self.edge_ch - 1, bond_type), _conv1x1(1, bond_type), _conv1x1(rw + 1, bond_se),
+                nn.Linear(bond_se + 2 * bond_type, nf),
+                nn.Linear(self.edge_ch, atom_se), nn.Linear(self.atom_ch, atom_type), nn.Linear(rw, atom_se),
+                nn.Linear(atom_type + 2 * atom_se, nf)]
+        for _ in range(L):
+            mods += [_HybridBlockParams(nf), nn.Linear(nf, cat), nn.Linear(nf, cat)]
+        mods += [nn.Linear(cat * L + atom_type, nf), nn.Linear(nf, nf // 2), nn.Linear(nf // 2, self.atom_ch)]
+        mods += [_conv1x1(cat * L + bond_type, nf), _conv1x1(nf, nf // 2), _conv1x1(nf // 2, self.edge_ch - 1)]
+        mods += [_conv1x1(cat * L + bond_type, nf), _conv1x1(nf, nf // 2), _conv1x1(nf // 2, 1)]
+        self.all_modules = nn.ModuleList(mods)
+
+        # ---- runtime state (not part of state_dict) ----
+        self._packed = None           # (version key, device blob, woff ctypes array, n_woff)
+        self._plans = {}              # per batch of atom counts: descriptor + workspace, keyed by the mask storage (see _plan)
+        self.max_blocks = -1          # tests: stop after this many blocks (the workspace then holds h and e of that block)
+        self.last_flags = None        # kept for interface parity: this model has one walk (directed) and one arithmetic form
+        self.split_bf16 = False       # the 3-D models' opt-in form; not built for this model (forward raises when set)
+        self.register_load_state_dict_post_hook(_drop_packed_after_load)
+
+    # -- weights (same invalidation rules as DGT_concat_2D._weights) ---------------------------------
+    def _tensors(self):
+        return list(self.parameters()) + list(self.buffers())
+
+    def _time_freq(self):
+        half = self.nf // 2                       # the reference's sinusoid table, fp32 as it computes it
+        return torch.exp(torch.arange(half, dtype=torch.float32) * -(math.log(10000) / (half - 1)))
+
+    def _weights(self, device):
+        ts = self._tensors()
+        key = (str(device),) + tuple(p._version for p in ts) + tuple(p.data_ptr() for p in ts)
+        if self._packed is None or self._packed[0] != key:
+            sd = dict(self.state_dict())
+            sd['time_freq'] = self._time_freq()
+            host, woff_c, n_woff = capi.pack_weights_cdgs(self._cfg_struct, sd, None)
+            self._packed = (key, host.to(device), woff_c, n_woff)
+            self._packed_fingerprint = self._fingerprint()
+        return self._packed
+
+    def _fingerprint(self):
+        ps = [p.detach() for p in self._tensors()]
+        norms = torch._foreach_norm(ps)
+        w = torch.arange(1, len(norms) + 1, device=norms[0].device, dtype=torch.float64)
+        return float((torch.stack([n.double() for n in norms]) * (1.0 + 1e-3 * w)).sum().item())
+
+    def _recheck_weights(self):
+        if self._packed is not None and self._fingerprint() != getattr(self, '_packed_fingerprint', None):
+            self._packed = None
+
+    def invalidate_packed_weights(self):
+        """Drop the packed kernel weights; the next forward re-packs from the current parameters (needed after in-place `.data`
+        updates that bump no tensor version, e.g. the reference's ExponentialMovingAverage.copy_to / restore)."""
+        self._packed = None
+
+    # -- per-batch descriptor and workspace -----------------------------------------------------------
+    def _plan(self, node_mask, edge_mask, device, validate=True):
+        key = (node_mask.data_ptr(), tuple(node_mask.shape), tuple(node_mask.stride()), str(node_mask.device))
+        plan = self._plans.get(key)
+        if plan is not None and plan['mask_version'] == node_mask._version:
+            return plan
+        self._recheck_weights()                          # new batch (= new sampling round): catch `.data` weight updates
+        B, N = node_mask.shape[0], node_mask.shape[1]
+        if N > MAX_N:
+            raise NotImplementedError("CDGS: padded width N = %d above the limit of %d atoms" % (N, MAX_N))
+        nm = node_mask.reshape(B, N)
+        n_nodes = nm.sum(1).round().to(torch.int32)
+        if validate:
+            prefix = (torch.arange(N, device=nm.device).unsqueeze(0) < n_nodes.unsqueeze(1)).to(nm.dtype)
+            if not torch.equal(prefix, nm):
+                raise ValueError("node_mask must be a prefix mask (real atoms first), as the samplers build it")
+            em = edge_mask.reshape(B, N, N)
+            want = prefix.unsqueeze(1) * prefix.unsqueeze(2) * (~torch.eye(N, dtype=torch.bool, device=nm.device))
+            if not torch.equal(want.to(em.dtype), em):
+                raise ValueError("edge_mask must be node_mask x node_mask with the diagonal removed")
+        n_host = np.ascontiguousarray(n_nodes.cpu().numpy(), dtype=np.int32)     # one sync per new batch
+        L = capi.lib()
+        lay = (ctypes.c_int64 * 8)()
+        n_ptr = n_host.ctypes.data_as(ctypes.c_void_p)
+        capi.check(L.jodo_cdgs_layout(ctypes.byref(self._cfg_struct), B, N, n_ptr, lay), 'jodo_cdgs_layout')
+        desc_host = torch.empty(int(lay[0]), dtype=torch.int32)
+        capi.check(L.jodo_cdgs_fill_desc(ctypes.byref(self._cfg_struct), B, N, n_ptr, ctypes.c_void_p(desc_host.data_ptr()),
+                                         ctypes.c_int64(int(lay[0]))), 'jodo_cdgs_fill_desc')
+        plan = dict(desc=desc_host.to(device), ws=torch.zeros(int(lay[1]), dtype=torch.uint8, device=device), n_nodes=n_host, B=B, N=N,
+                    Nn=int(lay[2]), rows=int(lay[3]), h_off=int(lay[4]), e_off=int(lay[5]), code_off=int(lay[6]), land_off=int(lay[7]),
+                    mask=node_mask, mask_version=node_mask._version)
+        self._plans.pop(key, None)
+        if len(self._plans) >= 8:                        # bounded cache
+            self._plans.pop(next(iter(self._plans)))
+        self._plans[key] = plan
+        return plan
+
+    def _replicate_for_data_parallel(self):
+        raise RuntimeError(
+            "jodo_amd %s cannot be replicated by torch.nn.DataParallel over several devices: its descriptors, workspace and packed "
+            "weights belong to one device.  DataParallel(model, device_ids=[one device]) is supported." % type(self).__name__)
+
+    # -- forward -------------------------------------------------------------------------------
+    def forward(self, t, x, node_mask, edge_mask, context=None, *args, **kwargs):
+        edge_x = kwargs['edge_x']
+        if not x.is_cuda:
+            raise RuntimeError("jodo_amd CDGS runs on an MI355X only (got a %s tensor); there is no CPU fallback — "
+                               "use tests/oracle_cdgs.py for CPU checks" % x.device)
+        if self.split_bf16:
+            raise NotImplementedError("split_bf16 is not implemented for CDGS (exact fp32 only)")
+        inputs_want_grad = any(t_ is not None and t_.requires_grad for t_ in (x, edge_x, t))
+        wants_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        if torch.is_grad_enabled() and (wants_grad or inputs_want_grad):
+            raise NotImplementedError("CDGS is inference only: call it under torch.no_grad() (training / backward for this model is "
+                                      "not implemented)")
+        B, N, dims = x.shape
+        if dims != self.atom_ch or edge_x.shape != (B, N, N, self.edge_ch) or t.shape != (B,):
+            raise ValueError("shape mismatch: x %s edge_x %s t %s" % (tuple(x.shape), tuple(edge_x.shape), tuple(t.shape)))
+        dev = x.device
+        f32 = lambda v: v.detach().to(torch.float32).contiguous()
+        x_, ex_, t_ = f32(x), f32(edge_x), f32(t)
+        plan = self._plan(node_mask, edge_mask, dev)     # first: a new batch re-checks the weight fingerprint
+        _, blob, woff_c, n_woff = self._weights(dev)
+        out_x = torch.empty_like(x_)
+        out_e = torch.empty_like(ex_)
+        n_ptr = plan['n_nodes'].ctypes.data_as(ctypes.c_void_p)
+        capi.check(capi.lib().jodo_cdgs_forward(ctypes.byref(self._cfg_struct), B, N, n_ptr, capi.ptr(plan['desc']), capi.ptr(blob), woff_c,
+                                                n_woff, capi.ptr(t_), capi.ptr(x_), capi.ptr(ex_), capi.ptr(out_x), capi.ptr(out_e),
+                                                capi.ptr(plan['ws']), int(self.max_blocks), capi.current_stream_ptr()),
+                   'jodo_cdgs_forward')
+        self._last_plan = plan
+        return out_x, out_e
+
+    # -- tests: the state inside the workspace after the last call ------------------------------------
+    def debug_state(self):
+        """(h [Nn, nf], e [sum n^2, nf]) of the last call as the kernels left them: h compact over real atoms; e row
+        eoff_b + r n_b + c, every ordered pair its own row, diagonal rows zero."""
+        p = self._last_plan
+        D, ws = self.nf, p['ws']
+        h = ws[p['h_off']:p['h_off'] + p['Nn'] * D * 4].view(torch.float32).reshape(p['Nn'], D)
+        e = ws[p['e_off']:p['e_off'] + p['rows'] * D * 4].view(torch.float32).reshape(p['rows'], D)
+        return h.clone(), e.clone()
+
+    def debug_rw(self):
+        """(distance code int32 [sum n^2], landing probabilities [Nn, rw_depth]) of the last call's random-walk features, rows as in
+        debug_state."""
+        p = self._last_plan
+        ws = p['ws']
+        code = ws[p['code_off']:p['code_off'] + p['rows'] * 4].view(torch.int32)
+        land = ws[p['land_off']:p['land_off'] + p['Nn'] * 16 * 4].view(torch.float32).reshape(p['Nn'], 16)
+        return code.clone(), land[:, :self.rw_depth].clone()

@@ -159,10 +159,12 @@ class _ParityNoise:
     rank consumes the global CPU generator identically, so the slices are a partition of ONE draw and a world-size-N
     run reproduces the world-size-1 run molecule for molecule."""
 
-    def __init__(self, n_nodes_round, lo, hi, node_nf, edge_nf, device):
+    def __init__(self, n_nodes_round, lo, hi, node_nf, edge_nf, device, keep_width=False):
         self.bs, self.N = len(n_nodes_round), int(max(n_nodes_round))
         self.lo, self.hi = lo, hi
         self.Nl = int(max(n_nodes_round[lo:hi])) if hi > lo else 0
+        if keep_width and hi > lo:                      # a model whose result depends on the padded width (CDGS): the round's width
+            self.Nl = self.N
         self.node_nf, self.edge_nf, self.device = node_nf, edge_nf, device
         self.nm, self.em = build_masks(n_nodes_round, self.N, 'cpu')
 
@@ -505,10 +507,11 @@ def _get_sampling_fn_2d(config, noise_scheduler, nodes_dist, batch_size, n_sampl
         time_steps = torch.linspace(noise_scheduler.T, eps, steps)      # host scalars, as in the 3-D path
         sampler = AncestralSampler_2D(noise_scheduler, time_steps, config.model.pred_data, config.model.self_cond)
 
-    def one_round(model, n_nodes, noise=None):
-        """n_nodes molecules (this process's share of a round) -> list of decoded molecule tuples."""
+    def one_round(model, n_nodes, noise=None, pad_to=None):
+        """n_nodes molecules (this process's share of a round) -> list of decoded molecule tuples.  pad_to: the padded width when it
+        is not the share's own maximum (parity shards of a model that depends on the padded width)."""
         bs = len(n_nodes)
-        max_n = int(max(n_nodes))
+        max_n = int(max(n_nodes)) if pad_to is None else int(pad_to)
         node_mask, edge_mask = build_masks(n_nodes, max_n, device)
         if noise is not None:
             z, edge_z = noise.node(), noise.edge()
@@ -598,15 +601,18 @@ def _get_sampling_fn_2d(config, noise_scheduler, nodes_dist, batch_size, n_sampl
             else:                                              # parity: replay the unsharded run's draws
                 from .dist import shard_range
                 indices = []
+                # CDGS normalises its edge state over the padded tensor: a molecule's scores depend on the width its batch is padded
+                # to, so a share of a round reproduces the unsharded run only at the ROUND's width (every other model: the share's own)
+                keep_width = _depends_on_padded_width(model)
                 for r in range(rounds):
                     n_nodes = n_nodes_all[r * batch_size:(r + 1) * batch_size]
                     lo, hi = shard_range(len(n_nodes), rank, world)
-                    noise = _ParityNoise2D(n_nodes.tolist(), lo, hi, node_nf, edge_nf, device)
+                    noise = _ParityNoise2D(n_nodes.tolist(), lo, hi, node_nf, edge_nf, device, keep_width=keep_width)
                     if hi == lo:                               # nothing of this round is ours: stay in step with the stream
                         for _ in range(1 if dpm else steps + 1):   # (the DPM-solver draws the initial state only)
                             noise.node(); noise.edge()
                         continue
-                    mols += one_round(model, n_nodes[lo:hi], noise)
+                    mols += one_round(model, n_nodes[lo:hi], noise, pad_to=int(max(n_nodes)) if keep_width else None)
                     indices += list(range(r * batch_size + lo, r * batch_size + hi))
                 sampling_fn_2D.last_indices = indices
         return mols                                            # caller gathers / shuffles
@@ -614,6 +620,14 @@ def _get_sampling_fn_2d(config, noise_scheduler, nodes_dist, batch_size, n_sampl
     sampling_fn_2D.last_indices = None
     sampling_fn_2D.last_decoded = decoded_rounds
     return sampling_fn_2D
+
+
+def _depends_on_padded_width(model):
+    """True for a model (possibly wrapped) that declares `depends_on_padded_width`: its result for a molecule is a function of the width N
+    the batch is padded to (CDGS: the reference's dense edge GroupNorm)."""
+    while hasattr(model, 'module'):
+        model = model.module
+    return bool(getattr(model, 'depends_on_padded_width', False))
 
 
 def full_edge_index(n_nodes, batch_size, device):

@@ -1,0 +1,148 @@
+"""Benchmark of one ancestral sampling step of the CDGS model (network + update) at the QM9 config, and of the baseline a user without
+the HIP path would run on the same GPU: the dense torch evaluation of the same network (tests/oracle_cdgs.py, float32) on the device,
+under the same sampler.  Both legs run in this one command on the same GPU, on the same batch.
+
+    python tools/bench_cdgs.py [--workload qm9|geom] [--batches 500,2000] [--steps 50] [--warmup 5] [--no-baseline] [--out-dir profiles]
+                               [--kernel-stats CSV --kernel-stats-steps K]
+
+Atom counts are drawn from the training histogram of the config's dataset (`qm9_with_h`, seed 42).  Timing as bench.py does it: warm-up,
+synchronise, `steps` sampler.step calls, synchronise.  Per batch size it writes profiles/cdgs_<workload>_b<B>.json: ms/step of both
+legs, ns per ordered pair, and the executed fraction of the 157.3 TFLOP/s fp32-MFMA peak.  Flops: 2 x 393 216 per edge row per block
+(lin_edge0 | lin_edge1 and the edge feed-forward) plus the edge readouts, embeddings and heads, plus the node GEMMs; the kernels walk
+every ordered pair on its own (nothing is halved) and the n diagonal rows of a molecule besides, which the count includes because they
+are executed.  The dense leg evaluates the whole padded batch at once: chunking it by molecules would change the padded width, and with
+it this model's result.
+--kernel-stats: the kernel table of a `rocprofv3 --kernel-trace --stats` run of this tool with --no-baseline (a run of its own); its kc_*
+rows per sampler step are added to the record of the largest batch.
+"""
+import argparse
+import csv
+import json
+import os
+import re
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+
+from jodo_amd import configs                                                      # noqa: E402
+from jodo_amd.diffusion.noise_schedule import NoiseScheduleVP                     # noqa: E402
+from jodo_amd.models import get_model_class, get_node_dist, load_dataset_info, deterministic_init_   # noqa: E402
+from jodo_amd.models.utils import sample_gaussian_with_mask, sample_symmetric_edge_feature_noise      # noqa: E402
+from jodo_amd.sampling import AncestralSampler_2D, build_masks                    # noqa: E402
+import oracle_cdgs as OC                                                          # noqa: E402
+
+WORKLOADS = {'qm9': 'vpsde_qm9_2d_cdgs', 'geom': 'vpsde_geom_2d_cdgs'}
+PEAK_TFLOPS = 157.3
+
+
+class Dense:
+    """The dense torch evaluation with the model's call signature."""
+
+    def __init__(self, sd, hp):
+        self.sd, self.hp = sd, hp
+
+    def __call__(self, t, x, node_mask, edge_mask, context=None, **kw):
+        return OC.forward(self.sd, self.hp, t, x, node_mask, edge_mask, kw['edge_x'])
+
+
+def time_steps(sampler, model, z, edge_z, node_mask, edge_mask, warmup, steps):
+    st = sampler.init_state(z, edge_z)
+    with torch.no_grad():
+        for i in range(warmup):
+            st = sampler.step(model, i, st, node_mask, edge_mask, None)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(warmup, warmup + steps):
+            st = sampler.step(model, i, st, node_mask, edge_mask, None)
+        torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / steps * 1e3, st
+
+
+def flops_per_step(model, n_nodes):
+    D, L = model.nf, model.n_layers
+    cat = 2 * D // L
+    catp = (cat + 31) // 32 * 32
+    KA, KE = (L * catp + 154 + 63) // 64 * 64, (L * catp + 192 + 63) // 64 * 64
+    Nn, R = sum(n_nodes), sum(n * n for n in n_nodes)
+    B = len(n_nodes)
+    pair_block = 393216 + D * catp                                           # E0 | E1, edge feed-forward, readout (padded as run)
+    node_block = 2 * D * D + 3 * D * D + 2 * (2 * D * D) + D * catp + 2 * (2 * D * D)   # gin_nn, q k v, node FF, readout, FF(h_i)
+    macs = R * (L * pair_block + D * D + KE * 2 * D + 2 * D * D + D * 32)
+    macs += Nn * (L * node_block + D * D + KA * D + D * (D // 2) + (D // 2) * 32)
+    macs += B * (D * 2 * D + 2 * D * D + D * 2 * D * L)
+    return 2 * macs, 2 * R * L * 393216
+
+
+def kernel_split(csv_path, sampler_steps):
+    """kc_* rows of a rocprofv3 kernel-stats table -> {kernel: ms per sampler step}"""
+    out = {}
+    with open(csv_path) as f:
+        for row in csv.DictReader(f):
+            name = row['Name']
+            if 'kc_' not in name:
+                continue
+            m = re.search(r'(kc_[a-z0-9_]+)(<[^>]*>|ILi\dE)?', name)
+            key = (m.group(1) + (m.group(2) or '').replace(' ', '')) if m else name
+            out[key] = round(out.get(key, 0.0) + float(row['TotalDurationNs']) / sampler_steps * 1e-6, 4)
+    return dict(sorted(out.items(), key=lambda kv: -kv[1]))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--workload', default='qm9', choices=sorted(WORKLOADS))
+    ap.add_argument('--batches', default='500,2000')
+    ap.add_argument('--steps', type=int, default=50)
+    ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--no-baseline', action='store_true')
+    ap.add_argument('--out-dir', default=os.path.join(ROOT, 'profiles'))
+    ap.add_argument('--kernel-stats', default=None)
+    ap.add_argument('--kernel-stats-steps', type=int, default=None, help='sampler steps (warm-up included) of the profiled run')
+    args = ap.parse_args()
+    dev = torch.device('cuda:0')
+    cfg = configs.get(WORKLOADS[args.workload])
+    cfg.device = dev
+    model = deterministic_init_(get_model_class('CDGS')(cfg), seed=42).to(dev).eval()
+    dense = Dense({k: v.detach().clone() for k, v in model.state_dict().items()}, OC.hparams(cfg))
+    ns = NoiseScheduleVP(cfg.sde.schedule, continuous_beta_0=cfg.sde.continuous_beta_0, continuous_beta_1=cfg.sde.continuous_beta_1)
+    sampler = AncestralSampler_2D(ns, torch.linspace(ns.T, 1e-3, cfg.sampling.steps), cfg.model.pred_data, cfg.model.self_cond)
+    dist = get_node_dist(load_dataset_info(cfg.data.info_name))
+    batches = [int(b) for b in args.batches.split(',')]
+    for B in batches:
+        torch.manual_seed(42)
+        n_nodes = dist.sample(B).tolist()
+        N = int(max(n_nodes))
+        nm, em = build_masks(n_nodes, N, dev)
+        z = sample_gaussian_with_mask((B, N, cfg.data.atom_types), dev, nm)
+        edge_z = sample_symmetric_edge_feature_noise(B, N, cfg.model.edge_ch, em)
+        pairs = sum(n * (n - 1) for n in n_nodes)
+        flops, pair_flops = flops_per_step(model, n_nodes)
+        ms, st = time_steps(sampler, model, z, edge_z, nm, em, args.warmup, args.steps)
+        out = dict(tool='tools/bench_cdgs.py', workload=args.workload, config=WORKLOADS[args.workload], batch=B, padded_width=N,
+                   atoms=sum(n_nodes), ordered_pairs=pairs, edge_rows_executed=sum(n * n for n in n_nodes), steps=args.steps,
+                   warmup=args.warmup, hip_ms_per_step=round(ms, 3), hip_ns_per_ordered_pair=round(ms * 1e6 / pairs, 2),
+                   flops_per_step=flops, pair_chain_flops_per_step=pair_flops, hip_tflops=round(flops / ms * 1e-9, 2),
+                   hip_fraction_of_fp32_mfma_peak=round(flops / ms * 1e-9 / PEAK_TFLOPS, 4), peak_tflops=PEAK_TFLOPS,
+                   finite=bool(torch.isfinite(st['x']).all() and torch.isfinite(st['edge_x']).all()))
+        if not args.no_baseline:
+            dms, dst = time_steps(sampler, dense, z, edge_z, nm, em, min(args.warmup, 2), args.steps)
+            out.update(dense_torch_ms_per_step=round(dms, 3), dense_torch_ns_per_ordered_pair=round(dms * 1e6 / pairs, 2),
+                       hip_over_dense_time=round(ms / dms, 4), hip_not_slower_than_dense=bool(ms <= dms),
+                       dense_padded_positions=B * N * N, dense_finite=bool(torch.isfinite(dst['x']).all()))
+        if args.kernel_stats and B == max(batches):
+            out['kernel_ms_per_step'] = kernel_split(args.kernel_stats, args.kernel_stats_steps or args.warmup + args.steps)
+            out['kernel_stats_source'] = os.path.basename(args.kernel_stats)
+        os.makedirs(args.out_dir, exist_ok=True)
+        with open(os.path.join(args.out_dir, 'cdgs_%s_b%d.json' % (args.workload, B)), 'w') as f:
+            json.dump(out, f, indent=1)
+        print(json.dumps(out), flush=True)
+        del z, edge_z, st
+        torch.cuda.empty_cache()
+
+
+if __name__ == '__main__':
+    main()
