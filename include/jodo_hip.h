@@ -800,6 +800,41 @@ int jodo_cdgs_forward(const jodo_cdgs_cfg* cfg, int B, int N, const int32_t* n_n
                       const int64_t* woff, int n_woff, const float* t, const float* x, const float* edge_x, float* out_x, float* out_e,
                       void* workspace, int max_blocks, void* stream);
 
+/* ---- CDGS training (csrc/cdgs_train.hip): forward with kept activations + the gradient of every parameter ----
+ * jodo_cdgs_train_* mirror jodo_train2d_* one for one: tensors by name in their PyTorch layouts at create (every tensor of the
+ * state_dict, the GINE `local_model.eps` buffers included; a leading "module." is accepted), params_dev / grads_dev pointer tables in
+ * that order, explicit stream, caller-owned workspace that carries the kept tensors from forward to backward, gradients fully written
+ * (gaps under 16 bytes between two gradient buffers included) in a fixed launch order without atomics: two backward calls on the same
+ * activations give the same bits.  The eps buffers are inputs: their value is used, their grads_dev entry must be NULL.
+ * Layout: the reference's dense padded tensors, node row b N + i, edge row (b N + r) N + c, padded and diagonal rows included; the
+ * edge feed-forward, its residual and norm2_edge run over all B N^2 rows, for every dropout probability.  Any N; B N^2 <= 2^30.
+ * Dropout (train_common.h drop_mul): site = 8 l + {1 h_local, 2 h_attn, 3 node FF hidden, 4 node FF out, 5 edge FF hidden, 6 edge FF
+ * out}, element = flat index of the reference's own dense tensor.  Supported: nf a multiple of 32 with GroupNorm groups of 8 channels
+ * (nf 256), n_heads dividing nf, 1 <= n_layers <= 16, edge_ch >= 2.
+ * Inputs: time_freq [nf / 2] (the sinusoid's frequencies, caller-made as for jodo_cdgs_pack_weights_host), t [B], x [B, N, atom_ch],
+ * edge_x [B, N, N, edge_ch]; the backward reads x and edge_x again (embedding weight gradients).  No input gradients.
+ * jodo_cdgs_train_set_option: option 2 only (accepted for parity; the forward keeps the same tensors either way).
+ * jodo_cdgs_train_debug_locate: 0 = h after `layer` blocks [B N, nf], 1 = e after `layer` blocks [B N^2, nf], 2 = alpha of block
+ * `layer` [B N^2, n_heads], 3 = xhat of its norm2_edge [B N^2, nf]. */
+typedef struct jodo_cdgs_train jodo_cdgs_train;
+int jodo_cdgs_train_create(const jodo_cdgs_cfg* cfg, int B, int N, const int32_t* n_nodes_host, const jodo_tensor* params, int n_params,
+                           jodo_cdgs_train** out);
+void jodo_cdgs_train_destroy(jodo_cdgs_train* t);
+size_t jodo_cdgs_train_desc_bytes(const jodo_cdgs_train* t);
+size_t jodo_cdgs_train_workspace_bytes(const jodo_cdgs_train* t);
+const void* jodo_cdgs_train_desc_host(const jodo_cdgs_train* t);
+int jodo_cdgs_train_upload(jodo_cdgs_train* t, void* desc_dev, void* stream);
+int jodo_cdgs_train_set_option(jodo_cdgs_train* t, int option, int value);
+int jodo_cdgs_train_debug_locate(const jodo_cdgs_train* t, int what, int layer, size_t* byte_offset, size_t* count);
+/* tests: out[rows, F] = the dropout multipliers of rows row0 .. row0 + rows - 1 of a [., F] tensor at `site`, element row * F + f */
+int jodo_cdgs_train_debug_drop(float dropout_p, uint64_t seed, int site, int64_t row0, int rows, int F, float* out, void* stream);
+int jodo_cdgs_train_forward(jodo_cdgs_train* t, const void* desc_dev, const float* const* params_dev, int n_params, const float* time_freq,
+                            const float* t_in, const float* x, const float* edge_x, float dropout_p, uint64_t seed, float* out_x, float* out_e,
+                            void* workspace, void* stream);
+int jodo_cdgs_train_backward(jodo_cdgs_train* t, const void* desc_dev, const float* const* params_dev, float* const* grads_dev, int n_params,
+                             const float* x, const float* edge_x, const float* d_out_x, const float* d_out_e, float dropout_p, uint64_t seed,
+                             void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,7 @@
 #include "../../include/jodo_hip.h"
 #include "jodo_hip_internal.h"
 #include "dgt_device.h"
+#include "cdgs_common.h"
 
 using namespace jd;
 
@@ -186,8 +187,7 @@ __device__ __forceinline__ float gn8(float v, float gamma, float beta) {
 // ---- prologue -----------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void kc_time(KC A) {                       // sinusoid of t * 999: [sin (128) | cos (128)]
     const int b = blockIdx.x, c = threadIdx.x;
-    const float arg = (A.t[b] * 999.f) * A.W[A.wg[JCG_FREQ] + (c & 127)];
-    A.tin[(size_t)b * DC + c] = c < 128 ? sinf(arg) : cosf(arg);
+    A.tin[(size_t)b * DC + c] = jcdgs::sinusoid(A.t[b], A.W + A.wg[JCG_FREQ], c, DC / 2);
 }
 
 // Random-walk features of one molecule: AD = adj / (deg + 1e-8), powers AD^2 .. AD^(K+1) through two buffers, the landing probabilities
@@ -200,7 +200,7 @@ __global__ __launch_bounds__(256) void kc_rw(KC A) {
     int* cnt = A.cnt + eoff;
     for (int idx = threadIdx.x; idx < nn; idx += 256) {
         const int r = idx / n, c = idx % n;
-        ad[idx] = (r != c && A.edge_x[(((size_t)b * A.N + r) * A.N + c) * A.ch] >= 0.f) ? 1.f : 0.f;
+        ad[idx] = jcdgs::adjacent(r != c, A.edge_x[(((size_t)b * A.N + r) * A.N + c) * A.ch]) ? 1.f : 0.f;
     }
     __syncthreads();
     for (int r = threadIdx.x; r < n; r += 256) {

@@ -5,8 +5,10 @@ Same constructor argument, parameter names / shapes / registration order (one `a
 `strict=True` loading, the 4-D conv weights and the GINE `eps` buffers included) and the same call as the reference class:
     model(t, x, node_mask, edge_mask, context=None, edge_x=...) -> (atom_score [B,N,atom_types], bond_score [B,N,N,edge_ch])
 The arithmetic runs in libjodo_hip.so (csrc/cdgs_forward.hip, `jodo_cdgs_forward`) on the current HIP stream: the weights are packed
-once (csrc/cdgs_pack.cpp), a descriptor and a workspace are built per batch of atom counts.  Inference only, exact fp32; there is no
-CPU or eager fallback, no training path, no split-bf16 form and no graph replay — those raise.
+once (csrc/cdgs_pack.cpp), a descriptor and a workspace are built per batch of atom counts.  Exact fp32; there is no CPU or eager
+fallback, no split-bf16 form and no graph replay — those raise.  Training is opt-in: with `hip_training = True` (set by
+jodo_amd.losses.get_step_fn) a grad-enabled call runs csrc/cdgs_train.hip on the live parameters, keeps the activations, and
+loss.backward() returns every parameter's gradient (jodo_amd/train.py TrainEngineCDGS); unset, a grad-enabled call raises.
 
 The edge GroupNorm of the reference normalises the dense padded tensor, so a molecule's scores depend on the width N the caller
 padded the batch to; the kernels reproduce that from the tensors' N.
@@ -100,7 +102,8 @@ class CDGS(nn.Module):
         nf, L, rw = m.nf, m.n_layers, m.rw_depth
         self.nf, self.n_layers, self.rw_depth = nf, L, rw
         self.atom_ch, self.edge_ch = int(d.atom_types), int(m.edge_ch)
-        self.dropout_p = m.dropout                # identity at inference; kept for config parity
+        self.dropout_p = m.dropout                # identity at inference; active in the training path under model.train()
+        self.hip_training = False                 # opt-in: a grad-enabled call goes to csrc/cdgs_train.hip (get_step_fn sets it)
         self._cfg_struct = _Cfg(nf, L, m.n_heads, self.atom_ch, self.edge_ch, rw)
 
         # ---- parameter tree: one list, reference construction order ----
@@ -213,12 +216,19 @@ class CDGS(nn.Module):
             raise NotImplementedError("split_bf16 is not implemented for CDGS (exact fp32 only)")
         inputs_want_grad = any(t_ is not None and t_.requires_grad for t_ in (x, edge_x, t))
         wants_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
-        if torch.is_grad_enabled() and (wants_grad or inputs_want_grad):
-            raise NotImplementedError("CDGS is inference only: call it under torch.no_grad() (training / backward for this model is "
-                                      "not implemented)")
+        if not self.hip_training and torch.is_grad_enabled() and (wants_grad or inputs_want_grad):
+            raise NotImplementedError("CDGS is inference only: call it under torch.no_grad(), or set model.hip_training = True for the HIP "
+                                      "training path (jodo_amd.losses.get_step_fn does)")
+        if self.hip_training and torch.is_grad_enabled() and inputs_want_grad:
+            raise RuntimeError("the HIP CDGS returns parameter gradients only: detach the inputs (the reference's loss needs no input "
+                               "gradient)")
         B, N, dims = x.shape
         if dims != self.atom_ch or edge_x.shape != (B, N, N, self.edge_ch) or t.shape != (B,):
             raise ValueError("shape mismatch: x %s edge_x %s t %s" % (tuple(x.shape), tuple(edge_x.shape), tuple(t.shape)))
+        if self.hip_training and (wants_grad or (self.training and self.dropout_p > 0)):
+            # training path (csrc/cdgs_train.hip): activations kept for loss.backward(); under model.train() dropout is active in a
+            # no-grad call too, as in the reference
+            return self._forward_train(t, x, edge_x, node_mask, edge_mask, wants_grad)
         dev = x.device
         f32 = lambda v: v.detach().to(torch.float32).contiguous()
         x_, ex_, t_ = f32(x), f32(edge_x), f32(t)
@@ -233,6 +243,65 @@ class CDGS(nn.Module):
                    'jodo_cdgs_forward')
         self._last_plan = plan
         return out_x, out_e
+
+    # -- training path (opt-in: hip_training) ------------------------------------------------------------
+    def _train_engine(self, node_mask, edge_mask, device):
+        """One TrainEngineCDGS (jodo_cdgs_train handle + device table) per batch of atom counts and padded width, keyed by the counts
+        themselves like DGT_concat_2D._train_engine; all engines of the module share its two activation workspaces."""
+        from ..train import TrainEngineCDGS
+        B, N = node_mask.shape[0], node_mask.shape[1]
+        last = self.__dict__.get('_train_last')
+        if (last is not None and last[0] is node_mask and last[1] == node_mask._version and last[2] is edge_mask
+                and last[3] == edge_mask._version):
+            return last[4]
+        hint = getattr(node_mask, '_jodo_counts', None)          # counts the loss already has on the host (losses.process_batch_2D)
+        if hint is not None and len(hint) == B:
+            n_host = np.ascontiguousarray(hint, dtype=np.int32)
+        else:
+            nm = node_mask.reshape(B, N)
+            n_nodes = nm.sum(1).round().to(torch.int32)
+            prefix = (torch.arange(N, device=nm.device).unsqueeze(0) < n_nodes.unsqueeze(1))
+            em = edge_mask.reshape(B, N, N)
+            want = prefix.unsqueeze(1) & prefix.unsqueeze(2) & (~torch.eye(N, dtype=torch.bool, device=nm.device))
+            ok = torch.stack([(prefix.to(nm.dtype) == nm).all(), (want.to(em.dtype) == em).all()]).to(torch.int32)
+            host = torch.cat([n_nodes, ok]).cpu().numpy()        # counts and both mask checks in one transfer
+            if not host[B]:
+                raise ValueError("node_mask must be a prefix mask (real atoms first), as the samplers build it")
+            if not host[B + 1]:
+                raise ValueError("edge_mask must be node_mask x node_mask with the diagonal removed")
+            n_host = np.ascontiguousarray(host[:B])
+        key = (str(device), N) + tuple(int(v) for v in n_host)
+        cache = self.__dict__.setdefault('_train_engines', {})
+        eng = cache.pop(key, None)
+        if eng is None:
+            named = self.__dict__.get('_train_named')
+            if named is None:
+                named = self.__dict__['_train_named'] = TrainEngineCDGS.named_table([(k, tuple(v.shape)) for k, v in self.state_dict().items()])
+            pool = self.__dict__.setdefault('_train_pool', TrainEngineCDGS.new_pool())
+            eng = TrainEngineCDGS(self._cfg_struct, n_host, N, named, device, pool=pool)
+            while len(cache) >= 16:
+                cache.pop(next(iter(cache)))
+        else:
+            eng.check_free()
+        cache[key] = eng                                         # most recently used last
+        self.__dict__['_train_last'] = (node_mask, node_mask._version, edge_mask, edge_mask._version, eng)
+        return eng
+
+    def _forward_train(self, t, x, edge_x, node_mask, edge_mask, wants_grad):
+        from ..train import cdgs_autograd
+        f32 = lambda v: v.detach().to(torch.float32).contiguous()
+        eng = self._train_engine(node_mask, edge_mask, x.device)
+        p = float(self.dropout_p) if self.training else 0.0
+        # dropout masks: counter-based, keyed by a seed drawn from torch's generator (so torch.manual_seed reproduces a step)
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if p > 0 else 0
+        freq = self.__dict__.get('_train_freq')
+        if freq is None or freq.device != x.device:
+            freq = self.__dict__['_train_freq'] = self._time_freq().to(x.device)
+        # the live tensors on every call, state_dict order: parameters and the GINE eps buffers (inputs without a gradient)
+        tensors = list(self.state_dict(keep_vars=True).values())
+        if wants_grad:
+            return cdgs_autograd(eng, p, seed, freq, f32(t), f32(x), f32(edge_x), tensors)
+        return eng.forward([q.detach().contiguous() for q in tensors], freq, f32(t), f32(x), f32(edge_x), p, seed)
 
     # -- tests: the state inside the workspace after the last call ------------------------------------
     def debug_state(self):

@@ -1,6 +1,7 @@
 """Python plumbing of the training side behind the C ABI; device tensors in, device tensors out, no CPU
 fallback.
 
+  TrainEngineCDGS / cdgs_autograd  the same for CDGS (csrc/cdgs_train.hip), behind models/cdgs.py when `hip_training` is set
   TrainEngineEGNN / egnn_autograd  the same for the property classifier (csrc/egnn_train.hip), behind cond_gen/model.py when `hip_training` is set
   TrainEngine2D / dgt2d_autograd   the same for DGT_concat_2D (csrc/dgt2d_train.hip), behind models/dgt2d.py when `hip_training` is set
   TrainEngine / dgt_autograd   the whole score network under autograd: jodo_train_forward keeps the activations,
@@ -258,6 +259,107 @@ class TrainEngineEGNN(TrainEngine):
         return grads
 
 
+class TrainEngineCDGS(TrainEngine):
+    """The same for CDGS (csrc/cdgs_train.hip): `cfg_struct` is a jodo_cdgs_cfg, `named_shapes` lists every tensor of the state_dict
+    (the GINE `local_model.eps` buffers included: inputs without a gradient), the inputs are t [B], x [B, N, atom_ch] and
+    edge_x [B, N, N, edge_ch] plus the sinusoid's frequency table.  The workspace holds the reference's dense padded tensors (B N^2
+    edge rows); `check_free` refuses a workspace larger than the device has free before anything is allocated.  Pool, slots and the
+    pinned staging ring are TrainEngine's.  debug_fetch selectors: 0 = h after `layer` blocks [B N, nf], 1 = e after `layer` blocks
+    [B N^2, nf], 2 = alpha of block `layer` [B N^2, n_heads], 3 = xhat of its norm2_edge [B N^2, nf]."""
+
+    _abi = 'jodo_cdgs_train'
+
+    def __init__(self, *args, **kwargs):
+        if kwargs.get('lib') is not None:
+            capi.bind_cdgs_train(kwargs['lib'])
+        super().__init__(*args, **kwargs)
+        names =[self._named['arr'][i].name.decode() for i in range(self.n_params)]
+        self.is_buffer = [n.endswith('local_model.eps') for n in names]
+        self.check_free()
+
+    def _available(self, dev, releasing=0):
+        """Bytes a new allocation on `dev` can get: what the driver reports free, what torch's allocator holds without using, and
+        `releasing`, the size of a buffer that is dropped before the allocation."""
+        return int(torch.cuda.mem_get_info(dev)[0]) + int(torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)) + int(releasing)
+
+    def _refuse(self, avail):
+        raise RuntimeError("CDGS training: the activation workspace of this batch (B = %d, N = %d: %d dense tile rows) needs %d bytes, "
+                           "the device has %d bytes free; use a smaller batch" % (self.B, self.N, self.B * self.N * self.N, self.ws_bytes, avail))
+
+    def check_free(self):
+        """Raise at creation when no slot of the pool could ever hold this batch (no recompute or checkpointing form exists to fall back
+        to).  The allocation itself is checked again, at its real size, in _take_slot."""
+        dev = torch.device(self.device)
+        if dev.type != 'cuda':
+            return
+        bufs = [s_['buf'].numel() for s_ in self.pool['slots'] if s_['buf'] is not None and s_['buf'].device == dev]
+        if bufs and max(bufs) >= self.ws_bytes:
+            return
+        avail = self._available(dev, min(bufs) if len(bufs) == len(self.pool['slots']) else 0)     # a full pool grows by replacing a buffer
+        if self.ws_bytes > avail:
+            self._refuse(avail)
+
+    def _take_slot(self, device, keep):
+        """TrainEngine._take_slot with the growth checked at the size that is really allocated: the slot the base class will choose is
+        grown here, with the 20 % headroom when that fits, without it when only the exact size fits, and refused (bytes wanted, bytes
+        free) when neither does; the base class then finds the buffer large enough."""
+        dev = torch.device(device)
+        if dev.type == 'cuda':
+            free = [s_ for s_ in self.pool['slots'] if not s_['live']]
+            slot = max(free, key=lambda s_: s_['stamp']) if free else min(self.pool['slots'], key=lambda s_: s_['stamp'])
+            buf = slot['buf']
+            if buf is None or buf.numel() < self.ws_bytes or buf.device != dev:
+                releasing = buf.numel() if buf is not None and buf.device == dev else 0
+                avail = self._available(dev, releasing)
+                want = self.ws_bytes if buf is None else int(self.ws_bytes * 1.2)
+                if want > avail:
+                    want = self.ws_bytes
+                if want > avail:
+                    self._refuse(avail)
+                slot['buf'] = buf = None                          # release before growing
+                slot['buf'] = torch.zeros(want, dtype=torch.uint8, device=dev)
+        return super()._take_slot(device, keep)
+
+    def forward(self, tensors, time_freq, t, x, edge_x, dropout_p, seed, keep=False):
+        """tensors: contiguous float32 tensors in the order of `named_shapes` (parameters and buffers).  Returns (atom_score, bond_score);
+        the kept tensors stay in a workspace slot of the pool (self.stamp names it)."""
+        assert len(tensors) == self.n_params
+        slot = self._take_slot(x.device, keep)
+        self._slot, self.stamp = slot, slot['stamp']
+        out_x, out_e = torch.empty_like(x), torch.empty_like(edge_x)
+        self._check(self._fn('forward')(
+            self.handle, capi.ptr(self.desc), self._ptrs(tensors), self.n_params, capi.ptr(time_freq), capi.ptr(t), capi.ptr(x), capi.ptr(edge_x),
+            ctypes.c_float(dropout_p), ctypes.c_uint64(seed), capi.ptr(out_x), capi.ptr(out_e), capi.ptr(slot['buf']), self._stream()),
+            self._abi + '_forward')
+        return out_x, out_e
+
+    def backward(self, tensors, x, edge_x, d_out_x, d_out_e, dropout_p, seed, stamp=None):
+        """Gradients of every PARAMETER of `tensors` (state_dict order, the buffers skipped) for the forward `stamp` (default: this
+        engine's last forward)."""
+        slot = self.slot_of(self.stamp if stamp is None else stamp)
+        if slot is None:
+            raise RuntimeError("the activations of this forward were overwritten by later training-path forwards of the same module "
+                               "(%d activation workspaces per module, INTEGRATION.md §5); call backward earlier" % len(self.pool['slots']))
+        from .optim import carve, slice_offsets
+        ps = [p for p, buf in zip(tensors, self.is_buffer) if not buf]
+        lay = self.__dict__.get('_grad_layout')
+        if lay is None:
+            offs, total = slice_offsets([p.numel() for p in ps])
+            lay = self._grad_layout = ([tuple(p.shape) for p in ps], offs, total)
+        flat = torch.empty(lay[2], dtype=torch.float32, device=ps[0].device)
+        tail = lay[1][-1] + ps[-1].numel()
+        if tail != lay[2]:
+            flat[tail:].zero_()
+        grads = carve(flat, lay[0], lay[1])
+        it = iter(grads)
+        slots = (ctypes.c_void_p * self.n_params)(*[None if buf else next(it).data_ptr() for buf in self.is_buffer])
+        self._check(self._fn('backward')(
+            self.handle, capi.ptr(self.desc), self._ptrs(tensors), slots, self.n_params, capi.ptr(x), capi.ptr(edge_x), capi.ptr(d_out_x),
+            capi.ptr(d_out_e), ctypes.c_float(dropout_p), ctypes.c_uint64(seed), capi.ptr(slot['buf']), self._stream()), self._abi + '_backward')
+        slot['live'] = False
+        return grads
+
+
 def release_slot(pool, stamp):
     for s_ in pool['slots']:
         if s_['stamp'] == stamp:
@@ -304,6 +406,31 @@ def dgt_autograd(engine, dropout_p, seed, xh, edge_x, cond_x, cond_edge_x, noise
 def dgt2d_autograd(engine, dropout_p, seed, xh, edge_x, cond_x, cond_edge_x, noise_level, params):
     """The 2-D score network (a TrainEngine2D) as the same autograd node: no context."""
     return _DGTTrainFn.apply(engine, dropout_p, seed, xh, edge_x, cond_x, cond_edge_x, noise_level, None, *params)
+
+
+class _CDGSTrainFn(torch.autograd.Function):
+    """CDGS as one autograd node: (atom_score, bond_score) from t, x, edge_x (no gradient) and the parameters; `is_param` tells the
+    parameters from the buffers among `tensors` (state_dict order), whose gradients come from jodo_cdgs_train_backward."""
+
+    @staticmethod
+    def forward(ctx, engine, dropout_p, seed, time_freq, t, x, edge_x, *tensors):
+        ts = [p.detach().contiguous() for p in tensors]
+        out_x, out_e = engine.forward(ts, time_freq, t, x, edge_x, dropout_p, seed, keep=True)
+        ctx.engine, ctx.dropout_p, ctx.seed, ctx.ts, ctx.x, ctx.edge_x = engine, dropout_p, seed, ts, x, edge_x
+        ctx.stamp = engine.stamp
+        ctx.slot_guard = _SlotGuard(engine.pool, engine.stamp)
+        return out_x, out_e
+
+    @staticmethod
+    def backward(ctx, d_out_x, d_out_e):
+        grads = iter(ctx.engine.backward(ctx.ts, ctx.x, ctx.edge_x, d_out_x.contiguous(), d_out_e.contiguous(), ctx.dropout_p, ctx.seed,
+                                         stamp=ctx.stamp))
+        return (None,) * 7 + tuple(None if buf else next(grads) for buf in ctx.engine.is_buffer)
+
+
+def cdgs_autograd(engine, dropout_p, seed, time_freq, t, x, edge_x, tensors):
+    """(atom_score, bond_score) of a TrainEngineCDGS under autograd; tensors: the module's parameters and buffers in state_dict order."""
+    return _CDGSTrainFn.apply(engine, dropout_p, seed, time_freq, t, x, edge_x, *tensors)
 
 
 class _EGNNTrainFn(torch.autograd.Function):
