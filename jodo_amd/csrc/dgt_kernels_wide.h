@@ -293,44 +293,45 @@ __global__ __launch_bounds__(64, 1) void k_node_post(KArgs A) {
 // add up to the LayerNorm mean of a directed edge.  One (strip, piece) item per wave: 2 x n_strips items.
 // Rotated statistics (rot_active): the rows are Q P R / Q P C; A' = F (Q P R) with the folded F = W0 diag(1 + sc) Q^T of this
 // forward (k_fold_coord, A.ffold) — no scaling, no means (P removed them).
+// The item's rows go through buffer loads (BRow, dgt_device.h): all of them are requested at the item top, followed by the first
+// weight quads, and one wait serves both — as plain global loads hipcc sank them towards the first MFMAs.  Of the per-node
+// descriptors only node_b is read, and only where the modulation row is needed (QM9 B = 2500: k_node_ab 128 -> 121 us as a launch of
+// its own, the two k_node_mix launches of a block 277 + 48 -> 263 + 43 us together with the Gram tiles' change below).
 template <int D>
 __device__ __forceinline__ void node_ab_body(const KArgs& A, int item) {
     if (D != 256 && !A.flags[FLAG_UNIFORM_T]) return;       // nf = 384 pushes coord_mlp.0 through only with a shared modulation row
     using X = Dim<D>;
     const int lane = threadIdx.x & 63, j = lane & 31, half = lane >> 5;
-    const int strip = item >> 1, piece = item & 1;
-    const LaneNode L = lane_node(A, strip, j);
+    const int strip = item >> 1, piece = item & 1, v = strip * 32 + j;
     const bool rot = rot_active(A);
-    const float* qsc = mod_row(A, L.b) + A.mod_base + X::M_EQUI + D;       // equi_update.time_mlp: (shift, scale)
-    const TRow src = trow(piece == 0 ? A.wrow : A.wcol, X::ND, L.v, half);
+    // (the base pointer is selected, not the descriptor: a select between two buffer resources went through scratch)
+    const BRow src = brow(piece == 0 ? A.wrow : A.wcol, X::ND, v, half);
+    const float* wbase = rot ? A.ffold + (size_t)A.layer * D * D : A.W;
+    const WSrc ws = make_wsrc(wbase, lane);
+    const unsigned o0 = rot ? 0u : (unsigned)(A.wb[JB_C0_W] * 4);
     float x[X::HD];
-    float sum = 0.f;
     if (rot) {                                              // (one branch around two straight-line loops: a branch per block
 #pragma unroll                                              //  serialised the row loads — 116 -> 161 us per launch)
         for (int b = 0; b < X::ND; ++b) {
             float t[16];
-            load16T(src, b, t);
+            bload16(src, b, t);
 #pragma unroll
             for (int s = 0; s < 16; ++s) x[b * 16 + s] = t[s];
         }
     } else {
+        const float* qsc = mod_row(A, A.pd.node_b[v]) + A.mod_base + X::M_EQUI + D;       // equi_update.time_mlp: (shift, scale)
+        float sum = 0.f;
 #pragma unroll
         for (int b = 0; b < X::ND; ++b) {
             float t[16], g[16];
-            load16T(src, b, t);
+            bload16(src, b, t);
             load16(qsc + b * 32 + half * 16, g);
 #pragma unroll
             for (int s = 0; s < 16; ++s) { sum += t[s]; x[b * 16 + s] = t[s] * (1.f + g[s]); }
         }
-    }
-    if (!rot) {
         const float red = pair_sum(sum);
-        if (half == 0) A.rmean[(size_t)L.v * 2 + piece] = red * (1.f / D);
+        if (half == 0) A.rmean[(size_t)v * 2 + piece] = red * (1.f / D);
     }
-    // (the base pointer is selected, not the descriptor: a select between two buffer resources went through scratch)
-    const float* wbase = rot ? A.ffold + (size_t)A.layer * D * D : A.W;
-    const WSrc ws = make_wsrc(wbase, lane);
-    const unsigned o0 = rot ? 0u : (unsigned)(A.wb[JB_C0_W] * 4);
     WPipe<X::PG> wp;
     wpipe_prime(wp, ws, o0);
     float* dst = piece == 0 ? A.ua : A.ub;
@@ -341,7 +342,7 @@ __device__ __forceinline__ void node_ab_body(const KArgs& A, int item) {
         float r[16];
 #pragma unroll
         for (int s = 0; s < 16; ++s) r[s] = acc[s];
-        store16T(dst, X::ND, L.v, half, b, r);
+        store16T(dst, X::ND, v, half, b, r);
     }
 }
 template <int D>
@@ -376,6 +377,22 @@ __device__ __forceinline__ void node_gram_body(const KArgs& A, int tile) {
     const float4* ma = reinterpret_cast<const float4*>(A.wcol) + (size_t)(refa >> 5) * X::ND * 256 + (refa & 31) + 32 * half;
     const float4* mc = reinterpret_cast<const float4*>(A.wcol) + (size_t)(refc >> 5) * X::ND * 256 + (refc & 31) + 32 * half;
     const float sgn = centre ? 1.f : 0.f;
+    // Descriptors of the epilogue's rows, read before the MFMA chain: accumulator register s of half h holds row 8 (s / 4) + 4 h + s % 4;
+    // irow = that atom's index inside the molecule, -1 = no store.  (Read inside the store loop, every register paid dependent loads
+    // behind a branch: k_node_gram 34 -> 30 us per launch at QM9 B = 2500.)
+    int irow[16];
+    {
+        int na_[16], noffa[16];                             // all 48 loads first, no branch between them
+#pragma unroll
+        for (int s = 0; s < 16; ++s) {
+            const int va = sa * 32 + 8 * (s >> 2) + 4 * half + (s & 3);
+            na_[s] = A.pd.node_n[va]; noffa[s] = A.pd.node_noff[va]; irow[s] = A.pd.node_i[va];
+        }
+#pragma unroll
+        for (int s = 0; s < 16; ++s) irow[s] = ((nc > 0) & (na_[s] > 0) & (noffa[s] == noffc)) ? irow[s] : -1;
+    }
+#pragma unroll
+    for (int s = 0; s < 16; ++s) asm volatile("" : "+v"(irow[s]));          // here, not sunk into the store loop
     f32x16 acc = zero16();
     float na[4] = {0.f, 0.f, 0.f, 0.f}, nc4[4] = {0.f, 0.f, 0.f, 0.f};      // squared norms of this lane's halves of a', c'
 #pragma unroll
@@ -396,11 +413,10 @@ __device__ __forceinline__ void node_gram_body(const KArgs& A, int tile) {
     const float nC = pair_sum((nc4[0] + nc4[1]) + (nc4[2] + nc4[3]));
     const size_t eoffc = (size_t)A.pd.node_eoff[vc];
 #pragma unroll
-    for (int s = 0; s < 16; ++s) {                          // accumulator register s of half h holds row 8 (s / 4) + 4 h + s % 4
-        const int m = 8 * (s >> 2) + 4 * half + (s & 3), va = sa * 32 + m;
+    for (int s = 0; s < 16; ++s) {
+        const int m = 8 * (s >> 2) + 4 * half + (s & 3);
         const float nRa = __shfl(nR, m);
-        if (nc > 0 && A.pd.node_n[va] > 0 && A.pd.node_noff[va] == noffc)
-            A.gramE[eoffc + (size_t)A.pd.node_i[va] * nc + ic] = nRa + nC + 2.f * acc[s];
+        if (irow[s] >= 0) A.gramE[eoffc + (size_t)irow[s] * nc + ic] = nRa + nC + 2.f * acc[s];
     }
 }
 template <int D>
