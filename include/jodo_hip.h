@@ -799,6 +799,36 @@ int jodo_cdgs_fill_desc(const jodo_cdgs_cfg* cfg, int B, int N, const int32_t* n
 int jodo_cdgs_forward(const jodo_cdgs_cfg* cfg, int B, int N, const int32_t* n_nodes_host, const void* desc_dev, const float* packed_w,
                       const int64_t* woff, int n_woff, const float* t, const float* x, const float* edge_x, float* out_x, float* out_e,
                       void* workspace, int max_blocks, void* stream);
+/* Split-bf16 ("bf16x3") form of CDGS — OPT-IN, never the default path.  Every row GEMM over node rows or edge rows runs on the bf16 MFMA
+ * with three-term operands (kernel kc_gemm_s; the arithmetic of csrc/dgt_split.h, as in the 2-D model's form above): the embeddings
+ * JCG_NEMB_W, JCG_EEMB_W; per block JCB_GIN1_W, JCB_GIN2_W, JCB_QKV_W, JCB_E01_W, JCB_FF1_W .. JCB_FF4_W, JCB_RN_W, JCB_RE_W; the heads
+ * JCG_AH1_W .. JCG_AH3_W, JCG_EH1_W .. JCG_EH3_W.  The three GEMMs over the B time-embedding rows (T1, T2, TMOD) stay exact fp32, so the
+ * time shifts are the same bits in both forms; GINE, attention, the GroupNorms, the random-walk features, the embedding inputs and the
+ * outputs are unchanged, as are all biases (read from the fp32 blob).
+ * The tape is a function of the packed blob with the semantics of jodo_dgt2d_split_size / jodo_dgt2d_pack_split_host: every covered tiled
+ * matrix [nb][nk][8 quads][64 lanes][4] floats becomes bf16 [nb][nk * 4 K16 steps][3 terms: hi, mid, lo][64 lanes][8], every term rounded
+ * to nearest even.  jodo_cdgs_split_size: *tape_bytes and toff_out[n_woff] = byte offset of every covered slot (16-byte aligned), indexed
+ * like the woff table, -1 for the slots that are not covered; n_woff must be the table size of jodo_cdgs_packed_size.
+ * jodo_cdgs_pack_split_host: (packed HOST blob, its woff table) -> the tape in HOST memory; the caller uploads it.
+ * jodo_cdgs_forward_split: jodo_cdgs_forward plus tape_dev (device copy of the tape), toff (its HOST offset table) and flags_dev (4 int32
+ * on the device): same launch sequence, max_blocks honoured; its first launch writes flags_dev[0..3] = {0, 0, 0, 1} ([3]: the split form
+ * ran, the word the 2-D model uses).  Every covered slot must have an aligned place in toff, else JODO_ERR_ARG. */
+int jodo_cdgs_split_size(const jodo_cdgs_cfg* cfg, size_t* tape_bytes, int64_t* toff_out, int n_woff);
+int jodo_cdgs_pack_split_host(const jodo_cdgs_cfg* cfg, const float* packed_host, const int64_t* woff, int n_woff, void* tape_host,
+                              size_t cap_bytes);
+int jodo_cdgs_forward_split(const jodo_cdgs_cfg* cfg, int B, int N, const int32_t* n_nodes_host, const void* desc_dev, const float* packed_w,
+                            const int64_t* woff, int n_woff, const float* t, const float* x, const float* edge_x, float* out_x,
+                            float* out_e, void* workspace, int max_blocks, void* stream, const void* tape_dev, const int64_t* toff,
+                            int32_t* flags_dev);
+/* tests: the production row GEMM of CDGS on caller-packed device weights, y [rows, n_out] (stride ldy) = residual + act(x' W^T + bias);
+ * x' by mode: 0 row of x [rows, K] (stride ldx); 1 that row plus row (molecule of the edge row) of xadd (stride ldadd); 2 x[atom r] +
+ * x[atom c] of the edge row, x [Nn, K].  act 0 none, 1 SiLU, 2 ReLU, 3 tanh; residual (stride ldy) may be y or NULL; bias may be NULL.
+ * K a multiple of 64, n_out of 32, else JODO_ERR_ARG (null x / w_dev / y likewise).  Modes 1 and 2 read desc_dev, the descriptor of
+ * (cfg, B, N, n_nodes_host), and rows must equal its edge-row count; mode 0 ignores them.  split = 0: w_dev is the f32 packing
+ * (kc_gemm); 1: the split packing (kc_gemm_s with the forward's dispatch), both as jodo_debug_pack_split emits them. */
+int jodo_debug_gemm_cdgs(int split, int mode, const jodo_cdgs_cfg* cfg, int B, int N, const int32_t* n_nodes_host, const void* desc_dev,
+                         const float* x, int ldx, int rows, int K, int n_out, const void* w_dev, const float* bias, int act,
+                         const float* xadd, int ldadd, const float* residual, float* y, int ldy, void* stream);
 
 /* ---- CDGS training (csrc/cdgs_train.hip): forward with kept activations + the gradient of every parameter ----
  * jodo_cdgs_train_* mirror jodo_train2d_* one for one: tensors by name in their PyTorch layouts at create (every tensor of the

@@ -154,7 +154,24 @@ def _bind_cdgs(L):
     fill.argtypes = [p, i, i, p, p, ctypes.c_int64]
     fwd.argtypes = [p, i, i, p, p, p, p, i] + [p] * 6 + [i, p]
     chk.restype = size.restype = pack.restype = lay.restype = fill.restype = fwd.restype = i
+    _bind_cdgs_split(L)
     bind_cdgs_train(L)
+
+
+def _bind_cdgs_split(L):
+    """Argument types of the CDGS split-bf16 exports (jodo_cdgs_split_size, jodo_cdgs_pack_split_host, jodo_cdgs_forward_split,
+    jodo_debug_gemm_cdgs; include/jodo_hip.h)."""
+    i, p = ctypes.c_int, ctypes.c_void_p
+    try:
+        size, pack, fwd, dbg = L.jodo_cdgs_split_size, L.jodo_cdgs_pack_split_host, L.jodo_cdgs_forward_split, L.jodo_debug_gemm_cdgs
+    except AttributeError as e:
+        raise JodoHipError("%s lacks the CDGS split exports (%s): rebuild it with python -c 'import __graft_entry__ as g; g.build()'"
+                           % (LIB_PATH, e))
+    size.argtypes = [p, p, p, i]
+    pack.argtypes = [p, p, p, i, p, ctypes.c_size_t]
+    fwd.argtypes = [p, i, i, p, p, p, p, i] + [p] * 6 + [i, p] + [p, p, p]
+    dbg.argtypes = [i, i, p, i, i, p, p, p, i, i, i, i, p, p, i, p, i, p, p, i, p]
+    size.restype = pack.restype = fwd.restype = dbg.restype = i
 
 
 def bind_cdgs_train(L):
@@ -322,6 +339,21 @@ def split_tape_2d(cfg_struct, blob_host, woff, n_woff, device=None):
     tape = torch.empty(total.value, dtype=torch.uint8)
     check(L.jodo_dgt2d_pack_split_host(ctypes.byref(cfg_struct), ctypes.c_void_p(blob_host.data_ptr()), woff, n_woff,
                                        ctypes.c_void_p(tape.data_ptr()), ctypes.c_size_t(total.value)), 'jodo_dgt2d_pack_split_host')
+    return (tape if device is None else tape.to(device)), toff
+
+
+def split_tape_cdgs(cfg_struct, blob_host, woff, n_woff, device=None):
+    """The CDGS split-bf16 tape, derived from its packed blob (`blob_host`: the CPU blob of pack_weights_cdgs with its offset table):
+    (tape uint8 tensor on the CPU or uploaded to `device`, toff ctypes int64 array — byte offsets into the tape indexed like `woff`,
+    -1 for the slots that stay fp32) through jodo_cdgs_split_size / jodo_cdgs_pack_split_host."""
+    import torch
+    L = lib()
+    total = ctypes.c_size_t()
+    toff = (ctypes.c_int64 * n_woff)()
+    check(L.jodo_cdgs_split_size(ctypes.byref(cfg_struct), ctypes.byref(total), toff, n_woff), 'jodo_cdgs_split_size')
+    tape = torch.empty(total.value, dtype=torch.uint8)
+    check(L.jodo_cdgs_pack_split_host(ctypes.byref(cfg_struct), ctypes.c_void_p(blob_host.data_ptr()), woff, n_woff,
+                                      ctypes.c_void_p(tape.data_ptr()), ctypes.c_size_t(total.value)), 'jodo_cdgs_pack_split_host')
     return (tape if device is None else tape.to(device)), toff
 
 

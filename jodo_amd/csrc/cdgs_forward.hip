@@ -14,11 +14,16 @@
 //   kc_estats (per (molecule, group) moments over 8 channels x N x N positions of the PADDED batch, double accumulators, fixed order)
 //   kc_enorm (normalise, affine, mask; second pass in place) -> kc_gemm (edge readout)
 // No float atomics anywhere: every reduction has one owner and a fixed order.
+//
+// jodo_cdgs_forward_split (opt-in, model.bf16x3): the same launch sequence with every kc_gemm over node rows or edge rows replaced by
+// kc_gemm_s, the split-bf16 form (dgt_split.h) reading a weight tape derived from the packed blob; the three GEMMs over the B
+// time-embedding rows and every other kernel are the exact-fp32 ones above.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/jodo_hip.h"
 #include "jodo_hip_internal.h"
 #include "dgt_device.h"
+#include "dgt_split.h"
 #include "cdgs_common.h"
 
 using namespace jd;
@@ -95,6 +100,47 @@ struct GemmC {
     const float* xadd; int ldadd; const int* rowmol; const int *mol_n, *mol_noff, *mol_eoff;
 };
 constexpr int GC_NOB = 4, GC_MT = 2;
+// bias, activation, residual and the store of a strip's 32 x 32 accumulator images: the one epilogue of both forms of the row GEMM
+template <int NOB, int MT>
+__device__ __forceinline__ void gemmc_epilogue(const GemmC& G, const f32x16 (&acc)[NOB][MT], const int (&row)[MT], int ob0, int h) {
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+        if (row[m] >= G.rows) continue;
+#pragma unroll
+        for (int o = 0; o < NOB; ++o) {
+            if (ob0 + o >= G.NB) continue;
+            const int col0 = (ob0 + o) * 32 + 16 * h;
+            float v[16], bb[16];
+            if (G.bias) load16(G.bias + col0, bb);
+#pragma unroll
+            for (int s = 0; s < 16; ++s) {
+                v[s] = acc[o][m][s] + (G.bias ? bb[s] : 0.f);
+                if (G.act == 1) v[s] = silu_f(v[s]);
+                else if (G.act == 2) v[s] = fmaxf(v[s], 0.f);
+                else if (G.act == 3) v[s] = tanh_f(v[s]);
+            }
+            if (G.R) {
+                float rr[16];
+                load16(G.R + (size_t)row[m] * G.ldr + col0, rr);
+#pragma unroll
+                for (int s = 0; s < 16; ++s) v[s] += rr[s];
+            }
+            store16(G.Y + (size_t)row[m] * G.ldy + col0, v);
+        }
+    }
+}
+// the source rows of output row rw: xs is the second row of modes 1 and 2 (NULL in mode 0)
+template <int MODE>
+__device__ __forceinline__ void gemmc_src(const GemmC& G, int rw, const float*& xr, const float*& xs) {
+    if (MODE == 2) {
+        const int b = G.rowmol[rw], n = G.mol_n[b], loc = rw - G.mol_eoff[b];
+        xr = G.X + (size_t)(G.mol_noff[b] + loc / n) * G.ldx;
+        xs = G.X + (size_t)(G.mol_noff[b] + loc % n) * G.ldx;
+    } else {
+        xr = G.X + (size_t)rw * G.ldx;
+        xs = MODE == 1 ? G.xadd + (size_t)G.rowmol[rw] * G.ldadd : nullptr;
+    }
+}
 template <int MODE>
 __global__ __launch_bounds__(64) void kc_gemm(GemmC G) {
     constexpr int NOB = GC_NOB, MT = GC_MT;
@@ -106,15 +152,7 @@ __global__ __launch_bounds__(64) void kc_gemm(GemmC G) {
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
         row[m] = (strip * MT + m) * 32 + j;
-        const int rw = min(row[m], G.rows - 1);
-        if (MODE == 2) {
-            const int b = G.rowmol[rw], n = G.mol_n[b], loc = rw - G.mol_eoff[b];
-            xr[m] = G.X + (size_t)(G.mol_noff[b] + loc / n) * G.ldx;
-            xs[m] = G.X + (size_t)(G.mol_noff[b] + loc % n) * G.ldx;
-        } else {
-            xr[m] = G.X + (size_t)rw * G.ldx;
-            xs[m] = MODE == 1 ? G.xadd + (size_t)G.rowmol[rw] * G.ldadd : nullptr;
-        }
+        gemmc_src<MODE>(G, min(row[m], G.rows - 1), xr[m], xs[m]);
 #pragma unroll
         for (int o = 0; o < NOB; ++o) acc[o][m] = zero16();
     }
@@ -147,31 +185,91 @@ __global__ __launch_bounds__(64) void kc_gemm(GemmC G) {
             }
         }
     }
+    gemmc_epilogue<NOB, MT>(G, acc, row, ob0, h);
+}
+
+// ---- row GEMM, split-bf16 form (opt-in; dgt_split.h): same contract, same accumulator image, same epilogue ----------------------------
+// The counterpart of k2d_gemm_s (csrc/dgt2d_forward.hip) with the three row loads of kc_gemm.  G.W points at the matrix's slot of the split
+// tape (csrc/cdgs_pack.cpp): [out block][nk * 4 K16 steps][hi, mid, lo][64 lanes][8 bf16].  Per K chunk of 64 the activations of a tile
+// become four Split8; in modes 1 and 2 the two source rows are added in fp32 first, as kc_gemm adds them before its MFMAs, and the sum is
+// split.  A group is one (output block, K chunk) = 4 K16 steps = 12 KiB of tape, whose 24 MT MFMAs run while the next group's twelve
+// 16-byte loads are in flight (WPipeS<4>); the next chunk's rows (both of them in modes 1 and 2) are requested before the chunk's first
+// group.  Output blocks past NB read the last block's tape again and are dropped by the epilogue.  DESIGN.md 4n has the shape table.
+constexpr int GCS_NOB = 8, GCS_MT = 1;
+template <int MODE, int NOB, int MT>
+__global__ __launch_bounds__(64) void kc_gemm_s(GemmC G) {
+    const int lane = threadIdx.x, j = lane & 31, h = lane >> 5;
+    const int strip = blockIdx.x, ob0 = blockIdx.y * NOB;
+    f32x16 acc[NOB][MT];
+    int row[MT];
+    const float *xr[MT], *xs[MT];
+    float nxt[MT][32], nad[MT][32];                          // nad: the second row of modes 1 and 2 (dead in mode 0)
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
-        if (row[m] >= G.rows) continue;
+        row[m] = (strip * MT + m) * 32 + j;
+        gemmc_src<MODE>(G, min(row[m], G.rows - 1), xr[m], xs[m]);
+        load_nat<2>(xr[m], h, nxt[m]);
+        if (MODE != 0) load_nat<2>(xs[m], h, nad[m]);
+#pragma unroll
+        for (int o = 0; o < NOB; ++o) acc[o][m] = zero16();
+    }
+    const WSrc ws = make_wsrc(G.W, lane);
+    const unsigned blk = (unsigned)G.nk * 12288u;
+    unsigned boff[NOB];
+#pragma unroll
+    for (int o = 0; o < NOB; ++o) boff[o] = (unsigned)min(ob0 + o, G.NB - 1) * blk;
+    WPipeS<4> wp;
+    wpipe_prime_s(wp, ws, boff[0]);
+    for (int kc = 0; kc < G.nk; ++kc) {
+        Split8 xv[MT][4];
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            if (MODE != 0) {
+#pragma unroll
+                for (int s = 0; s < 32; ++s) nxt[m][s] += nad[m][s];
+            }
+#pragma unroll
+            for (int g = 0; g < 4; ++g) xv[m][g] = split8(&nxt[m][8 * g]);
+        }
+        if (kc + 1 < G.nk) {
+#pragma unroll
+            for (int m = 0; m < MT; ++m) {
+                load_nat<2>(xr[m] + (kc + 1) * 64, h, nxt[m]);
+                if (MODE != 0) load_nat<2>(xs[m] + (kc + 1) * 64, h, nad[m]);
+            }
+        }
 #pragma unroll
         for (int o = 0; o < NOB; ++o) {
-            if (ob0 + o >= G.NB) continue;
-            const int col0 = (ob0 + o) * 32 + 16 * h;
-            float v[16], bb[16];
-            if (G.bias) load16(G.bias + col0, bb);
+            u32x4 cur[4][3];
 #pragma unroll
-            for (int s = 0; s < 16; ++s) {
-                v[s] = acc[o][m][s] + (G.bias ? bb[s] : 0.f);
-                if (G.act == 1) v[s] = silu_f(v[s]);
-                else if (G.act == 2) v[s] = fmaxf(v[s], 0.f);
-                else if (G.act == 3) v[s] = tanh_f(v[s]);
-            }
-            if (G.R) {
-                float rr[16];
-                load16(G.R + (size_t)row[m] * G.ldr + col0, rr);
+            for (int i = 0; i < 4; ++i)
 #pragma unroll
-                for (int s = 0; s < 16; ++s) v[s] += rr[s];
+                for (int t = 0; t < 3; ++t) cur[i][t] = wp.q[i][t];
+            // (behind the last group the ring re-reads that group: a live address, never consumed)
+            const unsigned nof = o + 1 < NOB ? boff[o + 1] + (unsigned)kc * 12288u : boff[0] + (unsigned)min(kc + 1, G.nk - 1) * 12288u;
+            wpipe_prime_s(wp, ws, nof);
+            pipeline_fence();
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const bf16x8 wh = as_bf16x8(cur[i][0]), wm = as_bf16x8(cur[i][1]), wl = as_bf16x8(cur[i][2]);
+                // the six products of mfma_step_s, small terms first, dealt over the tiles
+#pragma unroll
+                for (int m = 0; m < MT; ++m) acc[o][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xv[m][i].l, acc[o][m], 0, 0, 0);
+#pragma unroll
+                for (int m = 0; m < MT; ++m) acc[o][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, xv[m][i].h, acc[o][m], 0, 0, 0);
+#pragma unroll
+                for (int m = 0; m < MT; ++m) acc[o][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wm, xv[m][i].m, acc[o][m], 0, 0, 0);
+#pragma unroll
+                for (int m = 0; m < MT; ++m) acc[o][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xv[m][i].m, acc[o][m], 0, 0, 0);
+#pragma unroll
+                for (int m = 0; m < MT; ++m) acc[o][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wm, xv[m][i].h, acc[o][m], 0, 0, 0);
+#pragma unroll
+                for (int m = 0; m < MT; ++m) acc[o][m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, xv[m][i].h, acc[o][m], 0, 0, 0);
             }
-            store16(G.Y + (size_t)row[m] * G.ldy + col0, v);
+            pipeline_fence();
         }
     }
+    gemmc_epilogue<NOB, MT>(G, acc, row, ob0, h);
 }
 
 // GroupNorm of one 256-wide row held one channel per thread: groups of 8 consecutive lanes, biased variance around the mean, eps 1e-6
@@ -403,16 +501,35 @@ __global__ void kc_out_edges(KC A) {                   // (s + s^T) / 2 over the
     A.out_e[idx] = v;
 }
 
+__global__ void kc_flags_init(int32_t* flags) {            // the 2-D model's flag words: [3] = the split-bf16 form ran; the others unused here
+    if (threadIdx.x < 4) flags[threadIdx.x] = threadIdx.x == 3 ? 1 : 0;
+}
+
 struct Ctx { hipStream_t st; const KC* A; };
 
+// the split form of one row-load mode, dispatched on NB as the 2-D launcher does
+template <int MODE>
+int gemm_split(hipStream_t st, const GemmC& G) {
+    const unsigned strips = (unsigned)((G.rows + 32 * GCS_MT - 1) / (32 * GCS_MT));
+    if (G.NB >= 3) LCD((kc_gemm_s<MODE, GCS_NOB, GCS_MT>), dim3(strips, (unsigned)((G.NB + GCS_NOB - 1) / GCS_NOB)), 64, G);
+    else if (G.NB == 2) LCD((kc_gemm_s<MODE, 2, GCS_MT>), dim3(strips, 1), 64, G);
+    else LCD((kc_gemm_s<MODE, 1, GCS_MT>), dim3(strips, 1), 64, G);
+    return JODO_OK;
+}
+
+// WS != NULL: the matrix's slot of the split tape, split-bf16 form (kc_gemm_s); W is then not read
 int gemm(const Ctx& C, int mode, const float* X, int ldx, int64_t rows, int Kc, const float* W, const float* bias, int n_out, int act,
-         float* Y, int ldy, const float* R = nullptr, int ldr = 0, const float* xadd = nullptr, int ldadd = 0) {
+         float* Y, int ldy, const float* R = nullptr, int ldr = 0, const float* xadd = nullptr, int ldadd = 0, const void* WS = nullptr) {
     if (rows <= 0) return JODO_OK;
     hipStream_t st = C.st;
     GemmC G;
     G.X = X; G.ldx = ldx; G.Y = Y; G.ldy = ldy; G.W = W; G.bias = bias; G.rows = (int)rows; G.nk = (Kc + 63) / 64; G.NB = (n_out + 31) / 32;
     G.act = act; G.R = R; G.ldr = ldr; G.xadd = xadd; G.ldadd = ldadd; G.rowmol = C.A->pair_b; G.mol_n = C.A->mol_n;
     G.mol_noff = C.A->mol_noff; G.mol_eoff = C.A->mol_eoff;
+    if (WS) {
+        G.W = static_cast<const float*>(WS);
+        return mode == 0 ? gemm_split<0>(st, G) : mode == 1 ? gemm_split<1>(st, G) : gemm_split<2>(st, G);
+    }
     const dim3 grid((unsigned)((rows + 32 * GC_MT - 1) / (32 * GC_MT)), (unsigned)((G.NB + GC_NOB - 1) / GC_NOB));
     if (mode == 0) LCD(kc_gemm<0>, grid, 64, G);
     else if (mode == 1) LCD(kc_gemm<1>, grid, 64, G);
@@ -451,14 +568,30 @@ extern "C" int jodo_cdgs_fill_desc(const jodo_cdgs_cfg* cfg, int B, int N, const
     return JODO_OK;
 }
 
-extern "C" int jodo_cdgs_forward(const jodo_cdgs_cfg* cfg, int B, int N, const int32_t* n_nodes, const void* desc_dev, const float* packed_w,
-                                 const int64_t* woff, int n_woff, const float* t, const float* x, const float* edge_x, float* out_x,
-                                 float* out_e, void* workspace, int max_blocks, void* stream) {
+// the covered slots of the split tape (csrc/cdgs_pack.cpp split_slots): every row GEMM over node rows or edge rows
+static const int split_global[] = {JCG_NEMB_W, JCG_EEMB_W, JCG_AH1_W, JCG_AH2_W, JCG_AH3_W, JCG_EH1_W, JCG_EH2_W, JCG_EH3_W};
+static const int split_block[] = {JCB_GIN1_W, JCB_GIN2_W, JCB_QKV_W, JCB_E01_W, JCB_FF1_W, JCB_FF2_W, JCB_FF3_W, JCB_FF4_W, JCB_RN_W, JCB_RE_W};
+
+// tape_dev != NULL: the split-bf16 form of the node-row and edge-row GEMMs (flags_dev then receives {0, 0, 0, 1}); the launch sequence
+// is the same either way
+static int forward_cdgs(const jodo_cdgs_cfg* cfg, int B, int N, const int32_t* n_nodes, const void* desc_dev, const float* packed_w,
+                        const int64_t* woff, int n_woff, const float* t, const float* x, const float* edge_x, float* out_x, float* out_e,
+                        void* workspace, int max_blocks, void* stream, const void* tape_dev = nullptr, const int64_t* toff = nullptr,
+                        int32_t* flags_dev = nullptr) {
     if (!desc_dev || !packed_w || !woff || !t || !x || !edge_x || !out_x || !out_e || !workspace)
         return jodo_set_error(JODO_ERR_ARG, "cdgs_forward: null argument");
     if (int rc = jodo_cdgs_check_cfg(cfg)) return rc;
     if (n_woff != JCG_GLOBAL_COUNT + cfg->n_layers * JCB_BLOCK_COUNT)
         return jodo_set_error(JODO_ERR_ARG, "cdgs_forward: weight table has %d slots, expected %d", n_woff, JCG_GLOBAL_COUNT + cfg->n_layers * JCB_BLOCK_COUNT);
+    if (tape_dev) {                                          // split-bf16 form: every covered slot needs its place in the tape
+        if (!toff || !flags_dev) return jodo_set_error(JODO_ERR_ARG, "cdgs_forward: split tape without its offset table or the flag words");
+        bool ok = true;
+        for (int s : split_global) ok = ok && toff[s] >= 0 && toff[s] % 16 == 0;
+        for (int lyr = 0; lyr < cfg->n_layers; ++lyr)
+            for (int s : split_block) { const int64_t o = toff[JCG_GLOBAL_COUNT + lyr * JCB_BLOCK_COUNT + s]; ok = ok && o >= 0 && o % 16 == 0; }
+        if (!ok) return jodo_set_error(JODO_ERR_ARG, "cdgs_forward: the split tape's offset table misses a covered slot");
+    }
+    const char* T = static_cast<const char*>(tape_dev);
     Lay l;
     if (int rc = make_lay(cfg, B, N, n_nodes, &l)) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -481,7 +614,13 @@ extern "C" int jodo_cdgs_forward(const jodo_cdgs_cfg* cfg, int B, int N, const i
     const int Nn = l.Nn, L = l.L, D = DC;
     const unsigned R = (unsigned)l.R;
     int rc;
-    // ---- time embedding and every block's time shifts (the blocks read temb only through SiLU) ----
+    // a row GEMM over node rows or edge rows: weights of woff slot `slot`, from the split tape when there is one
+    auto mm = [&](int mode, const float* X, int ldx, int64_t rows, int Kc, int slot, const float* bias, int n_out, int act, float* Y, int ldy,
+                  const float* Rs = nullptr, int ldr = 0, const float* xadd = nullptr, int ldadd = 0) {
+        return gemm(C, mode, X, ldx, rows, Kc, W + woff[slot], bias, n_out, act, Y, ldy, Rs, ldr, xadd, ldadd, T ? T + toff[slot] : nullptr);
+    };
+    if (T) LCD(kc_flags_init, 1, 64, flags_dev);
+    // ---- time embedding and every block's time shifts (the blocks read temb only through SiLU; exact fp32 in both forms) ----
     LCD(kc_time, B, 256, A);
     if ((rc = gemm(C, 0, A.tin, D, B, D, W + A.wg[JCG_T1_W], W + A.wg[JCG_T1_B], 2 * D, 1, t1, 2 * D))) return rc;
     if ((rc = gemm(C, 0, t1, 2 * D, B, 2 * D, W + A.wg[JCG_T2_W], W + A.wg[JCG_T2_B], D, 1, temb, D))) return rc;
@@ -489,9 +628,9 @@ extern "C" int jodo_cdgs_forward(const jodo_cdgs_cfg* cfg, int B, int N, const i
     // ---- random-walk features and embeddings ----
     LCD(kc_rw, B, 256, A);
     LCD(kc_embed_nodes, Nn, 256, A);
-    if ((rc = gemm(C, 0, A.nin, D, Nn, D, W + A.wg[JCG_NEMB_W], W + A.wg[JCG_NEMB_B], D, 0, A.h, D))) return rc;
+    if ((rc = mm(0, A.nin, D, Nn, D, JCG_NEMB_W, W + A.wg[JCG_NEMB_B], D, 0, A.h, D))) return rc;
     LCD(kc_embed_edges, R, 256, A);
-    if ((rc = gemm(C, 0, A.tmp, D, l.R, D, W + A.wg[JCG_EEMB_W], W + A.wg[JCG_EEMB_B], D, 0, A.e, D))) return rc;
+    if ((rc = mm(0, A.tmp, D, l.R, D, JCG_EEMB_W, W + A.wg[JCG_EEMB_B], D, 0, A.e, D))) return rc;
     LCD(kc_zero_diag, Nn, 256, A);
     // ---- blocks ----
     const bool stop = max_blocks >= 0 && max_blocks <= L;
@@ -502,36 +641,77 @@ extern "C" int jodo_cdgs_forward(const jodo_cdgs_cfg* cfg, int B, int N, const i
         const float* te = A.tmod + (size_t)lyr * 2 * D + D;          // row b of the time shifts: stride 2 D L
         LCD(kc_addt, Nn, 256, A, lyr);
         LCD(kc_gine, Nn, 256, A, lyr);
-        if ((rc = gemm(C, 0, A.agg, D, Nn, D, W + A.wb[JCB_GIN1_W], W + A.wb[JCB_GIN1_B], D, 2, g1, D))) return rc;
-        if ((rc = gemm(C, 0, g1, D, Nn, D, W + A.wb[JCB_GIN2_W], W + A.wb[JCB_GIN2_B], D, 0, g2, D))) return rc;
-        if ((rc = gemm(C, 0, A.hs, D, Nn, D, W + A.wb[JCB_QKV_W], W + A.wb[JCB_QKV_B], 3 * D, 0, A.qkv, 3 * D))) return rc;
-        if ((rc = gemm(C, 1, A.e, D, l.R, D, W + A.wb[JCB_E01_W], nullptr, 2 * D, 3, A.tmp, 2 * D, nullptr, 0, te, 2 * D * L))) return rc;
+        if ((rc = mm(0, A.agg, D, Nn, D, slot0 + JCB_GIN1_W, W + A.wb[JCB_GIN1_B], D, 2, g1, D))) return rc;
+        if ((rc = mm(0, g1, D, Nn, D, slot0 + JCB_GIN2_W, W + A.wb[JCB_GIN2_B], D, 0, g2, D))) return rc;
+        if ((rc = mm(0, A.hs, D, Nn, D, slot0 + JCB_QKV_W, W + A.wb[JCB_QKV_B], 3 * D, 0, A.qkv, 3 * D))) return rc;
+        if ((rc = mm(1, A.e, D, l.R, D, slot0 + JCB_E01_W, nullptr, 2 * D, 3, A.tmp, 2 * D, nullptr, 0, te, 2 * D * L))) return rc;
         LCD(kc_attn, Nn, 256, A);
         LCD(kc_gn2, Nn, 256, Nn, (const float*)A.h, (const float*)g2, W + A.wb[JCB_NL_G], W + A.wb[JCB_NL_B], (const float*)A.h,
             (const float*)A.att, W + A.wb[JCB_NA_G], W + A.wb[JCB_NA_B], A.hc);
-        if ((rc = gemm(C, 0, A.hc, D, Nn, D, W + A.wb[JCB_FF1_W], W + A.wb[JCB_FF1_B], 2 * D, 1, f1, 2 * D))) return rc;
-        if ((rc = gemm(C, 0, f1, 2 * D, Nn, 2 * D, W + A.wb[JCB_FF2_W], W + A.wb[JCB_FF2_B], D, 0, f2, D))) return rc;
+        if ((rc = mm(0, A.hc, D, Nn, D, slot0 + JCB_FF1_W, W + A.wb[JCB_FF1_B], 2 * D, 1, f1, 2 * D))) return rc;
+        if ((rc = mm(0, f1, 2 * D, Nn, 2 * D, slot0 + JCB_FF2_W, W + A.wb[JCB_FF2_B], D, 0, f2, D))) return rc;
         LCD(kc_gn2, Nn, 256, Nn, (const float*)A.hc, (const float*)f2, W + A.wb[JCB_NN_G], W + A.wb[JCB_NN_B], (const float*)nullptr,
             (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, A.h);
-        if ((rc = gemm(C, 0, A.h, D, Nn, D, W + A.wb[JCB_RN_W], W + A.wb[JCB_RN_B], l.catp, 0, A.ahid + lyr * l.catp, l.KA))) return rc;
+        if ((rc = mm(0, A.h, D, Nn, D, slot0 + JCB_RN_W, W + A.wb[JCB_RN_B], l.catp, 0, A.ahid + lyr * l.catp, l.KA))) return rc;
         // edge path: e <- e + FF(h_r + h_c) in place; FF(h_i) and FF(0) for the padded positions (row Nn of hc is zero and never written)
-        if ((rc = gemm(C, 2, A.hc, D, l.R, D, W + A.wb[JCB_FF3_W], W + A.wb[JCB_FF3_B], 2 * D, 1, A.tmp, 2 * D))) return rc;
-        if ((rc = gemm(C, 0, A.tmp, 2 * D, l.R, 2 * D, W + A.wb[JCB_FF4_W], W + A.wb[JCB_FF4_B], D, 0, A.e, D, A.e, D))) return rc;
-        if ((rc = gemm(C, 0, A.hc, D, Nn + 1, D, W + A.wb[JCB_FF3_W], W + A.wb[JCB_FF3_B], 2 * D, 1, x1, 2 * D))) return rc;
-        if ((rc = gemm(C, 0, x1, 2 * D, Nn + 1, 2 * D, W + A.wb[JCB_FF4_W], W + A.wb[JCB_FF4_B], D, 0, A.xff, D))) return rc;
+        if ((rc = mm(2, A.hc, D, l.R, D, slot0 + JCB_FF3_W, W + A.wb[JCB_FF3_B], 2 * D, 1, A.tmp, 2 * D))) return rc;
+        if ((rc = mm(0, A.tmp, 2 * D, l.R, 2 * D, slot0 + JCB_FF4_W, W + A.wb[JCB_FF4_B], D, 0, A.e, D, A.e, D))) return rc;
+        if ((rc = mm(0, A.hc, D, Nn + 1, D, slot0 + JCB_FF3_W, W + A.wb[JCB_FF3_B], 2 * D, 1, x1, 2 * D))) return rc;
+        if ((rc = mm(0, x1, 2 * D, Nn + 1, 2 * D, slot0 + JCB_FF4_W, W + A.wb[JCB_FF4_B], D, 0, A.xff, D))) return rc;
         LCD(kc_estats, B, 1024, A);
         LCD(kc_enorm, R, 256, A);
-        if ((rc = gemm(C, 0, A.e, D, l.R, D, W + A.wb[JCB_RE_W], W + A.wb[JCB_RE_B], l.catp, 0, A.ehid + lyr * l.catp, l.KE))) return rc;
+        if ((rc = mm(0, A.e, D, l.R, D, slot0 + JCB_RE_W, W + A.wb[JCB_RE_B], l.catp, 0, A.ehid + lyr * l.catp, l.KE))) return rc;
     }
     if (stop) return JODO_OK;                                        // debug stop: h and e stay in the workspace (the heads reuse e)
     // ---- heads ----
-    if ((rc = gemm(C, 0, A.ahid, l.KA, Nn, l.KA, W + A.wg[JCG_AH1_W], W + A.wg[JCG_AH1_B], D, 1, a1, D))) return rc;
-    if ((rc = gemm(C, 0, a1, D, Nn, D, W + A.wg[JCG_AH2_W], W + A.wg[JCG_AH2_B], D / 2, 1, a2, D / 2))) return rc;
-    if ((rc = gemm(C, 0, a2, D / 2, Nn, D / 2, W + A.wg[JCG_AH3_W], W + A.wg[JCG_AH3_B], 32, 0, A.a3, 32))) return rc;
-    if ((rc = gemm(C, 0, A.ehid, l.KE, l.R, l.KE, W + A.wg[JCG_EH1_W], W + A.wg[JCG_EH1_B], 2 * D, 1, A.tmp, 2 * D))) return rc;
-    if ((rc = gemm(C, 0, A.tmp, 2 * D, l.R, 2 * D, W + A.wg[JCG_EH2_W], W + A.wg[JCG_EH2_B], D, 1, A.e, D))) return rc;
-    if ((rc = gemm(C, 0, A.e, D, l.R, D, W + A.wg[JCG_EH3_W], W + A.wg[JCG_EH3_B], 32, 0, A.eh3, 32))) return rc;
+    if ((rc = mm(0, A.ahid, l.KA, Nn, l.KA, JCG_AH1_W, W + A.wg[JCG_AH1_B], D, 1, a1, D))) return rc;
+    if ((rc = mm(0, a1, D, Nn, D, JCG_AH2_W, W + A.wg[JCG_AH2_B], D / 2, 1, a2, D / 2))) return rc;
+    if ((rc = mm(0, a2, D / 2, Nn, D / 2, JCG_AH3_W, W + A.wg[JCG_AH3_B], 32, 0, A.a3, 32))) return rc;
+    if ((rc = mm(0, A.ehid, l.KE, l.R, l.KE, JCG_EH1_W, W + A.wg[JCG_EH1_B], 2 * D, 1, A.tmp, 2 * D))) return rc;
+    if ((rc = mm(0, A.tmp, 2 * D, l.R, 2 * D, JCG_EH2_W, W + A.wg[JCG_EH2_B], D, 1, A.e, D))) return rc;
+    if ((rc = mm(0, A.e, D, l.R, D, JCG_EH3_W, W + A.wg[JCG_EH3_B], 32, 0, A.eh3, 32))) return rc;
     LCD(kc_out_nodes, (unsigned)(((size_t)B * N * A.ach + 255) / 256), 256, A);
     LCD(kc_out_edges, (unsigned)(((size_t)B * N * N * A.ch + 255) / 256), 256, A);
     return JODO_OK;
+}
+
+extern "C" int jodo_cdgs_forward(const jodo_cdgs_cfg* cfg, int B, int N, const int32_t* n_nodes, const void* desc_dev, const float* packed_w,
+                                 const int64_t* woff, int n_woff, const float* t, const float* x, const float* edge_x, float* out_x,
+                                 float* out_e, void* workspace, int max_blocks, void* stream) {
+    return forward_cdgs(cfg, B, N, n_nodes, desc_dev, packed_w, woff, n_woff, t, x, edge_x, out_x, out_e, workspace, max_blocks, stream);
+}
+
+// jodo_cdgs_forward with the split-bf16 form of every row GEMM over node rows and edge rows: tape_dev / toff from jodo_cdgs_split_size and
+// jodo_cdgs_pack_split_host (the device copy of the tape, the host offset table).  Its first launch writes flags_dev[0..3] = {0, 0, 0, 1}.
+extern "C" int jodo_cdgs_forward_split(const jodo_cdgs_cfg* cfg, int B, int N, const int32_t* n_nodes, const void* desc_dev,
+                                       const float* packed_w, const int64_t* woff, int n_woff, const float* t, const float* x,
+                                       const float* edge_x, float* out_x, float* out_e, void* workspace, int max_blocks, void* stream,
+                                       const void* tape_dev, const int64_t* toff, int32_t* flags_dev) {
+    if (!tape_dev || !toff || !flags_dev) return jodo_set_error(JODO_ERR_ARG, "cdgs_forward_split: null split tape, offset table or flag words");
+    return forward_cdgs(cfg, B, N, n_nodes, desc_dev, packed_w, woff, n_woff, t, x, edge_x, out_x, out_e, workspace, max_blocks, stream,
+                        tape_dev, toff, flags_dev);
+}
+
+// tests: the production row GEMM on caller-packed device weights, y [rows, n_out] = residual + act(x' [rows, K] W^T + bias) with x' by
+// mode as in GemmC.  split = 0: w_dev is the f32 packing, kc_gemm; split = 1: the split packing (both as jodo_debug_pack_split emits
+// them), kc_gemm_s as forward_cdgs launches it.  Modes 1 and 2 read the descriptor of (cfg, B, N, n_nodes) and need rows = its edge rows.
+extern "C" int jodo_debug_gemm_cdgs(int split, int mode, const jodo_cdgs_cfg* cfg, int B, int N, const int32_t* n_nodes, const void* desc_dev,
+                                    const float* x, int ldx, int rows, int K, int n_out, const void* w_dev, const float* bias, int act,
+                                    const float* xadd, int ldadd, const float* residual, float* y, int ldy, void* stream) {
+    if (!x || !w_dev || !y || rows <= 0 || K <= 0 || K % 64 || n_out <= 0 || n_out % 32 || act < 0 || act > 3 || mode < 0 || mode > 2 ||
+        ldx < K || ldy < n_out)
+        return jodo_set_error(JODO_ERR_ARG, "debug_gemm_cdgs: bad argument");
+    KC A{};
+    if (mode != 0) {
+        if (!desc_dev || (mode == 1 && (!xadd || ldadd < K))) return jodo_set_error(JODO_ERR_ARG, "debug_gemm_cdgs: mode %d needs its descriptor and rows", mode);
+        if (int rc = jodo_cdgs_check_cfg(cfg)) return rc;
+        Lay l;
+        if (int rc = make_lay(cfg, B, N, n_nodes, &l)) return rc;
+        if (rows != l.R) return jodo_set_error(JODO_ERR_ARG, "debug_gemm_cdgs: %d rows, the descriptor has %lld edge rows", rows, (long long)l.R);
+        const int* dsc = static_cast<const int*>(desc_dev);
+        A.mol_n = dsc + l.off_n; A.mol_noff = dsc + l.off_noff; A.mol_eoff = dsc + l.off_eoff; A.node_b = dsc + l.off_node; A.pair_b = dsc + l.off_pair;
+    }
+    const Ctx C{(hipStream_t)stream, &A};
+    return gemm(C, mode, x, ldx, rows, K, static_cast<const float*>(w_dev), bias, n_out, act, y, ldy, residual, ldy, xadd, ldadd,
+                split ? w_dev : nullptr);
 }

@@ -13,6 +13,7 @@
 #include <vector>
 #include "../../include/jodo_hip.h"
 #include "jodo_hip_internal.h"
+#include "split_tape.h"
 
 namespace {
 
@@ -246,4 +247,79 @@ extern "C" int jodo_cdgs_pack_weights_host(const jodo_cdgs_cfg* cfg, const jodo_
     std::memset(packed_host, 0, need * sizeof(float));
     P.blob = packed_host;
     return run(cfg, P, woff);
+}
+
+// ---- split-bf16 ("bf16x3") weight tape of the row GEMMs over node rows and edge rows (opt-in form, csrc/cdgs_forward.hip kc_gemm_s) ----
+// A function of the packed blob, exactly as the 2-D model's tape (csrc/dgt2d_pack.cpp): every covered tiled matrix float
+// [nb][nk][8 quads][64 lanes][4] is re-read as bf16 [nb][nk * 4 K16 steps][3 terms: hi, mid, lo][64 lanes][8] by jd_tape::split_tiles
+// (csrc/split_tape.h).  The three GEMMs over the B time-embedding rows (T1, T2, TMOD) stay exact fp32 and have no slot.
+namespace {
+
+struct SplitSlot { int slot, nb, nk; };                   // slot: index into the woff table
+
+std::vector<SplitSlot> split_slots(const jodo_cdgs_cfg* c) {
+    const int D = c->nf, L = c->n_layers, catp = (2 * D / L + 31) / 32 * 32;
+    const int KA = (L * catp + (D - 2 * (int)(D * 0.2)) + 63) / 64 * 64, KE = (L * catp + 192 + 63) / 64 * 64;
+    std::vector<SplitSlot> s;
+    for (int l = 0; l < L; ++l) {
+        const int at = JCG_GLOBAL_COUNT + l * JCB_BLOCK_COUNT;
+        s.push_back({at + JCB_GIN1_W, D / 32, D / 64});
+        s.push_back({at + JCB_GIN2_W, D / 32, D / 64});
+        s.push_back({at + JCB_QKV_W, 3 * D / 32, D / 64});
+        s.push_back({at + JCB_E01_W, 2 * D / 32, D / 64});
+        s.push_back({at + JCB_FF1_W, 2 * D / 32, D / 64});
+        s.push_back({at + JCB_FF2_W, D / 32, 2 * D / 64});
+        s.push_back({at + JCB_FF3_W, 2 * D / 32, D / 64});
+        s.push_back({at + JCB_FF4_W, D / 32, 2 * D / 64});
+        s.push_back({at + JCB_RN_W, catp / 32, D / 64});
+        s.push_back({at + JCB_RE_W, catp / 32, D / 64});
+    }
+    s.push_back({JCG_NEMB_W, D / 32, D / 64});
+    s.push_back({JCG_EEMB_W, D / 32, D / 64});
+    s.push_back({JCG_AH1_W, D / 32, KA / 64});
+    s.push_back({JCG_AH2_W, D / 2 / 32, D / 64});
+    s.push_back({JCG_AH3_W, 1, D / 2 / 64});
+    s.push_back({JCG_EH1_W, 2 * D / 32, KE / 64});
+    s.push_back({JCG_EH2_W, D / 32, 2 * D / 64});
+    s.push_back({JCG_EH3_W, 1, D / 64});
+    return s;
+}
+
+}  // namespace
+
+extern "C" int jodo_cdgs_split_size(const jodo_cdgs_cfg* cfg, size_t* tape_bytes, int64_t* toff_out, int n_woff) {
+    if (!tape_bytes || !toff_out) return jodo_set_error(JODO_ERR_ARG, "cdgs_split_size: null argument");
+    if (int rc = jodo_cdgs_check_cfg(cfg)) return rc;
+    const int want = JCG_GLOBAL_COUNT + cfg->n_layers * JCB_BLOCK_COUNT;
+    if (n_woff != want) return jodo_set_error(JODO_ERR_ARG, "cdgs_split_size: offset table of %d slots, expected %d", n_woff, want);
+    for (int i = 0; i < n_woff; ++i) toff_out[i] = -1;
+    size_t at = 0;
+    for (const SplitSlot& s : split_slots(cfg)) {
+        toff_out[s.slot] = (int64_t)at;
+        at += (size_t)s.nb * s.nk * jd_tape::TILE_BYTES;  // a multiple of 16 bytes: every slot stays 16-byte aligned
+    }
+    *tape_bytes = at;
+    return JODO_OK;
+}
+
+extern "C" int jodo_cdgs_pack_split_host(const jodo_cdgs_cfg* cfg, const float* packed_host, const int64_t* woff, int n_woff, void* tape_host,
+                                         size_t cap_bytes) {
+    if (!packed_host || !woff || !tape_host) return jodo_set_error(JODO_ERR_ARG, "cdgs_pack_split: null argument");
+    if (int rc = jodo_cdgs_check_cfg(cfg)) return rc;
+    const int want = JCG_GLOBAL_COUNT + cfg->n_layers * JCB_BLOCK_COUNT;
+    if (n_woff != want) return jodo_set_error(JODO_ERR_ARG, "cdgs_pack_split: offset table of %d slots, expected %d", n_woff, want);
+    std::vector<int64_t> toff((size_t)n_woff);
+    size_t need = 0;
+    if (int rc = jodo_cdgs_split_size(cfg, &need, toff.data(), n_woff)) return rc;
+    if (cap_bytes < need) return jodo_set_error(JODO_ERR_ARG, "cdgs_pack_split: buffer of %zu bytes, need %zu", cap_bytes, need);
+    size_t blob_floats = 0;
+    int nw = 0;
+    if (int rc = jodo_cdgs_packed_size(cfg, &blob_floats, &nw)) return rc;
+    for (const SplitSlot& s : split_slots(cfg)) {
+        const size_t tiles = (size_t)s.nb * s.nk;
+        if (woff[s.slot] < 0 || (size_t)woff[s.slot] + tiles * jd_tape::TILE_FLOATS > blob_floats)
+            return jodo_set_error(JODO_ERR_ARG, "cdgs_pack_split: weight offset of slot %d outside the packed blob", s.slot);
+        jd_tape::split_tiles(packed_host + woff[s.slot], tiles, reinterpret_cast<uint16_t*>(static_cast<char*>(tape_host) + toff[(size_t)s.slot]));
+    }
+    return JODO_OK;
 }

@@ -21,6 +21,7 @@
 #include <vector>
 #include "../../include/jodo_hip.h"
 #include "jodo_hip_internal.h"
+#include "split_tape.h"
 
 namespace {
 
@@ -251,9 +252,7 @@ extern "C" int jodo_dgt2d_pack_weights_host(const jodo_cfg2d* cfg, const jodo_te
 // ---- split-bf16 ("bf16x3") weight tape of the node GEMMs and the pair update (opt-in form, csrc/dgt2d_forward.hip) --------------------------------------
 // A function of the packed blob: every covered tiled matrix float [nb][nk][8 quads][64 lanes][4] is re-read as
 //     bf16 [nb][nk * 4 K16 steps][3 terms: hi, mid, lo][64 lanes][8]
-// where element j of lane l in K16 step G of a chunk is the chunk's f32 k-step 8 G + j of the same lane, tile[(8 G + j) / 4][l][(8 G + j) % 4]
-// (the relation of csrc/dgt_split.h between the two MFMA forms), so row maps and slot order have no second implementation.  Every term is
-// rounded to nearest even, as split8 rounds the activations; hi + mid + lo is the float exactly.
+// by jd_tape::split_tiles (csrc/split_tape.h, shared with the CDGS tape), so row maps and slot order have no second implementation.
 namespace {
 
 struct SplitSlot { int slot, nb, nk; };                   // slot: index into the woff table
@@ -276,20 +275,6 @@ std::vector<SplitSlot> split_slots(const jodo_cfg2d* c) {
     s.push_back({J2_NH2_W, D / 2 / 32, D / 64});
     s.push_back({J2_NH3_W, 1, D / 2 / 64});
     return s;
-}
-
-uint16_t bf16_rne(float v) {                              // finite inputs (weights); NaN keeps a quiet payload
-    uint32_t u;
-    std::memcpy(&u, &v, 4);
-    if ((u & 0x7f800000u) == 0x7f800000u) return (uint16_t)((u >> 16) | ((u & 0xffffu) ? 0x40u : 0u));
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-float bf16_f32(uint16_t b) {
-    const uint32_t u = (uint32_t)b << 16;
-    float v;
-    std::memcpy(&v, &u, 4);
-    return v;
 }
 
 }  // namespace
@@ -326,21 +311,7 @@ extern "C" int jodo_dgt2d_pack_split_host(const jodo_cfg2d* cfg, const float* pa
         const size_t tiles = (size_t)s.nb * s.nk;
         if (woff[s.slot] < 0 || (size_t)woff[s.slot] + tiles * 2048 > blob_floats)
             return jodo_set_error(JODO_ERR_ARG, "dgt2d_pack_split: weight offset of slot %d outside the packed blob", s.slot);
-        const float* src = packed_host + woff[s.slot];
-        uint16_t* dst = reinterpret_cast<uint16_t*>(static_cast<char*>(tape_host) + toff[(size_t)s.slot]);
-        for (size_t t = 0; t < tiles; ++t)
-            for (int G = 0; G < 4; ++G)
-                for (int l = 0; l < 64; ++l)
-                    for (int j = 0; j < 8; ++j) {
-                        const int k = 8 * G + j;
-                        const float v = src[t * 2048 + ((size_t)(k / 4) * 64 + l) * 4 + k % 4];
-                        const uint16_t hi = bf16_rne(v);
-                        const float r1 = v - bf16_f32(hi);
-                        const uint16_t mid = bf16_rne(r1);
-                        const float r2 = r1 - bf16_f32(mid);
-                        uint16_t* o = dst + (t * 4 + G) * 1536 + (size_t)l * 8 + j;
-                        o[0] = hi; o[512] = mid; o[1024] = bf16_rne(r2);
-                    }
+        jd_tape::split_tiles(packed_host + woff[s.slot], tiles, reinterpret_cast<uint16_t*>(static_cast<char*>(tape_host) + toff[(size_t)s.slot]));
     }
     return JODO_OK;
 }

@@ -5,8 +5,15 @@ Same constructor argument, parameter names / shapes / registration order (one `a
 `strict=True` loading, the 4-D conv weights and the GINE `eps` buffers included) and the same call as the reference class:
     model(t, x, node_mask, edge_mask, context=None, edge_x=...) -> (atom_score [B,N,atom_types], bond_score [B,N,N,edge_ch])
 The arithmetic runs in libjodo_hip.so (csrc/cdgs_forward.hip, `jodo_cdgs_forward`) on the current HIP stream: the weights are packed
-once (csrc/cdgs_pack.cpp), a descriptor and a workspace are built per batch of atom counts.  Exact fp32; there is no CPU or eager
-fallback, no split-bf16 form and no graph replay — those raise.  Training is opt-in: with `hip_training = True` (set by
+once (csrc/cdgs_pack.cpp), a descriptor and a workspace are built per batch of atom counts.  Exact fp32 by default; there is no CPU or
+eager fallback and no graph replay, and the 3-D models' `split_bf16` switch is not taken by this model — those raise.
+
+`model.bf16x3 = True` (opt-in, runtime state, read per call) selects the three-term bf16 form of every row GEMM over node rows and edge
+rows (`jodo_cdgs_forward_split`, kernel kc_gemm_s) from a weight tape derived from the packed blob; the time-embedding GEMMs, GINE,
+attention, the GroupNorms and the random-walk features stay exact fp32.  `model.last_flags[3]` tells that the split form ran (after a
+default call `last_flags` is None).  Sample quality under the split form is untested: no trained weights exist here.
+
+Training is opt-in: with `hip_training = True` (set by
 jodo_amd.losses.get_step_fn) a grad-enabled call runs csrc/cdgs_train.hip on the live parameters, keeps the activations, and
 loss.backward() returns every parameter's gradient (jodo_amd/train.py TrainEngineCDGS); unset, a grad-enabled call raises.
 
@@ -124,10 +131,13 @@ class CDGS(nn.Module):
 
         # ---- runtime state (not part of state_dict) ----
         self._packed = None           # (version key, device blob, woff ctypes array, n_woff)
+        self._tape = None             # (the _packed it was derived from, device tape, toff ctypes array): valid for that _packed only
         self._plans = {}              # per batch of atom counts: descriptor + workspace, keyed by the mask storage (see _plan)
         self.max_blocks = -1          # tests: stop after this many blocks (the workspace then holds h and e of that block)
-        self.last_flags = None        # kept for interface parity: this model has one walk (directed) and one arithmetic form
+        self.last_flags = None        # after a bf16x3 call: the 4 int32 words jodo_cdgs_forward_split wrote ([3] = 1); else None
         self.split_bf16 = False       # the 3-D models' opt-in form; not built for this model (forward raises when set)
+        self.bf16x3 = False           # opt-in, read per call: the split-bf16 (three-term) form of the node-row and edge-row GEMMs
+                                      # (kc_gemm_s).  Combines with max_blocks.  The training path ignores it.
         self.register_load_state_dict_post_hook(_drop_packed_after_load)
 
     # -- weights (same invalidation rules as DGT_concat_2D._weights) ---------------------------------
@@ -142,12 +152,29 @@ class CDGS(nn.Module):
         ts = self._tensors()
         key = (str(device),) + tuple(p._version for p in ts) + tuple(p.data_ptr() for p in ts)
         if self._packed is None or self._packed[0] != key:
+            self._tape = None
             sd = dict(self.state_dict())
             sd['time_freq'] = self._time_freq()
             host, woff_c, n_woff = capi.pack_weights_cdgs(self._cfg_struct, sd, None)
             self._packed = (key, host.to(device), woff_c, n_woff)
             self._packed_fingerprint = self._fingerprint()
+            if self.bf16x3:                              # the tape lives and dies with the blob it is derived from
+                self._split_tape(device, host)
         return self._packed
+
+    def _split_tape(self, device, blob_host=None):
+        """(device tape, toff) of the split-bf16 form for the current `_packed`: host conversion of the packed blob + one upload, when
+        the blob is re-packed with the switch on or on the first call with the switch on."""
+        packed, t = self._packed, self._tape
+        if t is None or t[0] is not packed:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("bf16x3 was switched on under graph capture for weights packed without it: run one eager call with "
+                                   "bf16x3 = True first")
+            if blob_host is None:
+                blob_host = packed[1].cpu()
+            tape, toff = capi.split_tape_cdgs(self._cfg_struct, blob_host, packed[2], packed[3], device)
+            t = self._tape = (packed, tape, toff)
+        return t[1], t[2]
 
     def _fingerprint(self):
         ps = [p.detach() for p in self._tensors()]
@@ -158,11 +185,13 @@ class CDGS(nn.Module):
     def _recheck_weights(self):
         if self._packed is not None and self._fingerprint() != getattr(self, '_packed_fingerprint', None):
             self._packed = None
+            self._tape = None
 
     def invalidate_packed_weights(self):
         """Drop the packed kernel weights; the next forward re-packs from the current parameters (needed after in-place `.data`
         updates that bump no tensor version, e.g. the reference's ExponentialMovingAverage.copy_to / restore)."""
         self._packed = None
+        self._tape = None
 
     # -- per-batch descriptor and workspace -----------------------------------------------------------
     def _plan(self, node_mask, edge_mask, device, validate=True):
@@ -192,7 +221,8 @@ class CDGS(nn.Module):
         desc_host = torch.empty(int(lay[0]), dtype=torch.int32)
         capi.check(L.jodo_cdgs_fill_desc(ctypes.byref(self._cfg_struct), B, N, n_ptr, ctypes.c_void_p(desc_host.data_ptr()),
                                          ctypes.c_int64(int(lay[0]))), 'jodo_cdgs_fill_desc')
-        plan = dict(desc=desc_host.to(device), ws=torch.zeros(int(lay[1]), dtype=torch.uint8, device=device), n_nodes=n_host, B=B, N=N,
+        plan = dict(desc=desc_host.to(device), ws=torch.zeros(int(lay[1]), dtype=torch.uint8, device=device),
+                    flags=torch.zeros(4, dtype=torch.int32, device=device), n_nodes=n_host, B=B, N=N,
                     Nn=int(lay[2]), rows=int(lay[3]), h_off=int(lay[4]), e_off=int(lay[5]), code_off=int(lay[6]), land_off=int(lay[7]),
                     mask=node_mask, mask_version=node_mask._version)
         self._plans.pop(key, None)
@@ -237,10 +267,16 @@ class CDGS(nn.Module):
         out_x = torch.empty_like(x_)
         out_e = torch.empty_like(ex_)
         n_ptr = plan['n_nodes'].ctypes.data_as(ctypes.c_void_p)
-        capi.check(capi.lib().jodo_cdgs_forward(ctypes.byref(self._cfg_struct), B, N, n_ptr, capi.ptr(plan['desc']), capi.ptr(blob), woff_c,
-                                                n_woff, capi.ptr(t_), capi.ptr(x_), capi.ptr(ex_), capi.ptr(out_x), capi.ptr(out_e),
-                                                capi.ptr(plan['ws']), int(self.max_blocks), capi.current_stream_ptr()),
-                   'jodo_cdgs_forward')
+        args = (ctypes.byref(self._cfg_struct), B, N, n_ptr, capi.ptr(plan['desc']), capi.ptr(blob), woff_c, n_woff, capi.ptr(t_),
+                capi.ptr(x_), capi.ptr(ex_), capi.ptr(out_x), capi.ptr(out_e), capi.ptr(plan['ws']), int(self.max_blocks),
+                capi.current_stream_ptr())
+        if self.bf16x3:
+            tape, toff = self._split_tape(dev)
+            capi.check(capi.lib().jodo_cdgs_forward_split(*args, capi.ptr(tape), toff, capi.ptr(plan['flags'])), 'jodo_cdgs_forward_split')
+            self.last_flags = plan['flags']
+        else:
+            capi.check(capi.lib().jodo_cdgs_forward(*args), 'jodo_cdgs_forward')
+            self.last_flags = None
         self._last_plan = plan
         return out_x, out_e
 

@@ -3,7 +3,7 @@ the HIP path would run on the same GPU: the dense torch evaluation of the same n
 under the same sampler.  Both legs run in this one command on the same GPU, on the same batch.
 
     python tools/bench_cdgs.py [--workload qm9|geom] [--batches 500,2000] [--steps 50] [--warmup 5] [--no-baseline] [--out-dir profiles]
-                               [--kernel-stats CSV --kernel-stats-steps K]
+                               [--kernel-stats CSV --kernel-stats-steps K] [--split off|on|both] [--repeats R]
 
 Atom counts are drawn from the training histogram of the config's dataset (`qm9_with_h`, seed 42).  Timing as bench.py does it: warm-up,
 synchronise, `steps` sampler.step calls, synchronise.  Per batch size it writes profiles/cdgs_<workload>_b<B>.json: ms/step of both
@@ -14,6 +14,13 @@ are executed.  The dense leg evaluates the whole padded batch at once: chunking 
 it this model's result.
 --kernel-stats: the kernel table of a `rocprofv3 --kernel-trace --stats` run of this tool with --no-baseline (a run of its own); its kc_*
 rows per sampler step are added to the record of the largest batch.
+--split (default off: everything above, unchanged): `on` times the opt-in split-bf16 form (model.bf16x3 = True) alone and writes
+cdgs_<workload>_b<B>_split_on.json - the command to profile for the split form's kernel table; `both` alternates the exact and the split
+form in this one process on the same batch, --repeats times each (exact, split, exact, split, ...; `steps` sampler steps per leg after
+one shared warm-up of both forms), and writes cdgs_<workload>_b<B>_split.json: every leg's ms/step, the mean per form, split / exact, and
+per form the run-to-run spread (max - min of its legs) - a difference between the forms counts only beyond that spread.  No dense leg in
+these modes.  With `both`, --kernel-stats / --kernel-stats-exact take the kernel tables of profiled `--split on` / `--split off
+--no-baseline` runs of the same workload, batch, steps and warm-up.
 """
 import argparse
 import csv
@@ -92,6 +99,35 @@ def kernel_split(csv_path, sampler_steps):
     return dict(sorted(out.items(), key=lambda kv: -kv[1]))
 
 
+def split_record(args, model, sampler, z, edge_z, nm, em, base):
+    """--split on | both: the legs of one batch; returns the record"""
+    forms = ['split'] if args.split == 'on' else ['exact', 'split']
+    ran, legs, finite = {}, {f: [] for f in forms}, True
+    for f in forms:                                                                  # shared warm-up: plan, blob and tape exist before any leg
+        model.bf16x3 = f == 'split'
+        time_steps(sampler, model, z, edge_z, nm, em, args.warmup, 1)
+        ran[f] = None if model.last_flags is None else int(model.last_flags[3].item())
+    for _ in range(args.repeats):
+        for f in forms:
+            model.bf16x3 = f == 'split'
+            ms, st = time_steps(sampler, model, z, edge_z, nm, em, 0, args.steps)
+            legs[f].append(round(ms, 3))
+            finite = finite and bool(torch.isfinite(st['x']).all() and torch.isfinite(st['edge_x']).all())
+    model.bf16x3 = False
+    assert ran['split'] == 1 and ran.get('exact') is None, ran
+    out = dict(base, split=args.split, repeats=args.repeats, finite=finite, split_form_ran=ran['split'])
+    for f in forms:
+        mean = sum(legs[f]) / len(legs[f])
+        out.update({f + '_ms_per_step_legs': legs[f], f + '_ms_per_step': round(mean, 3),
+                    f + '_spread_ms': round(max(legs[f]) - min(legs[f]), 3),
+                    f + '_fraction_of_fp32_mfma_peak': round(base['flops_per_step'] / mean * 1e-9 / PEAK_TFLOPS, 4)})
+    if args.split == 'both':
+        spread = max(out['exact_spread_ms'], out['split_spread_ms'])
+        out.update(split_over_exact_time=round(out['split_ms_per_step'] / out['exact_ms_per_step'], 4), spread_ms=spread,
+                   split_faster_beyond_spread=bool(out['exact_ms_per_step'] - out['split_ms_per_step'] > spread))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--workload', default='qm9', choices=sorted(WORKLOADS))
@@ -102,6 +138,9 @@ def main():
     ap.add_argument('--out-dir', default=os.path.join(ROOT, 'profiles'))
     ap.add_argument('--kernel-stats', default=None)
     ap.add_argument('--kernel-stats-steps', type=int, default=None, help='sampler steps (warm-up included) of the profiled run')
+    ap.add_argument('--split', default='off', choices=['off', 'on', 'both'], help='the opt-in split-bf16 form (model.bf16x3)')
+    ap.add_argument('--repeats', type=int, default=3, help='--split on | both: timed legs per form')
+    ap.add_argument('--kernel-stats-exact', default=None, help='--split both: kernel-stats CSV of the exact form\'s profiled run')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     cfg = configs.get(WORKLOADS[args.workload])
@@ -121,6 +160,24 @@ def main():
         edge_z = sample_symmetric_edge_feature_noise(B, N, cfg.model.edge_ch, em)
         pairs = sum(n * (n - 1) for n in n_nodes)
         flops, pair_flops = flops_per_step(model, n_nodes)
+        if args.split != 'off':
+            base = dict(tool='tools/bench_cdgs.py', workload=args.workload, config=WORKLOADS[args.workload], batch=B, padded_width=N,
+                        atoms=sum(n_nodes), ordered_pairs=pairs, edge_rows_executed=sum(n * n for n in n_nodes), steps=args.steps,
+                        warmup=args.warmup, flops_per_step=flops, peak_tflops=PEAK_TFLOPS)
+            out = split_record(args, model, sampler, z, edge_z, nm, em, base)
+            ksteps = args.kernel_stats_steps or args.warmup + args.steps
+            for key, path in (('split', args.kernel_stats), ('exact', args.kernel_stats_exact)):
+                if path and B == max(batches):
+                    out[key + '_kernel_ms_per_step'] = kernel_split(path, ksteps)
+                    out[key + '_kernel_stats_source'] = os.path.basename(path)
+            os.makedirs(args.out_dir, exist_ok=True)
+            name = 'cdgs_%s_b%d_split%s.json' % (args.workload, B, '' if args.split == 'both' else '_on')
+            with open(os.path.join(args.out_dir, name), 'w') as f:
+                json.dump(out, f, indent=1)
+            print(json.dumps(out), flush=True)
+            del z, edge_z
+            torch.cuda.empty_cache()
+            continue
         ms, st = time_steps(sampler, model, z, edge_z, nm, em, args.warmup, args.steps)
         out = dict(tool='tools/bench_cdgs.py', workload=args.workload, config=WORKLOADS[args.workload], batch=B, padded_width=N,
                    atoms=sum(n_nodes), ordered_pairs=pairs, edge_rows_executed=sum(n * n for n in n_nodes), steps=args.steps,
