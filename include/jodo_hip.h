@@ -142,7 +142,14 @@ int jodo_plan_stats(const jodo_plan* plan, int64_t* out6);
  *              [4] = edge inputs were not symmetric (directed kernels used), [5] = STICKY count of calls in which
  *              the NaN guard fired (only ever incremented by the library; the caller clears it when it reads it),
  *              [6] = STICKY pin violations (JODO_OPT_PIN_*: bit 0 symmetry, bit 1 shared row), [7] reserved
- *   workspace: jodo_plan_workspace_bytes() bytes of device scratch
+ *   workspace: jodo_plan_workspace_bytes() bytes of device scratch, the caller's, kept between calls on the same plan.  What a caller
+ *              may leave in it: ANY FINITE float32 values (zero-fill it once before the first call; torch.empty / hipMalloc memory may
+ *              hold NaN bit patterns).  Outputs do not depend on the content — neither on another call's leftovers nor on finite garbage
+ *              (tests/test_forms_gpu.py poisons it) — with one exception: the two copies of the dense edge state ([sum n^2 + 32, nf / 4]
+ *              floats each) must not hold NaN / Inf, because the pair path never writes the diagonal rows (i, i) of a molecule's n x n
+ *              tile (nor, under JODO_OPT_HALF_ROWS, the mirror row of a pair) and reads them against a zero weight.  The library never
+ *              writes a non-finite value into those rows, so one fill is enough for the life of the workspace; every other array
+ *              may hold anything, NaN included.
  *   dbg: optional device buffer for intermediates (tests) or NULL */
 int jodo_dgt_forward(jodo_plan* plan, const void* desc_dev, const float* packed_w, const int64_t* woff,
                      int n_woff, const float* xh, const float* edge_x, const float* cond_x,
@@ -167,7 +174,8 @@ enum jodo_plan_option {
                                    * 12 / 14: automatic split, 2 / 4 waves per strip of the remainder launch */
     JODO_OPT_ATTN_VARIANT = 3,    /* nf 256 pair attention kernel, weight residency / hand-over granularity: 0 (default), 1, 2, 3 (dgt_kernels_attn.h); other values are rejected */
     /* Path pinning.  By default every forward launches every kernel variant and device flags decide which ones work (no host
-     * sync); the idle variants cost a dispatch each (~5 us, 24 per forward at 8 blocks).  Inside one sampling round the inputs
+     * sync); the idle variants cost a dispatch each (~5 us, 24 per forward at 8 blocks; counted by jodo_profile_read_kernels in
+     * tests/test_dgt_gpu.py: 88 -> 62 launches at QM9 B = 2500, i.e. 26 with the heads' two; 81 -> 63 for the conditional model).  Inside one sampling round the inputs
      * stay symmetric and the noise level stays shared, so a caller that has read flags [2] / [4] of one call may pin them for the
      * following calls on this plan: only the working variants are then launched.  A call that violates a pin (e.g. asymmetric
      * inputs under a symmetric pin) is detected on the device: flags[6] gets bit 0 (symmetry pin) / bit 1 (shared-row pin), sticky,
@@ -242,13 +250,17 @@ int jodo_debug_set_timing_buffer(jodo_plan* plan, void* dev16xu64);
  * packets per class boundary cost ~10 us each: ~0.5 ms per forward at 8 blocks); enable = 2 brackets only the
  * dominant class JODO_PROF_EDGE_UPDATE (~0.1 ms); enable = 16 + c brackets only class c (what the roofline leg needs: the class that was largest in
  * this run's warm-up); jodo_profile_read synchronises those events and returns, per class, the summed
- * milliseconds and launch counts since the last read (arrays of JODO_PROF_COUNT), then resets. */
+ * milliseconds and the number of BRACKETS (event pairs: one per class and block, whatever the plan's pins and options — not kernel
+ * launches) since the last read (arrays of JODO_PROF_COUNT), then resets.  jodo_profile_read_kernels returns, per class, the number of
+ * KERNEL LAUNCHES issued inside those brackets since its last call (a host counter; idle variants that exit on a device flag count, they
+ * are dispatches), then resets: what a pin or a launch-merging option changes. */
 enum jodo_prof_class {
     JODO_PROF_PROLOGUE = 0, JODO_PROF_NODE_PRE, JODO_PROF_EDGE_ATTN, JODO_PROF_RESERVED3, JODO_PROF_RESERVED4,
     JODO_PROF_NODE_POST, JODO_PROF_EDGE_UPDATE, JODO_PROF_EPILOGUE, JODO_PROF_COUNT
 };
 int jodo_profile_enable(jodo_plan* plan, int enable);
 int jodo_profile_read(jodo_plan* plan, float* ms_sum, int32_t* launches);
+int jodo_profile_read_kernels(jodo_plan* plan, int32_t* kernels);
 
 /* ---- caller-side kernels of the sampling loop ---------------------------
  * jodo_sampler_step  <- the update of AncestralSampler.sampling, sampling.py:536-589, with the noise
@@ -771,7 +783,10 @@ int jodo_debug_mlp(const float* x, int rows, const float* w1, const float* b1, c
  * diagonal rows included (they are zero between blocks and carry FF(2 h_i) inside the edge GroupNorm statistics).
  * jodo_cdgs_layout: out[0] = int32 words of the descriptor, out[1] = workspace bytes, out[2] = Nn, out[3] = R = sum n_b^2, byte offsets
  * into the workspace of out[4] = h [Nn, nf], out[5] = e [R, nf], out[6] = the distance codes (int32 [R]), out[7] = the landing
- * probabilities (float [Nn, 16], the first rw_depth live).  The workspace must be zero when first used and is the caller's.
+ * probabilities (float [Nn, 16], the first rw_depth live).  The workspace is the caller's.  What it may hold: any FINITE float32
+ * values (zero-fill it once).  Outputs do not depend on them (every forward writes the zero row of its [h ; 0] GEMM itself); NaN / Inf
+ * are not allowed because the head inputs are padded to a multiple of 64 columns (the edge head's also between dense_cate and
+ * dense_exist, columns 77 .. 95) that no kernel writes and that meet zero weight columns.
  * jodo_cdgs_fill_desc writes the descriptor into HOST memory: n_b [B], noff_b [B], eoff_b [B], b per real atom [Nn], b per edge row [R].
  * jodo_cdgs_forward: t [B], x [B, N, atom_ch], edge_x [B, N, N, edge_ch] -> out_x [B, N, atom_ch], out_e [B, N, N, edge_ch], masked.
  * max_blocks in [0, n_layers]: stop after that many blocks (0: after the embeddings) with h and e in the workspace; the outputs are then

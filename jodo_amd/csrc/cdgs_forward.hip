@@ -381,6 +381,9 @@ __global__ __launch_bounds__(256) void kc_embed_edges(KC A) {
 __global__ __launch_bounds__(256) void kc_zero_diag(KC A) {
     const int node = blockIdx.x, b = A.node_b[node], n = A.mol_n[b], i = node - A.mol_noff[b];
     A.e[((size_t)A.mol_eoff[b] + (size_t)i * n + i) * DC + threadIdx.x] = 0.f;
+    // row Nn of hc: the "0" of the [h ; 0] rows whose FF(0) the padded partners read; no kernel of a block writes it, so it is
+    // written here on every forward instead of being left to the workspace's first zero fill
+    if (node == 0) A.hc[(size_t)A.Nn * DC + threadIdx.x] = 0.f;
 }
 
 // ---- block -------------------------------------------------------------------------------------------------------------------------
@@ -653,7 +656,7 @@ static int forward_cdgs(const jodo_cdgs_cfg* cfg, int B, int N, const int32_t* n
         LCD(kc_gn2, Nn, 256, Nn, (const float*)A.hc, (const float*)f2, W + A.wb[JCB_NN_G], W + A.wb[JCB_NN_B], (const float*)nullptr,
             (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, A.h);
         if ((rc = mm(0, A.h, D, Nn, D, slot0 + JCB_RN_W, W + A.wb[JCB_RN_B], l.catp, 0, A.ahid + lyr * l.catp, l.KA))) return rc;
-        // edge path: e <- e + FF(h_r + h_c) in place; FF(h_i) and FF(0) for the padded positions (row Nn of hc is zero and never written)
+        // edge path: e <- e + FF(h_r + h_c) in place; FF(h_i) and FF(0) for the padded positions (row Nn of hc is the zero row: kc_zero_diag writes it, no block does)
         if ((rc = mm(2, A.hc, D, l.R, D, slot0 + JCB_FF3_W, W + A.wb[JCB_FF3_B], 2 * D, 1, A.tmp, 2 * D))) return rc;
         if ((rc = mm(0, A.tmp, 2 * D, l.R, 2 * D, slot0 + JCB_FF4_W, W + A.wb[JCB_FF4_B], D, 0, A.e, D, A.e, D))) return rc;
         if ((rc = mm(0, A.hc, D, Nn + 1, D, slot0 + JCB_FF3_W, W + A.wb[JCB_FF3_B], 2 * D, 1, x1, 2 * D))) return rc;

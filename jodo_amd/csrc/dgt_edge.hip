@@ -9,6 +9,9 @@ using namespace jd;
 
 namespace {
 
+// a launch that the plan's profiling brackets count (jodo_profile_read_kernels); errors are collected by the caller's jodo_check_launch
+#define KLAUNCH(...) do { hipLaunchKernelGGL(__VA_ARGS__); jodo_note_launch(); } while (0)
+
 // Pair update: one-iteration items, one wave each, every full round of 1024 (one per SIMD) in one launch; the items of the last,
 // sparsely filled round in a second launch that gives each item several waves:
 //   * hoisted forms (nf 256; any width under a shared modulation row): ZW = 2 / 4 waves share the output blocks of the per-pair
@@ -20,12 +23,12 @@ void launch_sym_variant(hipStream_t st, KArgs& A, int n_items, int zw) {
     if (!(D == 256 || FOLD)) zw = 1;                      // (the un-hoisted form has no per-pair Z to deal out)
     const int full = zw > 1 ? (n_items / 1024) * 1024 : n_items, rem = n_items - full;
     A.item0 = 0; A.dir_split = 0;
-    if (full > 0) hipLaunchKernelGGL((wide::k_edge_update_sym<D, R, FOLD, ROT>), dim3(full), dim3(64), 0, st, A);
+    if (full > 0) KLAUNCH((wide::k_edge_update_sym<D, R, FOLD, ROT>), dim3(full), dim3(64), 0, st, A);
     if (rem > 0) {
         A.item0 = full;
         if constexpr (D == 256 || FOLD) {
-            if (zw == 4) hipLaunchKernelGGL((wide::k_edge_update_sym<D, R, FOLD, ROT, 4>), dim3(rem), dim3(256), 0, st, A);
-            else hipLaunchKernelGGL((wide::k_edge_update_sym<D, R, FOLD, ROT, 2>), dim3(rem), dim3(128), 0, st, A);
+            if (zw == 4) KLAUNCH((wide::k_edge_update_sym<D, R, FOLD, ROT, 4>), dim3(rem), dim3(256), 0, st, A);
+            else KLAUNCH((wide::k_edge_update_sym<D, R, FOLD, ROT, 2>), dim3(rem), dim3(128), 0, st, A);
         }
         A.item0 = 0;
     }
@@ -54,8 +57,8 @@ int launch_update_sym(jodo_plan* p, hipStream_t st, KArgs& A) {
     if constexpr (D == 256) {
         if (run_plain && !run_fold && A.split_cond && A.wsplit && n1 > 0) {
             const int wgs = (p->n_pitems + 31) / 32 * 8;
-            if (d.r == 2) hipLaunchKernelGGL((split::k_edge_update_sym_split_cond<D, 2>), dim3(wgs), dim3(split::SPLIT_WAVES * 64), 0, st, A);
-            else hipLaunchKernelGGL((split::k_edge_update_sym_split_cond<D, 4>), dim3(wgs), dim3(split::SPLIT_WAVES * 64), 0, st, A);
+            if (d.r == 2) KLAUNCH((split::k_edge_update_sym_split_cond<D, 2>), dim3(wgs), dim3(split::SPLIT_WAVES * 64), 0, st, A);
+            else KLAUNCH((split::k_edge_update_sym_split_cond<D, 4>), dim3(wgs), dim3(split::SPLIT_WAVES * 64), 0, st, A);
             split_cond_ran = true;
         }
     }
@@ -70,8 +73,8 @@ int launch_update_sym(jodo_plan* p, hipStream_t st, KArgs& A) {
     if constexpr (D == 256 || D == 384) {
         if (run_fold && !run_plain && A.rot == 1 && A.wsplit && A.mfold_s) {
             const int wgs = (p->n_pitems + 31) / 32 * 8;
-            if (d.r == 2) hipLaunchKernelGGL((split::k_edge_update_sym_split<D, 2>), dim3(wgs), dim3(split::SPLIT_WAVES * 64), 0, st, A);
-            else hipLaunchKernelGGL((split::k_edge_update_sym_split<D, 4>), dim3(wgs), dim3(split::SPLIT_WAVES * 64), 0, st, A);
+            if (d.r == 2) KLAUNCH((split::k_edge_update_sym_split<D, 2>), dim3(wgs), dim3(split::SPLIT_WAVES * 64), 0, st, A);
+            else KLAUNCH((split::k_edge_update_sym_split<D, 4>), dim3(wgs), dim3(split::SPLIT_WAVES * 64), 0, st, A);
             split_ran = true;
         }
     }

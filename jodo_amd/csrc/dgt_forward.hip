@@ -68,22 +68,26 @@ int rowgemm(hipStream_t st, const float* X, int64_t ldx, float* Y, int64_t ldy, 
     dim3 grid((rows + 31) / 32, (NB + nob - 1) / nob);
     if (gx) grid = dim3(grid.y, grid.x);
     hipLaunchKernelGGL(k_rowgemm, grid, dim3(64), 0, st, G);
+    jodo_note_launch();
     return jodo_check_launch("k_rowgemm");
 }
 
 // event bracket for one launch class (no-op unless profiling is enabled on the plan)
 struct ProfScope {
-    jodo_plan* p; hipStream_t st; int cls; bool on;
+    jodo_plan* p; hipStream_t st; int cls; bool on; long long k0;
     static hipEvent_t get(jodo_plan* p) {
         if (!p->prof_pool.empty()) { hipEvent_t e = (hipEvent_t)p->prof_pool.back(); p->prof_pool.pop_back(); return e; }
         hipEvent_t e; (void)hipEventCreate(&e); return e;
     }
     ProfScope(jodo_plan* p_, hipStream_t st_, int cls_)
-        : p(p_), st(st_), cls(cls_), on(p_->prof_enabled == 1 || (p_->prof_enabled == 2 && cls_ == JODO_PROF_EDGE_UPDATE) || p_->prof_enabled == 16 + cls_) {
-        if (on) { hipEvent_t e = get(p); (void)hipEventRecord(e, st); p->prof_ev.push_back(e); }
+        : p(p_), st(st_), cls(cls_), on(p_->prof_enabled == 1 || (p_->prof_enabled == 2 && cls_ == JODO_PROF_EDGE_UPDATE) || p_->prof_enabled == 16 + cls_), k0(0) {
+        if (on) { hipEvent_t e = get(p); (void)hipEventRecord(e, st); p->prof_ev.push_back(e); k0 = jodo_launches_noted(); }
     }
     ~ProfScope() {
-        if (on) { hipEvent_t e = get(p); (void)hipEventRecord(e, st); p->prof_ev.push_back(e); p->prof_cls.push_back(cls); }
+        if (on) {
+            hipEvent_t e = get(p); (void)hipEventRecord(e, st); p->prof_ev.push_back(e); p->prof_cls.push_back(cls);
+            p->prof_kernels[cls] += jodo_launches_noted() - k0;          // the kernels launched inside the bracket (jodo_profile_read_kernels)
+        }
     }
 };
 

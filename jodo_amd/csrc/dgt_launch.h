@@ -14,6 +14,7 @@
     do {                                                                \
         auto kf_ = kern;                                                \
         hipLaunchKernelGGL(kf_, dim3(grid), dim3(block), 0, st, __VA_ARGS__); \
+        jodo_note_launch();                                             \
         int rc_ = jodo_check_launch(#kern);                             \
         if (rc_ != JODO_OK) return rc_;                                 \
     } while (0)

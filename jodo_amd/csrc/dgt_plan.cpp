@@ -120,6 +120,7 @@ extern "C" int jodo_plan_create(const jodo_cfg* cfg, int B, int N, const int32_t
     p->opt[JODO_OPT_PIN_SYMMETRIC] = 0; p->opt[JODO_OPT_PIN_UNIFORM_T] = 0; p->opt[JODO_OPT_ROT_STATS] = 1; p->opt[JODO_OPT_NODE_MIX] = 1;
     p->opt[JODO_OPT_SPLIT_BF16] = 0; p->split_w = nullptr; p->split_bytes = 0;
     p->prof_enabled = 0; p->force_directed = 0; p->dbg_timing = nullptr;
+    for (int c = 0; c < JODO_PROF_COUNT; ++c) p->prof_kernels[c] = 0;
 
     // molecules by descending size (stable): neighbouring lanes share n, big work first
     std::vector<int> order(B);
@@ -441,6 +442,11 @@ extern "C" int jodo_profile_read(jodo_plan* p, float* ms_sum, int32_t* launches)
         p->prof_pool.push_back(p->prof_ev[i]); p->prof_pool.push_back(p->prof_ev[i + 1]);
     }
     p->prof_ev.clear(); p->prof_cls.clear();
+    return JODO_OK;
+}
+extern "C" int jodo_profile_read_kernels(jodo_plan* p, int32_t* kernels) {
+    if (!p || !kernels) return jodo_set_error(JODO_ERR_ARG, "profile_read_kernels: null");
+    for (int c = 0; c < JODO_PROF_COUNT; ++c) { kernels[c] = (int32_t)p->prof_kernels[c]; p->prof_kernels[c] = 0; }
     return JODO_OK;
 }
 extern "C" size_t jodo_plan_desc_bytes(const jodo_plan* p) { return p ? p->desc.size() * sizeof(int32_t) : 0; }

@@ -93,6 +93,7 @@ struct jodo_plan {
     std::vector<void*> prof_ev;      // hipEvent_t start/stop pairs in record order
     std::vector<int> prof_cls;       // class of each pair
     std::vector<void*> prof_pool;    // reusable events
+    int64_t prof_kernels[JODO_PROF_COUNT];   // kernel launches issued inside the brackets of each class since the last jodo_profile_read_kernels
     int force_directed;              // debug: always take the directed (non-pair) kernels
     void* dbg_timing;                // debug: device buffer of 16 x u64 phase-cycle sums (or null)
     int max_blocks;                  // debug: limit blocks executed (<0 = all)

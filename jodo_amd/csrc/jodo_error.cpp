@@ -16,6 +16,10 @@ extern "C" int jodo_set_error(int code, const char* fmt, ...) {
 
 extern "C" const char* jodo_last_error(void) { return g_err; }
 
+static thread_local long long g_launches = 0;
+extern "C" void jodo_note_launch(void) { ++g_launches; }
+extern "C" long long jodo_launches_noted(void) { return g_launches; }
+
 extern "C" int jodo_check_launch(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return jodo_set_error(JODO_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));

@@ -254,7 +254,8 @@ class _DGTBase(nn.Module):
         L.jodo_plan_desc_bytes.restype = ctypes.c_size_t
         L.jodo_plan_workspace_bytes.restype = ctypes.c_size_t
         desc = torch.empty(L.jodo_plan_desc_bytes(handle), dtype=torch.uint8, device=device)
-        # zero-filled once: rows the kernels never write (diagonal edge rows on the pair path) must stay finite
+        # zero-filled once: rows the kernels never write (diagonal edge rows of the two edge-state copies on the pair path) must stay
+        # FINITE; their values do not matter (include/jodo_hip.h, jodo_dgt_forward; tests/test_forms_gpu.py runs on poisoned scratch)
         ws = torch.zeros(L.jodo_plan_workspace_bytes(handle), dtype=torch.uint8, device=device)
         if getattr(self, 'force_directed', False):       # tests: never use the symmetric pair kernels
             capi.check(L.jodo_debug_set_force_directed(handle, 1), 'jodo_debug_set_force_directed')
@@ -582,6 +583,16 @@ class _DGTBase(nn.Module):
             ms_t = [a + b for a, b in zip(ms_t, ms)]
             cnt_t = [a + b for a, b in zip(cnt_t, cnt)]
         return ms_t, cnt_t
+
+    def profile_read_kernels(self):
+        """Kernel launches per class (8) issued inside the profiling brackets since the last read, over the last call's plans:
+        profile_read's counts are brackets (one per class and block); these are the dispatches that pins and plan options change."""
+        tot = [0] * 8
+        for p in self._last_plans:
+            k = (ctypes.c_int32 * 8)()
+            capi.check(capi.lib().jodo_profile_read_kernels(p['handle'], k), 'jodo_profile_read_kernels')
+            tot = [a + b for a, b in zip(tot, k)]
+        return tot
 
     def work_model(self):
         """Executed MFMA flops per launch class of ONE evaluation like the last one (jodo_plan_work, summed over its plans)."""

@@ -11,6 +11,7 @@ import torch
 
 from oracle import dgt_oracle as O
 
+from forms_common import DeviceBatch, assert_pinned_call
 from helpers import (check_decodes, close64, debug_fetch, load_fixture, make_config, make_model, masks, oracle_32_64, random_inputs,
                      reference_blocks_dense, state_dict_cpu, K64, K64_HARD, K64_ROT_BIG, k64_for)
 
@@ -650,24 +651,43 @@ def test_full_size_batches_match_oracle_on_sampled_molecules(cfg_name, info, B, 
     xh[:, :, :3] -= xh[:, :, :3].sum(1, keepdim=True) / nm.sum(1, keepdim=True) * nm
     nl[:] = 0.5                                                              # sampling: one noise level per batch
     shared = 0 if hp.cond_ch else 1                          # conditional: the context makes every modulation row different
-    x1, e1 = run(model, xh, ex, nl, nm, em, None, None, ctx)
+    # masks (the plan key, _DGTBase._plan) and inputs go to the device ONCE: every call below runs on the same plan.  The module-level
+    # `run` moves the masks on every call — a new address, hence a new unpinned plan on zeroed scratch each time — which is how this
+    # test used to compare the flag-dispatched path with itself.
+    batch = DeviceBatch(xh, ex, nl, nm, em, ctx, DEV)
+    x1, e1 = batch(model)
     fl = model.last_flags.cpu().tolist()
     assert (fl[0], fl[2], fl[3], fl[4]) == (0, shared, 0, 0)      # no NaN, shared time row, first-step branch (:544), pair path
-    x2, e2 = run(model, xh, ex, nl, nm, em, x1, e1, ctx)
+    x2, e2 = batch(model, x1, e1)
     fl = model.last_flags.cpu().tolist()
     assert (fl[0], fl[2], fl[3], fl[4]) == (0, shared, 1, 0)      # self-conditioned branch
+    assert len(model._plans) == 1
+    # launches per forward: profile_read() counts BRACKETS (one per class and block: 2 + 4 L with or without pins, asserted below);
+    # profile_read_kernels() counts the kernel launches issued inside them, which is what a pin takes away
+    model.profile_enable(1)
+    model.profile_read(), model.profile_read_kernels()
+    batch(model, x1, e1)
+    brackets_flag, launches_flag = sum(model.profile_read()[1]), sum(model.profile_read_kernels())
     # The configuration the samplers (and bench.py's timed region) run: pin_paths() after the first self-conditioned evaluation —
     # half rows, merged heads, only the launches the flags leave.  Same kernels on the same values: bit-identical at the full
     # batch (k_node_mix, straddled attention groups, the merged heads' second round only exist at this size), and it is the
     # PINNED outputs that go to the oracle below.
-    model.pin_paths()
-    assert model._last_plan.get('pinned')
-    p2x, p2e = run(model, xh, ex, nl, nm, em, x1, e1, ctx)
-    p1x, p1e = run(model, xh, ex, nl, nm, em, None, None, ctx)
+    pinned_plan = batch.pin(model)
+    p2x, p2e = batch(model, x1, e1)                               # (every call under the pin asserts AFTER it ran that it ran on the pinned plan)
+    brackets_pin, launches_pin = sum(model.profile_read()[1]), sum(model.profile_read_kernels())
+    model.profile_enable(0)
+    p1x, p1e = batch(model)
+    assert model._last_plan.get('pinned') and model._last_plan is pinned_plan and len(model._plans) == 1
     assert model.take_nan_count() == 0                            # (also raises if a pin was violated)
+    # fewer launches under the pin: the idle variants are gone ("24 per forward at 8 blocks", pin_paths' docstring, is the expectation
+    # the printed numbers are to be compared with; the difference itself is not hard-coded)
+    print("%s B=%d %r: launches per self-conditioned forward flag-dispatched %d, pinned %d (difference %d, %d blocks; brackets %d / %d)" % (
+        cfg_name, B, over, launches_flag, launches_pin, launches_flag - launches_pin, hp.n_layers, brackets_flag, brackets_pin))
+    assert brackets_flag == brackets_pin == 2 + 4 * hp.n_layers
+    assert 0 < launches_pin < launches_flag
     for name, a, b in (('x1', x1, p1x), ('e1', e1, p1e), ('x2', x2, p2x), ('e2', e2, p2e)):
         assert torch.equal(a, b), "pinned != flag-dispatched on %s: max |diff| %.3e" % (name, (a - b).abs().max().item())
-    model.unpin_paths()
+    batch.unpin(model)
     x1, e1, x2, e2 = p1x, p1e, p2x, p2e
     N = max(n_nodes)
     for x, e in ((x1, e1), (x2, e2)):
@@ -1037,8 +1057,12 @@ def test_pinned_paths_equal_flag_dispatch(cfg_name, n_nodes, uniform, over):
     assert flags[4] == 0 and flags[2] == (1 if uniform and not hp.cond_ch else 0)
     model.pin_paths()
     assert model._last_plan.get('pinned')
+    pinned = list(model._last_plans)
     b2 = call(a1[0], a1[1])
+    assert_pinned_call(model, pinned)                        # AFTER the call: it ran on the plan that was pinned, not on a new one
     b1 = call()
+    assert_pinned_call(model, pinned)
+    assert len(model._plans) == 1
     assert torch.equal(a1[0], b1[0]) and torch.equal(a1[1], b1[1]) and torch.equal(a2[0], b2[0]) and torch.equal(a2[1], b2[1])
     assert model.take_nan_count() == 0
     bad = ex.clone()
@@ -1083,7 +1107,10 @@ def test_stream_interleaved_sub_batches_equal_single_stream(cfg_name, n_nodes, k
     a2 = run(one, xh, ex, nl, nm, em, a1[0], a1[1], ctx)
     b2 = split_call(a1[0], a1[1])
     many.pin_paths()
+    pinned = list(many._last_plans)
+    assert len(pinned) == k and all(p.get('pinned') for p in pinned)
     b3 = split_call(a1[0], a1[1])
+    assert_pinned_call(many, pinned)                         # AFTER the call: every sub-batch ran on its pinned plan
     close(b2[0], a2[0], atol=2e-5)
     close(b2[1], a2[1], atol=2e-5)
     assert torch.equal(b2[0], b3[0]) and torch.equal(b2[1], b3[1]) and many.take_nan_count() == 0

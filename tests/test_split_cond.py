@@ -14,6 +14,7 @@ from jodo_amd import capi, configs
 from jodo_amd.models import get_model_class, deterministic_init_
 from oracle import dgt_oracle as O
 
+from forms_common import assert_pinned_call
 from helpers import K64, close64, load_fixture, make_config, make_model, masks, oracle_32_64, random_inputs, state_dict_cpu
 
 DEV = 'cuda:0'
@@ -131,8 +132,11 @@ def test_conditional_split_pair_update_against_the_default_path_and_float64(over
         _run(model, xh, ex, nl, ctx, nmd, emd, first[0], first[1])
         model.pin_paths()
         assert model._last_plan.get('pinned') and (('split_tape' in model._last_plan) == split)
+        pinned = list(model._last_plans)
         o2 = _run(model, xh, ex, nl, ctx, nmd, emd, first[0], first[1])
+        assert_pinned_call(model, pinned)                          # AFTER the call: it ran on the plan that was pinned
         o1 = _run(model, xh, ex, nl, ctx, nmd, emd)
+        assert_pinned_call(model, pinned)
         if split:
             _split_ran(model)
         assert model.take_nan_count() == 0
@@ -178,10 +182,13 @@ def test_reference_conditional_fixture_through_the_split_path():
     _close(o1[0], t('out1_x')); _close(o1[1], t('out1_e'))
     _run(model, *args, t('out1_x'), t('out1_e'))
     model.pin_paths()
+    pinned = list(model._last_plans)
     o2 = _run(model, *args, t('out1_x'), t('out1_e'))
+    assert_pinned_call(model, pinned)                             # AFTER the call: it ran on the plan that was pinned
     _split_ran(model)
     _close(o2[0], t('out2_x')); _close(o2[1], t('out2_e'))
     o1p = _run(model, *args)                                      # and the first call under the pin
+    assert_pinned_call(model, pinned)
     _close(o1p[0], t('out1_x')); _close(o1p[1], t('out1_e'))
     assert model.take_nan_count() == 0
 
@@ -229,8 +236,11 @@ def test_conditional_split_on_a_real_batch():
     first = _run(model, xh, ex, nl, ctx, nmd, emd)
     _run(model, xh, ex, nl, ctx, nmd, emd, first[0], first[1])
     model.pin_paths()
+    pinned = list(model._last_plans)
     o2 = _run(model, xh, ex, nl, ctx, nmd, emd, first[0], first[1])
+    assert_pinned_call(model, pinned)                             # AFTER each call: it ran on the plan that was pinned
     o1 = _run(model, xh, ex, nl, ctx, nmd, emd)
+    assert_pinned_call(model, pinned)
     _split_ran(model)
     assert model._last_plan.get('pinned')
     assert model.take_nan_count() == 0
@@ -279,7 +289,9 @@ def _settle(model, inp, nm, em, unpin=True):
     o1 = ev(None, None)
     o2 = ev(*o1)
     model.pin_paths()
+    pinned = list(model._last_plans)
     o3 = ev(*o1)
+    assert_pinned_call(model, pinned)                             # AFTER the call: it ran on the plan(s) that were pinned
     _split_ran(model)
     assert model.take_nan_count() == 0
     if unpin:

@@ -158,6 +158,7 @@ def test_split_bf16_pair_update_against_the_default_path_and_float64(cfg_name, n
     first-step and self-conditioned evaluation."""
     import sys, os
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from forms_common import assert_pinned_call
     from helpers import K64, close64, make_config, make_model, oracle_32_64, random_inputs, state_dict_cpu
     from oracle import dgt_oracle as O
     DEV = 'cuda:0'
@@ -184,8 +185,11 @@ def test_split_bf16_pair_update_against_the_default_path_and_float64(cfg_name, n
         run(model, first[0], first[1])
         model.pin_paths()                                      # what a sampler does after its first self-conditioned evaluation
         assert model._last_plan.get('pinned') and (('split_tape' in model._last_plan) == split)
+        pinned = list(model._last_plans)
         o2 = run(model, first[0], first[1])
+        assert_pinned_call(model, pinned)                      # AFTER the call: it ran on the plan that was pinned
         o1 = run(model, None, None)
+        assert_pinned_call(model, pinned)
         assert model.take_nan_count() == 0
         outs[split] = (o1, o2)
         if not split:

@@ -10,6 +10,7 @@ import torch
 from jodo_amd.models import get_model_class
 from oracle import dgt_oracle as O
 
+from forms_common import assert_pinned_call
 from helpers import K64, close64, make_config, make_model, masks, oracle_32_64, random_inputs, state_dict_cpu
 
 pytestmark = pytest.mark.gpu
@@ -54,7 +55,9 @@ def settle(model, inp, nm, em, unpin=True):
     o1 = ev(None, None)
     o2 = ev(*o1)
     inner.pin_paths()
+    pinned = list(inner._last_plans)
     o3 = ev(*o1)
+    assert_pinned_call(inner, pinned)                            # AFTER the call: it ran on the plan(s) that were pinned
     assert inner.take_nan_count() == 0
     if unpin:
         inner.unpin_paths()
