@@ -224,13 +224,10 @@ class JodoTensor(ctypes.Structure):             # jodo_tensor (include/jodo_hip.
 _PACKED_SIZE = {}
 
 
-def pack_weights(cfg_struct, state_dict, device=None):
-    """state_dict (reference key names; values on any device) -> (blob, woff ctypes int64 array, n_woff) through the
-    C packer jodo_dgt_pack_weights[_host].  device=None: blob is a CPU torch tensor; otherwise it is packed straight
-    into a device tensor (one host->device copy of the blob inside the call)."""
+def _marshal(state_dict):
+    """state_dict (values on any device) -> (jodo_tensor array of named fp32 host tensors, the list that keeps their storage alive
+    for as long as the array is used)."""
     import numpy as np
-    import torch
-    L = lib()
     keep, arr = [], (JodoTensor * len(state_dict))()
     for i, (k, v) in enumerate(state_dict.items()):
         t = np.ascontiguousarray(v.detach().float().cpu().numpy())
@@ -238,6 +235,16 @@ def pack_weights(cfg_struct, state_dict, device=None):
         name = k.encode()
         keep.append((t, shp, name))
         arr[i] = JodoTensor(name, t.ctypes.data_as(ctypes.c_void_p), shp, t.ndim)
+    return arr, keep
+
+
+def pack_weights(cfg_struct, state_dict, device=None):
+    """state_dict (reference key names; values on any device) -> (blob, woff ctypes int64 array, n_woff) through the
+    C packer jodo_dgt_pack_weights[_host].  device=None: blob is a CPU torch tensor; otherwise it is packed straight
+    into a device tensor (one host->device copy of the blob inside the call)."""
+    import torch
+    L = lib()
+    arr, keep = _marshal(state_dict)
     # the packed size depends on the configuration only; asking for it runs the whole packer (QR factorisations included), so it
     # is asked once per configuration — a missing or mis-sized tensor is still a named error of the packing call below
     key = bytes(cfg_struct)
@@ -261,116 +268,72 @@ def pack_weights(cfg_struct, state_dict, device=None):
     return blob, woff, n_woff.value
 
 
+def _pack_host(abi, cfg_struct, state_dict, device):
+    """(blob, woff ctypes int64 array, n_woff) through <abi>_packed_size / <abi>_pack_weights_host: the packers that take the
+    configuration alone for the size and pack on the host."""
+    import torch
+    L = lib()
+    arr, keep = _marshal(state_dict)
+    n_floats, n_woff = ctypes.c_size_t(), ctypes.c_int()
+    check(getattr(L, abi + '_packed_size')(ctypes.byref(cfg_struct), ctypes.byref(n_floats), ctypes.byref(n_woff)), abi + '_packed_size')
+    woff = (ctypes.c_int64 * n_woff.value)()
+    blob = torch.empty(n_floats.value, dtype=torch.float32)
+    check(getattr(L, abi + '_pack_weights_host')(ctypes.byref(cfg_struct), arr, len(keep), ctypes.c_void_p(blob.data_ptr()),
+                                                 ctypes.c_size_t(n_floats.value), woff, n_woff.value), abi + '_pack_weights_host')
+    return (blob if device is None else blob.to(device)), woff, n_woff.value
+
+
 def pack_weights_2d(cfg_struct, state_dict, device=None):
     """The 2-D model's state_dict -> (blob, woff ctypes int64 array, n_woff) through jodo_dgt2d_pack_weights_host; device=None keeps
     the blob on the CPU, otherwise it is copied to `device`."""
-    import numpy as np
-    import torch
-    L = lib()
-    keep, arr = [], (JodoTensor * len(state_dict))()
-    for i, (k, v) in enumerate(state_dict.items()):
-        t = np.ascontiguousarray(v.detach().float().cpu().numpy())
-        shp = (ctypes.c_int64 * max(t.ndim, 1))(*t.shape)
-        name = k.encode()
-        keep.append((t, shp, name))
-        arr[i] = JodoTensor(name, t.ctypes.data_as(ctypes.c_void_p), shp, t.ndim)
-    n_floats, n_woff = ctypes.c_size_t(), ctypes.c_int()
-    check(L.jodo_dgt2d_packed_size(ctypes.byref(cfg_struct), ctypes.byref(n_floats), ctypes.byref(n_woff)), 'jodo_dgt2d_packed_size')
-    woff = (ctypes.c_int64 * n_woff.value)()
-    blob = torch.empty(n_floats.value, dtype=torch.float32)
-    check(L.jodo_dgt2d_pack_weights_host(ctypes.byref(cfg_struct), arr, len(keep), ctypes.c_void_p(blob.data_ptr()),
-                                         ctypes.c_size_t(n_floats.value), woff, n_woff.value), 'jodo_dgt2d_pack_weights_host')
-    return (blob if device is None else blob.to(device)), woff, n_woff.value
+    return _pack_host('jodo_dgt2d', cfg_struct, state_dict, device)
 
 
 def pack_weights_egnn(cfg_struct, state_dict, device=None):
     """The property classifier's state_dict -> (blob, woff ctypes int64 array, n_woff) through jodo_egnn_pack_weights_host;
     device=None keeps the blob on the CPU, otherwise it is copied to `device`."""
-    import numpy as np
-    import torch
-    L = lib()
-    keep, arr = [], (JodoTensor * len(state_dict))()
-    for i, (k, v) in enumerate(state_dict.items()):
-        t = np.ascontiguousarray(v.detach().float().cpu().numpy())
-        shp = (ctypes.c_int64 * max(t.ndim, 1))(*t.shape)
-        name = k.encode()
-        keep.append((t, shp, name))
-        arr[i] = JodoTensor(name, t.ctypes.data_as(ctypes.c_void_p), shp, t.ndim)
-    n_floats, n_woff = ctypes.c_size_t(), ctypes.c_int()
-    check(L.jodo_egnn_packed_size(ctypes.byref(cfg_struct), ctypes.byref(n_floats), ctypes.byref(n_woff)), 'jodo_egnn_packed_size')
-    woff = (ctypes.c_int64 * n_woff.value)()
-    blob = torch.empty(n_floats.value, dtype=torch.float32)
-    check(L.jodo_egnn_pack_weights_host(ctypes.byref(cfg_struct), arr, len(keep), ctypes.c_void_p(blob.data_ptr()),
-                                        ctypes.c_size_t(n_floats.value), woff, n_woff.value), 'jodo_egnn_pack_weights_host')
-    return (blob if device is None else blob.to(device)), woff, n_woff.value
+    return _pack_host('jodo_egnn', cfg_struct, state_dict, device)
 
 
 def pack_weights_cdgs(cfg_struct, state_dict, device=None):
     """The CDGS state_dict (plus the caller's 'time_freq') -> (blob, woff ctypes int64 array, n_woff) through
     jodo_cdgs_pack_weights_host; device=None keeps the blob on the CPU, otherwise it is copied to `device`."""
-    import numpy as np
+    return _pack_host('jodo_cdgs', cfg_struct, state_dict, device)
+
+
+def _split_tape(abi, cfg_struct, blob_host, woff, n_woff, device):
+    """(tape uint8 tensor on the CPU or uploaded to `device`, toff ctypes int64 array — byte offsets into the tape indexed like
+    `woff`, -1 for the slots that stay fp32) through <abi>_split_size / <abi>_pack_split_host."""
     import torch
     L = lib()
-    keep, arr = [], (JodoTensor * len(state_dict))()
-    for i, (k, v) in enumerate(state_dict.items()):
-        t = np.ascontiguousarray(v.detach().float().cpu().numpy())
-        shp = (ctypes.c_int64 * max(t.ndim, 1))(*t.shape)
-        name = k.encode()
-        keep.append((t, shp, name))
-        arr[i] = JodoTensor(name, t.ctypes.data_as(ctypes.c_void_p), shp, t.ndim)
-    n_floats, n_woff = ctypes.c_size_t(), ctypes.c_int()
-    check(L.jodo_cdgs_packed_size(ctypes.byref(cfg_struct), ctypes.byref(n_floats), ctypes.byref(n_woff)), 'jodo_cdgs_packed_size')
-    woff = (ctypes.c_int64 * n_woff.value)()
-    blob = torch.empty(n_floats.value, dtype=torch.float32)
-    check(L.jodo_cdgs_pack_weights_host(ctypes.byref(cfg_struct), arr, len(keep), ctypes.c_void_p(blob.data_ptr()),
-                                        ctypes.c_size_t(n_floats.value), woff, n_woff.value), 'jodo_cdgs_pack_weights_host')
-    return (blob if device is None else blob.to(device)), woff, n_woff.value
+    total = ctypes.c_size_t()
+    toff = (ctypes.c_int64 * n_woff)()
+    check(getattr(L, abi + '_split_size')(ctypes.byref(cfg_struct), ctypes.byref(total), toff, n_woff), abi + '_split_size')
+    tape = torch.empty(total.value, dtype=torch.uint8)
+    check(getattr(L, abi + '_pack_split_host')(ctypes.byref(cfg_struct), ctypes.c_void_p(blob_host.data_ptr()), woff, n_woff,
+                                               ctypes.c_void_p(tape.data_ptr()), ctypes.c_size_t(total.value)), abi + '_pack_split_host')
+    return (tape if device is None else tape.to(device)), toff
 
 
 def split_tape_2d(cfg_struct, blob_host, woff, n_woff, device=None):
     """The 2-D model's split-bf16 tape, derived from its packed blob (`blob_host`: the CPU blob of pack_weights_2d with its offset
-    table): (tape uint8 tensor on the CPU or uploaded to `device`, toff ctypes int64 array — byte offsets into the tape indexed like
-    `woff`, -1 for the slots that stay fp32) through jodo_dgt2d_split_size / jodo_dgt2d_pack_split_host."""
-    import torch
-    L = lib()
-    total = ctypes.c_size_t()
-    toff = (ctypes.c_int64 * n_woff)()
-    check(L.jodo_dgt2d_split_size(ctypes.byref(cfg_struct), ctypes.byref(total), toff, n_woff), 'jodo_dgt2d_split_size')
-    tape = torch.empty(total.value, dtype=torch.uint8)
-    check(L.jodo_dgt2d_pack_split_host(ctypes.byref(cfg_struct), ctypes.c_void_p(blob_host.data_ptr()), woff, n_woff,
-                                       ctypes.c_void_p(tape.data_ptr()), ctypes.c_size_t(total.value)), 'jodo_dgt2d_pack_split_host')
-    return (tape if device is None else tape.to(device)), toff
+    table): (tape, toff) as _split_tape returns them, through jodo_dgt2d_split_size / jodo_dgt2d_pack_split_host."""
+    return _split_tape('jodo_dgt2d', cfg_struct, blob_host, woff, n_woff, device)
 
 
 def split_tape_cdgs(cfg_struct, blob_host, woff, n_woff, device=None):
     """The CDGS split-bf16 tape, derived from its packed blob (`blob_host`: the CPU blob of pack_weights_cdgs with its offset table):
-    (tape uint8 tensor on the CPU or uploaded to `device`, toff ctypes int64 array — byte offsets into the tape indexed like `woff`,
-    -1 for the slots that stay fp32) through jodo_cdgs_split_size / jodo_cdgs_pack_split_host."""
-    import torch
-    L = lib()
-    total = ctypes.c_size_t()
-    toff = (ctypes.c_int64 * n_woff)()
-    check(L.jodo_cdgs_split_size(ctypes.byref(cfg_struct), ctypes.byref(total), toff, n_woff), 'jodo_cdgs_split_size')
-    tape = torch.empty(total.value, dtype=torch.uint8)
-    check(L.jodo_cdgs_pack_split_host(ctypes.byref(cfg_struct), ctypes.c_void_p(blob_host.data_ptr()), woff, n_woff,
-                                      ctypes.c_void_p(tape.data_ptr()), ctypes.c_size_t(total.value)), 'jodo_cdgs_pack_split_host')
-    return (tape if device is None else tape.to(device)), toff
+    (tape, toff) as _split_tape returns them, through jodo_cdgs_split_size / jodo_cdgs_pack_split_host."""
+    return _split_tape('jodo_cdgs', cfg_struct, blob_host, woff, n_woff, device)
 
 
 def pack_split_tape(cfg_struct, state_dict, device=None):
     """The static weight tape of the OPT-IN split-bf16 pair update (jodo_dgt_pack_split_host; JODO_OPT_SPLIT_BF16): a uint8 tensor
     (CPU, or uploaded to `device`).  Raises JodoHipError for configurations this tape is not built for (nf not 256 / 384; conditional
     models have a tape of their own, pack_split_cond_tape)."""
-    import numpy as np
     import torch
     L = lib()
-    keep, arr = [], (JodoTensor * len(state_dict))()
-    for i, (k, v) in enumerate(state_dict.items()):
-        t = np.ascontiguousarray(v.detach().float().cpu().numpy())
-        shp = (ctypes.c_int64 * max(t.ndim, 1))(*t.shape)
-        name = k.encode()
-        keep.append((t, shp, name))
-        arr[i] = JodoTensor(name, t.ctypes.data_as(ctypes.c_void_p), shp, t.ndim)
+    arr, keep = _marshal(state_dict)
     total, per_block, node_block, attn_block = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
     check(L.jodo_dgt_split_size(ctypes.byref(cfg_struct), ctypes.byref(total), ctypes.byref(per_block), ctypes.byref(node_block), ctypes.byref(attn_block)),
           'jodo_dgt_split_size')
@@ -384,16 +347,9 @@ def pack_split_cond_tape(cfg_struct, state_dict, device=None):
     """The conditional model's tape of the OPT-IN split-bf16 pair update (jodo_dgt_pack_split_cond_host; cond_DGT_concat at nf 256 under
     JODO_OPT_SPLIT_BF16): per block the edge FFN, the readout, input_lin's [e ; G] columns and coord_mlp.0 in the un-folded kernel's
     consumption order, a uint8 tensor (CPU, or uploaded to `device`).  Raises JodoHipError for unconditional models and nf != 256."""
-    import numpy as np
     import torch
     L = lib()
-    keep, arr = [], (JodoTensor * len(state_dict))()
-    for i, (k, v) in enumerate(state_dict.items()):
-        t = np.ascontiguousarray(v.detach().float().cpu().numpy())
-        shp = (ctypes.c_int64 * max(t.ndim, 1))(*t.shape)
-        name = k.encode()
-        keep.append((t, shp, name))
-        arr[i] = JodoTensor(name, t.ctypes.data_as(ctypes.c_void_p), shp, t.ndim)
+    arr, keep = _marshal(state_dict)
     total, per_block = ctypes.c_size_t(), ctypes.c_size_t()
     check(L.jodo_dgt_split_cond_size(ctypes.byref(cfg_struct), ctypes.byref(total), ctypes.byref(per_block)), 'jodo_dgt_split_cond_size')
     tape = torch.empty(total.value, dtype=torch.uint8)

@@ -16,20 +16,16 @@ refusing grad-enabled calls.
 import ctypes
 import pickle
 
-import numpy as np
 import torch
 from torch import nn
 
 from .. import capi
+from ..models._runtime import HostRuntime, lru_put, mask_counts
 
 
 class _CfgEGNN(ctypes.Structure):               # jodo_egnn_cfg (include/jodo_hip.h)
     _fields_ = [('hidden_nf', ctypes.c_int32), ('n_layers', ctypes.c_int32), ('in_node_nf', ctypes.c_int32), ('attention', ctypes.c_int32),
                 ('node_attr', ctypes.c_int32)]
-
-
-def _drop_packed_after_load(module, incompatible_keys):
-    module.invalidate_packed_weights()
 
 
 class _GCLParams(nn.Module):
@@ -43,8 +39,10 @@ class _GCLParams(nn.Module):
             self.att_mlp = nn.Sequential(nn.Linear(nf, 1), nn.Sigmoid())
 
 
-class EGNN(nn.Module):
+class EGNN(HostRuntime, nn.Module):
     """The reference's EGNN property classifier (HIP)."""
+
+    _engine_bound = 8
 
     def __init__(self, in_node_nf, in_edge_nf, hidden_nf, device='cpu', act_fn=nn.SiLU(), n_layers=4, coords_weight=1.0, attention=False,
                  node_attr=1):
@@ -70,63 +68,27 @@ class EGNN(nn.Module):
         self.node_dec = nn.Sequential(nn.Linear(hidden_nf, hidden_nf), nn.SiLU(), nn.Linear(hidden_nf, hidden_nf))
         self.graph_dec = nn.Sequential(nn.Linear(hidden_nf, hidden_nf), nn.SiLU(), nn.Linear(hidden_nf, 1))
         # ---- runtime state (not part of state_dict) ----
-        self._packed = None           # (version key, device blob, woff ctypes array, n_woff)
-        self._plans = {}              # per (B, N, atom counts): descriptor + workspace
+        self._init_runtime()          # _packed, _plans (here per (B, N, atom counts): descriptor + workspace)
         self.validate_masks = True    # one device pass per call: prefix node_mask, edge_mask = its off-diagonal outer product
         self.max_layers = -1          # tests: stop after this many layers; forward then returns the hidden state [Nn, hidden_nf]
         self.hip_training = False     # opt-in: grad-enabled calls go through the HIP training path (csrc/egnn_train.hip)
-        self.register_load_state_dict_post_hook(_drop_packed_after_load)
         self.to(self.device)
 
-    # -- weights (the contract of models/dgt.py) ---------------------------------------------------
-    def _weights(self, device):
-        key = (str(device),) + tuple(p._version for p in self.parameters()) + tuple(p.data_ptr() for p in self.parameters())
-        if self._packed is None or self._packed[0] != key:
-            host, woff_c, n_woff = capi.pack_weights_egnn(self._cfg_struct, self.state_dict(), None)
-            self._packed = (key, host.to(device), woff_c, n_woff)
-        return self._packed
-
-    def invalidate_packed_weights(self):
-        """Drop the packed kernel weights; the next forward re-packs from the current parameters (needed after in-place `.data`
-        updates that bump no tensor version)."""
-        self._packed = None
+    # -- weights (cache, fingerprint and invalidation: models/_runtime.HostRuntime; _recheck_weights is never called here: the plan
+    # lookup happens per call, and a recheck there would add a launch and a sync to every evaluation batch) -----------------------
+    def _pack(self, device):
+        return capi.pack_weights_egnn(self._cfg_struct, self.state_dict(), None)
 
     def load_state_dict(self, state_dict, strict=True, **kw):
         if state_dict and all(k.startswith('module.') for k in state_dict):      # a checkpoint saved from a DataParallel wrap
             state_dict = type(state_dict)((k[7:], v) for k, v in state_dict.items())
         return super().load_state_dict(state_dict, strict=strict, **kw)
 
-    def _replicate_for_data_parallel(self):
-        raise RuntimeError(
-            "jodo_amd %s cannot be replicated by torch.nn.DataParallel over several devices: its descriptors, workspace and packed "
-            "weights belong to one device.  DataParallel(model, device_ids=[one device]) is supported." % type(self).__name__)
-
     # -- per-batch descriptor and workspace -----------------------------------------------------------
-    def _counts(self, node_mask, edge_mask, B, N):
-        """Atom counts on the host (int32 [B]); with validate_masks the two mask checks ride on the same transfer."""
-        nm = node_mask.reshape(B, N)
-        n_nodes = nm.sum(1).round().to(torch.int32)
-        if self.validate_masks:
-            prefix = torch.arange(N, device=nm.device).unsqueeze(0) < n_nodes.unsqueeze(1)
-            ok = [(prefix.to(nm.dtype) == nm).all()]
-            if edge_mask is not None:
-                em = edge_mask.reshape(B, N, N)
-                want = prefix.unsqueeze(1) & prefix.unsqueeze(2) & (~torch.eye(N, dtype=torch.bool, device=nm.device))
-                ok.append((want.to(em.dtype) == em).all())
-            host = torch.cat([n_nodes, torch.stack(ok).to(torch.int32)]).cpu().numpy()        # counts and both checks in one transfer
-            if not host[B]:
-                raise ValueError("node_mask must be a prefix mask (real atoms first), as the samplers build it")
-            if edge_mask is not None and not host[B + 1]:
-                raise ValueError("edge_mask must be node_mask x node_mask with the diagonal removed (a fully connected molecule)")
-            n_host = np.ascontiguousarray(host[:B], dtype=np.int32)
-        else:
-            n_host = np.ascontiguousarray(n_nodes.cpu().numpy(), dtype=np.int32)
-        return n_host
-
     def _plan(self, node_mask, edge_mask, B, N, device):
-        n_host = self._counts(node_mask, edge_mask, B, N)
+        n_host = mask_counts(node_mask, edge_mask, B, N, self.validate_masks)
         key = (str(device), B, N, n_host.tobytes())
-        plan = self._plans.pop(key, None)
+        plan = self._plans.get(key)
         if plan is None:
             L = capi.lib()
             lay = (ctypes.c_int64 * 8)()
@@ -137,9 +99,7 @@ class EGNN(nn.Module):
                                              ctypes.c_int64(int(lay[0]))), 'jodo_egnn_fill_desc')
             plan = dict(desc=desc_host.to(device), ws=torch.zeros(int(lay[1]), dtype=torch.uint8, device=device), n_nodes=n_host,
                         Nn=int(lay[2]), h_off=int(lay[3]))
-            while len(self._plans) >= 8:                 # bounded cache
-                self._plans.pop(next(iter(self._plans)))
-        self._plans[key] = plan                          # most recently used last
+        lru_put(self._plans, key, plan, 8)               # most recently used last
         return plan
 
     # -- forward -------------------------------------------------------------------------------
@@ -185,23 +145,11 @@ class EGNN(nn.Module):
 
     # -- training path (opt-in: hip_training) ------------------------------------------------------------
     def _train_engine(self, node_mask, edge_mask, B, N, device):
-        """One TrainEngineEGNN (jodo_egnn_train handle + device tables) per set of atom counts, in a bounded cache like `_plans`; all
-        engines of the module share its two workspaces."""
+        """One TrainEngineEGNN (jodo_egnn_train handle + device tables) per set of atom counts, in the module's bounded cache
+        (models/_runtime.HostRuntime._engine_for_counts)."""
         from ..train import TrainEngineEGNN
-        n_host = self._counts(node_mask, edge_mask, B, N)
-        key = (str(device), B, N, n_host.tobytes())
-        cache = self.__dict__.setdefault('_train_engines', {})
-        eng = cache.pop(key, None)
-        if eng is None:
-            named = self.__dict__.get('_train_named')
-            if named is None:
-                named = self.__dict__['_train_named'] = TrainEngineEGNN.named_table([(k, tuple(v.shape)) for k, v in self.named_parameters()])
-            pool = self.__dict__.setdefault('_train_pool', TrainEngineEGNN.new_pool())
-            eng = TrainEngineEGNN(self._cfg_struct, n_host, N, named, device, pool=pool)
-            while len(cache) >= 8:
-                cache.pop(next(iter(cache)))
-        cache[key] = eng                                         # most recently used last
-        return eng
+        n_host = mask_counts(node_mask, edge_mask, B, N, self.validate_masks)
+        return self._engine_for_counts(TrainEngineEGNN, self._cfg_struct, n_host, N, device)
 
     def _forward_train(self, h0, x, node_mask, edge_mask, B, N, dev):
         from ..train import egnn_autograd

@@ -23,13 +23,12 @@ padded the batch to; the kernels reproduce that from the tensors' N.
 import ctypes
 import math
 
-import numpy as np
 import torch
 from torch import nn
 
 from .. import capi
 from . import utils
-from .dgt import _drop_packed_after_load
+from ._runtime import TapeRuntime
 
 MAX_N = 181                                     # JODO_CDGS_MAX_N (include/jodo_hip.h): the GEOM config's max_node
 
@@ -85,7 +84,7 @@ def _conv1x1(cin, cout):
 
 
 @utils.register_model(name='CDGS')
-class CDGS(nn.Module):
+class CDGS(TapeRuntime, nn.Module):
     """Graph noise-prediction model: GINE + edge-gated full attention blocks over random-walk features (HIP)."""
 
     depends_on_padded_width = True    # the dense edge GroupNorm: read by the sampling function's parity shards (jodo_amd/sampling.py)
@@ -130,90 +129,36 @@ class CDGS(nn.Module):
         self.all_modules = nn.ModuleList(mods)
 
         # ---- runtime state (not part of state_dict) ----
-        self._packed = None           # (version key, device blob, woff ctypes array, n_woff)
-        self._tape = None             # (the _packed it was derived from, device tape, toff ctypes array): valid for that _packed only
-        self._plans = {}              # per batch of atom counts: descriptor + workspace, keyed by the mask storage (see _plan)
+        self._init_runtime()          # _packed, _tape, _plans (per batch of atom counts: descriptor + workspace, see _plan)
         self.max_blocks = -1          # tests: stop after this many blocks (the workspace then holds h and e of that block)
         self.last_flags = None        # after a bf16x3 call: the 4 int32 words jodo_cdgs_forward_split wrote ([3] = 1); else None
         self.split_bf16 = False       # the 3-D models' opt-in form; not built for this model (forward raises when set)
         self.bf16x3 = False           # opt-in, read per call: the split-bf16 (three-term) form of the node-row and edge-row GEMMs
                                       # (kc_gemm_s).  Combines with max_blocks.  The training path ignores it.
-        self.register_load_state_dict_post_hook(_drop_packed_after_load)
 
-    # -- weights (same invalidation rules as DGT_concat_2D._weights) ---------------------------------
-    def _tensors(self):
-        return list(self.parameters()) + list(self.buffers())
+    # -- weights (cache, fingerprint, invalidation and the derived tape: _runtime.TapeRuntime) -----------
+    def _key_tensors(self):
+        return list(self.parameters()) + list(self.buffers())       # the GINE `eps` buffers are packed and read like the weights
 
     def _time_freq(self):
         half = self.nf // 2                       # the reference's sinusoid table, fp32 as it computes it
         return torch.exp(torch.arange(half, dtype=torch.float32) * -(math.log(10000) / (half - 1)))
 
-    def _weights(self, device):
-        ts = self._tensors()
-        key = (str(device),) + tuple(p._version for p in ts) + tuple(p.data_ptr() for p in ts)
-        if self._packed is None or self._packed[0] != key:
-            self._tape = None
-            sd = dict(self.state_dict())
-            sd['time_freq'] = self._time_freq()
-            host, woff_c, n_woff = capi.pack_weights_cdgs(self._cfg_struct, sd, None)
-            self._packed = (key, host.to(device), woff_c, n_woff)
-            self._packed_fingerprint = self._fingerprint()
-            if self.bf16x3:                              # the tape lives and dies with the blob it is derived from
-                self._split_tape(device, host)
-        return self._packed
+    def _pack(self, device):
+        sd = dict(self.state_dict())
+        sd['time_freq'] = self._time_freq()
+        return capi.pack_weights_cdgs(self._cfg_struct, sd, None)
 
-    def _split_tape(self, device, blob_host=None):
-        """(device tape, toff) of the split-bf16 form for the current `_packed`: host conversion of the packed blob + one upload, when
-        the blob is re-packed with the switch on or on the first call with the switch on."""
-        packed, t = self._packed, self._tape
-        if t is None or t[0] is not packed:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("bf16x3 was switched on under graph capture for weights packed without it: run one eager call with "
-                                   "bf16x3 = True first")
-            if blob_host is None:
-                blob_host = packed[1].cpu()
-            tape, toff = capi.split_tape_cdgs(self._cfg_struct, blob_host, packed[2], packed[3], device)
-            t = self._tape = (packed, tape, toff)
-        return t[1], t[2]
-
-    def _fingerprint(self):
-        ps = [p.detach() for p in self._tensors()]
-        norms = torch._foreach_norm(ps)
-        w = torch.arange(1, len(norms) + 1, device=norms[0].device, dtype=torch.float64)
-        return float((torch.stack([n.double() for n in norms]) * (1.0 + 1e-3 * w)).sum().item())
-
-    def _recheck_weights(self):
-        if self._packed is not None and self._fingerprint() != getattr(self, '_packed_fingerprint', None):
-            self._packed = None
-            self._tape = None
-
-    def invalidate_packed_weights(self):
-        """Drop the packed kernel weights; the next forward re-packs from the current parameters (needed after in-place `.data`
-        updates that bump no tensor version, e.g. the reference's ExponentialMovingAverage.copy_to / restore)."""
-        self._packed = None
-        self._tape = None
+    def _pack_tape(self, blob_host, woff_c, n_woff, device):
+        return capi.split_tape_cdgs(self._cfg_struct, blob_host, woff_c, n_woff, device)
 
     # -- per-batch descriptor and workspace -----------------------------------------------------------
     def _plan(self, node_mask, edge_mask, device, validate=True):
-        key = (node_mask.data_ptr(), tuple(node_mask.shape), tuple(node_mask.stride()), str(node_mask.device))
-        plan = self._plans.get(key)
-        if plan is not None and plan['mask_version'] == node_mask._version:
-            return plan
-        self._recheck_weights()                          # new batch (= new sampling round): catch `.data` weight updates
-        B, N = node_mask.shape[0], node_mask.shape[1]
-        if N > MAX_N:
-            raise NotImplementedError("CDGS: padded width N = %d above the limit of %d atoms" % (N, MAX_N))
-        nm = node_mask.reshape(B, N)
-        n_nodes = nm.sum(1).round().to(torch.int32)
-        if validate:
-            prefix = (torch.arange(N, device=nm.device).unsqueeze(0) < n_nodes.unsqueeze(1)).to(nm.dtype)
-            if not torch.equal(prefix, nm):
-                raise ValueError("node_mask must be a prefix mask (real atoms first), as the samplers build it")
-            em = edge_mask.reshape(B, N, N)
-            want = prefix.unsqueeze(1) * prefix.unsqueeze(2) * (~torch.eye(N, dtype=torch.bool, device=nm.device))
-            if not torch.equal(want.to(em.dtype), em):
-                raise ValueError("edge_mask must be node_mask x node_mask with the diagonal removed")
-        n_host = np.ascontiguousarray(n_nodes.cpu().numpy(), dtype=np.int32)     # one sync per new batch
+        if node_mask.shape[1] > MAX_N:
+            raise NotImplementedError("CDGS: padded width N = %d above the limit of %d atoms" % (node_mask.shape[1], MAX_N))
+        return self._cached_plan(node_mask, edge_mask, validate, lambda n_host, B, N: self._build_plan(n_host, B, N, device))
+
+    def _build_plan(self, n_host, B, N, device):
         L = capi.lib()
         lay = (ctypes.c_int64 * 8)()
         n_ptr = n_host.ctypes.data_as(ctypes.c_void_p)
@@ -221,20 +166,9 @@ class CDGS(nn.Module):
         desc_host = torch.empty(int(lay[0]), dtype=torch.int32)
         capi.check(L.jodo_cdgs_fill_desc(ctypes.byref(self._cfg_struct), B, N, n_ptr, ctypes.c_void_p(desc_host.data_ptr()),
                                          ctypes.c_int64(int(lay[0]))), 'jodo_cdgs_fill_desc')
-        plan = dict(desc=desc_host.to(device), ws=torch.zeros(int(lay[1]), dtype=torch.uint8, device=device),
+        return dict(desc=desc_host.to(device), ws=torch.zeros(int(lay[1]), dtype=torch.uint8, device=device),
                     flags=torch.zeros(4, dtype=torch.int32, device=device), n_nodes=n_host, B=B, N=N,
-                    Nn=int(lay[2]), rows=int(lay[3]), h_off=int(lay[4]), e_off=int(lay[5]), code_off=int(lay[6]), land_off=int(lay[7]),
-                    mask=node_mask, mask_version=node_mask._version)
-        self._plans.pop(key, None)
-        if len(self._plans) >= 8:                        # bounded cache
-            self._plans.pop(next(iter(self._plans)))
-        self._plans[key] = plan
-        return plan
-
-    def _replicate_for_data_parallel(self):
-        raise RuntimeError(
-            "jodo_amd %s cannot be replicated by torch.nn.DataParallel over several devices: its descriptors, workspace and packed "
-            "weights belong to one device.  DataParallel(model, device_ids=[one device]) is supported." % type(self).__name__)
+                    Nn=int(lay[2]), rows=int(lay[3]), h_off=int(lay[4]), e_off=int(lay[5]), code_off=int(lay[6]), land_off=int(lay[7]))
 
     # -- forward -------------------------------------------------------------------------------
     def forward(self, t, x, node_mask, edge_mask, context=None, *args, **kwargs):
@@ -282,54 +216,16 @@ class CDGS(nn.Module):
 
     # -- training path (opt-in: hip_training) ------------------------------------------------------------
     def _train_engine(self, node_mask, edge_mask, device):
-        """One TrainEngineCDGS (jodo_cdgs_train handle + device table) per batch of atom counts and padded width, keyed by the counts
-        themselves like DGT_concat_2D._train_engine; all engines of the module share its two activation workspaces."""
+        """One TrainEngineCDGS (jodo_cdgs_train handle + device table) per batch of atom counts and padded width, in the module's
+        bounded cache (_runtime.HostRuntime._engine_for_masks); an engine taken up again re-checks the device's free memory."""
         from ..train import TrainEngineCDGS
-        B, N = node_mask.shape[0], node_mask.shape[1]
-        last = self.__dict__.get('_train_last')
-        if (last is not None and last[0] is node_mask and last[1] == node_mask._version and last[2] is edge_mask
-                and last[3] == edge_mask._version):
-            return last[4]
-        hint = getattr(node_mask, '_jodo_counts', None)          # counts the loss already has on the host (losses.process_batch_2D)
-        if hint is not None and len(hint) == B:
-            n_host = np.ascontiguousarray(hint, dtype=np.int32)
-        else:
-            nm = node_mask.reshape(B, N)
-            n_nodes = nm.sum(1).round().to(torch.int32)
-            prefix = (torch.arange(N, device=nm.device).unsqueeze(0) < n_nodes.unsqueeze(1))
-            em = edge_mask.reshape(B, N, N)
-            want = prefix.unsqueeze(1) & prefix.unsqueeze(2) & (~torch.eye(N, dtype=torch.bool, device=nm.device))
-            ok = torch.stack([(prefix.to(nm.dtype) == nm).all(), (want.to(em.dtype) == em).all()]).to(torch.int32)
-            host = torch.cat([n_nodes, ok]).cpu().numpy()        # counts and both mask checks in one transfer
-            if not host[B]:
-                raise ValueError("node_mask must be a prefix mask (real atoms first), as the samplers build it")
-            if not host[B + 1]:
-                raise ValueError("edge_mask must be node_mask x node_mask with the diagonal removed")
-            n_host = np.ascontiguousarray(host[:B])
-        key = (str(device), N) + tuple(int(v) for v in n_host)
-        cache = self.__dict__.setdefault('_train_engines', {})
-        eng = cache.pop(key, None)
-        if eng is None:
-            named = self.__dict__.get('_train_named')
-            if named is None:
-                named = self.__dict__['_train_named'] = TrainEngineCDGS.named_table([(k, tuple(v.shape)) for k, v in self.state_dict().items()])
-            pool = self.__dict__.setdefault('_train_pool', TrainEngineCDGS.new_pool())
-            eng = TrainEngineCDGS(self._cfg_struct, n_host, N, named, device, pool=pool)
-            while len(cache) >= 16:
-                cache.pop(next(iter(cache)))
-        else:
-            eng.check_free()
-        cache[key] = eng                                         # most recently used last
-        self.__dict__['_train_last'] = (node_mask, node_mask._version, edge_mask, edge_mask._version, eng)
-        return eng
+        return self._engine_for_masks(TrainEngineCDGS, self._cfg_struct, node_mask, edge_mask, device)
 
     def _forward_train(self, t, x, edge_x, node_mask, edge_mask, wants_grad):
         from ..train import cdgs_autograd
         f32 = lambda v: v.detach().to(torch.float32).contiguous()
         eng = self._train_engine(node_mask, edge_mask, x.device)
-        p = float(self.dropout_p) if self.training else 0.0
-        # dropout masks: counter-based, keyed by a seed drawn from torch's generator (so torch.manual_seed reproduces a step)
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if p > 0 else 0
+        p, seed = self._dropout_draw()
         freq = self.__dict__.get('_train_freq')
         if freq is None or freq.device != x.device:
             freq = self.__dict__['_train_freq'] = self._time_freq().to(x.device)

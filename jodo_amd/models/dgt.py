@@ -18,13 +18,13 @@ on a non-GPU tensor, with gradients enabled, or with an unsupported config, forw
 """
 import ctypes
 
-import numpy as np
 import torch
 from torch import nn
 
 from .. import capi
 from .dims import ModelDims
 from . import utils
+from ._runtime import HostRuntime
 
 
 # ---------------------------------------------------------------------------------------------
@@ -99,17 +99,13 @@ def _mlp3(i, h, m, o):
     return nn.Sequential(nn.Linear(i, h), nn.SiLU(), nn.Linear(h, m), nn.SiLU(), nn.Linear(m, o))
 
 
-def _drop_packed_after_load(module, incompatible_keys):
-    """load_state_dict post hook (module-level so that the module stays picklable)."""
-    module.invalidate_packed_weights()
-
-
 _UNSUPPORTED = (('dist_gbf', True), ('cond_time', True), ('pred_data', True), ('gbf_name', 'CondGaussianLayer'),
                 ('CoM', True), ('softmax_inf', True))
 
 
-class _DGTBase(nn.Module):
+class _DGTBase(HostRuntime, nn.Module):
     conditional = False
+    _derived = ('_split_tape',)       # (pack generation, device uint8 tensor): the split form's static weight tape
 
     def __init__(self, config):
         super().__init__()
@@ -159,13 +155,11 @@ class _DGTBase(nn.Module):
             self.cond_lin = nn.Linear(cond_ch * D, T)
 
         # ---- runtime state (not part of state_dict) ----
-        self._packed = None           # (version_key, blob_dev, woff_host ctypes array)
+        self._init_runtime()          # _packed, _plans (plan cache keyed by the mask storage, see _plan), _split_tape
         self._pack_gen = 0            # pack generation: +1 on every re-pack of the blob (the split tape and the plans' tapes key on it)
-        self._plans = {}              # plan cache keyed by the mask storage (address, shape, version), see _plan
         self._splits = {}             # sub-batch splits of n_streams > 1, keyed likewise (node and edge mask storage, k), see _split_of
         self.n_streams = 1            # > 1: sub-batches evaluated concurrently on that many HIP streams (_forward_split)
         self._cfg_struct = None
-        self.register_load_state_dict_post_hook(_drop_packed_after_load)
         self.last_flags = None        # device int32[8] of the last call (NaN guard etc.)
         self.warn_nan = True
         # OPT-IN (default off): under pinned paths (pin_paths: what the samplers do after a round's first self-conditioned evaluation)
@@ -175,7 +169,6 @@ class _DGTBase(nn.Module):
         # shared noise level.  The conditional model at nf 256: the un-folded pair update (csrc/dgt_kernels_split_cond.h; per-molecule
         # noise levels allowed).  Ignored elsewhere (nf 128, asymmetric inputs).  The default path and every headline number stay exact fp32.
         self.split_bf16 = False       # True: pair update + node kernel; 'attention': also the attention kernel (experiments: measured slower)
-        self._split_tape = None       # (pack generation, device uint8 tensor): the split form's static weight tape
 
     # -- C structs ---------------------------------------------------------------------------
     class _Cfg(ctypes.Structure):
@@ -191,60 +184,23 @@ class _DGTBase(nn.Module):
                                          self.edge_th, 1 if d.wide else 0)
         return self._cfg_struct
 
-    # -- weights -----------------------------------------------------------------------------
-    def _weights(self, device):
-        # cheap key checked on every call: tensor versions (bumped by optimizer steps, load_state_dict, p.copy_) and
-        # storage addresses (model.to(...)).  In-place writes through `.data` (the reference's EMA copy_to / restore,
-        # models/ema.py:44-66) bump neither: a content fingerprint is compared whenever a new plan is built (once per
-        # sampling round, _plan below), and invalidate_packed_weights() forces a re-pack explicitly.
-        key = (str(device),) + tuple(p._version for p in self.parameters()) + tuple(p.data_ptr() for p in self.parameters())
-        if self._packed is None or self._packed[0] != key:
-            # C-side packer (csrc/dgt_pack.cpp, jodo_dgt_pack_weights): the state_dict goes through the C ABI as named
-            # fp32 tensors; tests/py_packing_model.py is an independent Python packer kept for tests (blob equality)
-            blob_dev, woff_c, n_woff = capi.pack_weights(self._cfg(), self.state_dict(), device)
-            # a `.data` write re-packs under the SAME key (versions and addresses unchanged): what follows the blob — the split tape and
-            # the tape handed to each pinned plan — compares this generation, not the key
-            self._pack_gen += 1
-            self._packed = (key, blob_dev, woff_c, n_woff)
-            self._packed_fingerprint = self._fingerprint()
-        return self._packed
+    # -- weights (cache, fingerprint and invalidation: _runtime.HostRuntime) ---------------------------
+    def _pack(self, device):
+        # C-side packer (csrc/dgt_pack.cpp, jodo_dgt_pack_weights): the state_dict goes through the C ABI as named
+        # fp32 tensors; tests/py_packing_model.py is an independent Python packer kept for tests (blob equality)
+        return capi.pack_weights(self._cfg(), self.state_dict(), device)
 
-    def _fingerprint(self):
-        """Content fingerprint of all parameters: one fused norm launch + one reduction, one host sync."""
-        ps = [p.detach() for p in self.parameters()]
-        norms = torch._foreach_norm(ps)
-        w = torch.arange(1, len(norms) + 1, device=norms[0].device, dtype=torch.float64)
-        return float((torch.stack([n.double() for n in norms]) * (1.0 + 1e-3 * w)).sum().item())
-
-    def _recheck_weights(self):
-        if self._packed is not None and self._fingerprint() != getattr(self, '_packed_fingerprint', None):
-            self._packed = None
-            self._split_tape = None
+    def _repacked(self, device, blob):
+        # a `.data` write re-packs under the SAME key (versions and addresses unchanged): what follows the blob — the split tape and
+        # the tape handed to each pinned plan — compares this generation, not the key
+        self._pack_gen += 1
 
     # -- plans ---------------------------------------------------------------------------------
     def _plan(self, node_mask, edge_mask, device, validate=True):
-        # keyed by the mask's storage address, shape and version counter; the entry keeps the mask alive, so its storage cannot be
-        # recycled for a different mask while the plan is cached (data_ptr alone would not be a safe key).  Not by tensor identity:
-        # torch.nn.DataParallel — how the reference's create_model wraps the model (models/utils.py:27) — scatters every call's
-        # arguments, and with one device that hands the module a fresh VIEW of the same mask on every call (same storage, same
-        # version counter); identity would rebuild the plan on each of a round's 1000 calls.
-        key = (node_mask.data_ptr(), tuple(node_mask.shape), tuple(node_mask.stride()), str(node_mask.device))
-        plan = self._plans.get(key)
-        if plan is not None and plan['mask_version'] == node_mask._version:
-            return plan
-        self._recheck_weights()                          # new batch (= new sampling round): catch `.data` weight updates
-        B, N = node_mask.shape[0], node_mask.shape[1]
-        nm = node_mask.reshape(B, N)
-        n_nodes = nm.sum(1).round().to(torch.int32)
-        if validate:
-            prefix = (torch.arange(N, device=nm.device).unsqueeze(0) < n_nodes.unsqueeze(1)).to(nm.dtype)
-            if not torch.equal(prefix, nm):
-                raise ValueError("node_mask must be a prefix mask (real atoms first), as the samplers build it")
-            em = edge_mask.reshape(B, N, N)
-            want = prefix.unsqueeze(1) * prefix.unsqueeze(2) * (~torch.eye(N, dtype=torch.bool, device=nm.device))
-            if not torch.equal(want.to(em.dtype), em):
-                raise ValueError("edge_mask must be node_mask x node_mask with the diagonal removed")
-        n_host = np.ascontiguousarray(n_nodes.cpu().numpy(), dtype=np.int32)     # one sync per new batch
+        destroy = lambda plan: capi.lib().jodo_plan_destroy(plan['handle'])
+        return self._cached_plan(node_mask, edge_mask, validate, lambda n_host, B, N: self._build_plan(n_host, B, N, device), destroy)
+
+    def _build_plan(self, n_host, B, N, device):
         L = capi.lib()
         handle = ctypes.c_void_p()
         capi.check(L.jodo_plan_create(ctypes.byref(self._cfg()), B, N, n_host.ctypes.data_as(ctypes.c_void_p),
@@ -263,26 +219,7 @@ class _DGTBase(nn.Module):
             capi.check(L.jodo_plan_set_option(handle, int(opt), int(val)), 'jodo_plan_set_option')
         capi.check(L.jodo_plan_upload(handle, capi.ptr(desc), capi.current_stream_ptr()), 'jodo_plan_upload')
         torch.cuda.current_stream().synchronize()        # host staging buffer lives in the plan; be safe
-        plan = dict(handle=handle, desc=desc, ws=ws, n_nodes=n_host, B=B, N=N, mask=node_mask,
-                    mask_version=node_mask._version, flags=torch.zeros(8, dtype=torch.int32, device=device))
-        stale = self._plans.pop(key, None)
-        if stale is not None:
-            L.jodo_plan_destroy(stale['handle'])
-        if len(self._plans) >= 8:                        # bounded cache
-            old = self._plans.pop(next(iter(self._plans)))
-            L.jodo_plan_destroy(old['handle'])
-        self._plans[key] = plan
-        return plan
-
-    def _replicate_for_data_parallel(self):
-        """torch.nn.DataParallel with more than one device (the reference's create_model on a multi-GPU node, models/utils.py:27)
-        shallow-copies the module into worker threads every forward: the copies would share this module's plan cache, ctypes
-        handles and the packed weight blob on cuda:0.  Multi-GPU here is one process per GPU with the batch sharded by the sampler."""
-        raise RuntimeError(
-            "jodo_amd %s cannot be replicated by torch.nn.DataParallel over several devices: its plans, workspace and packed weights "
-            "belong to one device.  Run one process per GPU (python -m torch.distributed.run --nproc-per-node N ...) and pass "
-            "shard=(rank, world) to jodo_amd.sampling.get_sampling_fn (jodo_amd/dist.py, INTEGRATION.md section 3); "
-            "DataParallel(model, device_ids=[one device]) is supported." % type(self).__name__)
+        return dict(handle=handle, desc=desc, ws=ws, n_nodes=n_host, B=B, N=N, flags=torch.zeros(8, dtype=torch.int32, device=device))
 
     def __del__(self):
         try:
@@ -335,67 +272,11 @@ class _DGTBase(nn.Module):
 
     # -- training path ---------------------------------------------------------------------------
     def _train_engine(self, node_mask, edge_mask, device):
-        """One TrainEngine (jodo_train handle + device tables) per batch of atom counts, keyed by the counts themselves.  A shuffling
-        loader practically never repeats a key, so a real training step CREATES its engine (host tables of ~4 R ints, one upload):
-        tools/train_bench.py times that case (`fresh_batches`) as its headline; the 16-entry cache only serves repeated evaluation of
-        one batch (tests, the self-conditioning double forward of a step).  All engines of a module share its activation workspaces
-        (TrainEngine.new_pool: two, so that a second grad-enabled forward may run before the first one's backward)."""
+        """One TrainEngine (jodo_train handle + device tables) per batch of atom counts, in the module's bounded cache
+        (_runtime.HostRuntime._engine_for_masks).  model.validate_masks = False skips the mask checks."""
         from ..train import TrainEngine
-        B, N = node_mask.shape[0], node_mask.shape[1]
-        # the same mask tensors as the previous call (the two forwards of a self-conditioned training step): the same engine, no host work
-        last = self.__dict__.get('_train_last')
-        if (last is not None and last[0] is node_mask and last[1] == node_mask._version and last[2] is edge_mask and last[3] == edge_mask._version
-                and last[4] == tuple(sorted((getattr(self, 'train_options', None) or {}).items()))):
-            return last[5]
-        eng = self._train_engine_lookup(node_mask, edge_mask, device, B, N)
-        self.__dict__['_train_last'] = (node_mask, node_mask._version, edge_mask, edge_mask._version, tuple(sorted((getattr(self, 'train_options', None) or {}).items())), eng)
-        return eng
-
-    def _train_engine_lookup(self, node_mask, edge_mask, device, B, N):
-        from ..train import TrainEngine
-        # atom counts that the caller already has on the host (process_edge_batch, jodo_amd/losses.py: the loader's batch is a CPU
-        # dict, losses.py:470-476 of the reference, so counts and the mask check cost nothing there): no device round trip, and a
-        # training step then runs without any host synchronisation
-        hint = getattr(node_mask, '_jodo_counts', None)
-        if hint is not None and len(hint) == B:
-            return self._train_engine_for(np.ascontiguousarray(hint, dtype=np.int32), N, device)
-        nm = node_mask.reshape(B, N)
-        n_nodes = nm.sum(1).round().to(torch.int32)
-        # mask validation and the atom counts reach the host in ONE transfer (one stream sync per new batch; round 4 paid three:
-        # two torch.equal and the counts).  model.validate_masks = False drops the comparison kernels as well (a loader that is
-        # known to build prefix masks, like the samplers' build_masks).
-        if getattr(self, 'validate_masks', True):
-            prefix = (torch.arange(N, device=nm.device).unsqueeze(0) < n_nodes.unsqueeze(1))
-            em = edge_mask.reshape(B, N, N)
-            want = prefix.unsqueeze(1) & prefix.unsqueeze(2) & (~torch.eye(N, dtype=torch.bool, device=nm.device))
-            ok = torch.stack([(prefix.to(nm.dtype) == nm).all(), (want.to(em.dtype) == em).all()]).to(torch.int32)
-            host = torch.cat([n_nodes, ok]).cpu().numpy()
-            if not host[B]:
-                raise ValueError("node_mask must be a prefix mask (real atoms first)")
-            if not host[B + 1]:
-                raise ValueError("edge_mask must be node_mask x node_mask with the diagonal removed")
-            n_host = np.ascontiguousarray(host[:B])
-        else:
-            n_host = n_nodes.cpu().numpy()
-        return self._train_engine_for(n_host, N, device)
-
-    def _train_engine_for(self, n_host, N, device):
-        from ..train import TrainEngine
-        opts = dict(getattr(self, 'train_options', None) or {})        # {jodo_train_set_option: value}, e.g. {0: 0}: op-by-op forward (tests)
-        key = (str(device), N, tuple(sorted(opts.items()))) + tuple(int(v) for v in n_host)
-        cache = self.__dict__.setdefault('_train_engines', {})
-        eng = cache.pop(key, None)
-        if eng is None:
-            # (the 351-entry name / shape table of the state_dict is built once per module, not once per batch)
-            named = self.__dict__.get('_train_named')
-            if named is None:
-                named = self.__dict__['_train_named'] = TrainEngine.named_table([(k, tuple(v.shape)) for k, v in self.state_dict().items()])
-            pool = self.__dict__.setdefault('_train_pool', TrainEngine.new_pool())     # the activation workspace(s) of this module
-            eng = TrainEngine(self._cfg(), n_host, N, named, device, pool=pool, options=opts)
-            while len(cache) >= 16:                             # handles are small (index tables); the workspace is shared
-                cache.pop(next(iter(cache)))
-        cache[key] = eng                                        # most recently used last
-        return eng
+        opts = tuple(sorted((getattr(self, 'train_options', None) or {}).items()))   # {jodo_train_set_option: value}, e.g. {0: 0}: op-by-op forward (tests)
+        return self._engine_for_masks(TrainEngine, self._cfg(), node_mask, edge_mask, device, opts, getattr(self, 'validate_masks', True))
 
     def _forward_train(self, xh, edge_x, cond_x, cond_edge_x, noise_level, context, node_mask, edge_mask, wants_grad):
         from ..train import dgt_autograd
@@ -405,9 +286,7 @@ class _DGTBase(nn.Module):
             raise ValueError("shape mismatch: xh %s edge_x %s" % (tuple(xh.shape), tuple(edge_x.shape)))
         f32 = lambda x: None if x is None else x.detach().to(torch.float32).contiguous()
         eng = self._train_engine(node_mask, edge_mask, xh.device)
-        p = float(self.dropout_p) if self.training else 0.0
-        # dropout masks: counter-based, keyed by a seed drawn from torch's generator (so torch.manual_seed reproduces a step)
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if p > 0 else 0
+        p, seed = self._dropout_draw()
         ctx_ = f32(context) if self.conditional else None
         # parameters in state_dict order = the order the engine was created with (parameters() of this tree, no buffers)
         params = list(self.parameters())
@@ -602,13 +481,6 @@ class _DGTBase(nn.Module):
             capi.check(capi.lib().jodo_plan_work(p['handle'], int(f[2]), int(not f[4]), w), 'jodo_plan_work')
             tot = [a + b for a, b in zip(tot, w)]
         return tot
-
-    def invalidate_packed_weights(self):
-        """Drop the packed kernel weights; the next forward re-packs from the current parameters.  Needed after
-        in-place updates that do not bump tensor versions (`param.data.copy_(...)`, e.g. the reference's
-        ExponentialMovingAverage.copy_to / restore, models/ema.py:44-66).  The split tape goes with it."""
-        self._packed = None
-        self._split_tape = None
 
     def nan_guard_fired(self):
         """Lazy read of the device NaN-guard flag of the last call (the reference prints a warning and

@@ -22,13 +22,13 @@ gradient; a default module keeps refusing grad-enabled calls ("inference only").
 """
 import ctypes
 
-import numpy as np
 import torch
 from torch import nn
 
 from .. import capi
 from . import utils
-from .dgt import _SinusoidParams, _mlp3, _time_seq, _AttnParams, _drop_packed_after_load
+from ._runtime import TapeRuntime
+from .dgt import _SinusoidParams, _mlp3, _time_seq, _AttnParams
 
 # (key, the one supported value) — the settings of configs/vpsde_zinc_2d_jodo.py and vpsde_moses_2d_jodo.py
 _SUPPORTED_2D = (('nf', 256), ('n_heads', 16), ('n_extra_heads', 1), ('mlp_ratio', 2), ('n_layers', 8), ('cond_time', True),
@@ -57,7 +57,7 @@ class _Cfg2D(ctypes.Structure):                 # jodo_cfg2d (include/jodo_hip.h
 
 
 @utils.register_model(name='DGT_concat_2D')
-class DGT_concat_2D(nn.Module):
+class DGT_concat_2D(TapeRuntime, nn.Module):
     """Diffusion Graph Transformer with self-conditioning for 2-D graphs (HIP)."""
 
     def __init__(self, config):
@@ -98,9 +98,7 @@ class DGT_concat_2D(nn.Module):
         self.time_mlp = nn.Sequential(_SinusoidParams(16), nn.Linear(17, T), nn.GELU(), nn.Linear(T, T))
 
         # ---- runtime state (not part of state_dict) ----
-        self._packed = None           # (version key, device blob, woff ctypes array, n_woff)
-        self._tape = None             # (the _packed it was derived from, device tape, toff ctypes array): valid for that _packed only
-        self._plans = {}              # per batch of atom counts: descriptor + workspace, keyed by the mask storage (see _plan)
+        self._init_runtime()          # _packed, _tape, _plans (per batch of atom counts: descriptor + workspace, see _plan)
         self.split_bf16 = False       # the 3-D models' opt-in form; not built for this model (forward raises when set)
         self.force_directed = False   # tests: always the directed fallback
         self.max_blocks = -1          # tests: stop after this many blocks (the workspace then holds h and e of that block)
@@ -111,71 +109,19 @@ class DGT_concat_2D(nn.Module):
         self.bf16x3 = False           # opt-in, read per call: the split-bf16 (three-term) form of the node GEMMs and the pair update
                                       # (k2d_gemm_s, k2d_pair_s); last_flags[3] tells which form ran (1 = split, 0 = exact fp32).
                                       # Combines with pair_attention / force_directed / max_blocks.  The training path ignores it.
-        self.register_load_state_dict_post_hook(_drop_packed_after_load)
 
-    # -- weights (same invalidation rules as _DGTBase._weights) ------------------------------------
-    def _weights(self, device):
-        key = (str(device),) + tuple(p._version for p in self.parameters()) + tuple(p.data_ptr() for p in self.parameters())
-        if self._packed is None or self._packed[0] != key:
-            self._tape = None
-            host, woff_c, n_woff = capi.pack_weights_2d(self._cfg_struct, self.state_dict(), None)
-            self._packed = (key, host.to(device), woff_c, n_woff)
-            self._packed_fingerprint = self._fingerprint()
-            if self.bf16x3:                              # the tape lives and dies with the blob it is derived from
-                self._split_tape(device, host)
-        return self._packed
+    # -- weights (cache, fingerprint, invalidation and the derived tape: _runtime.TapeRuntime) -----------
+    def _pack(self, device):
+        return capi.pack_weights_2d(self._cfg_struct, self.state_dict(), None)
 
-    def _split_tape(self, device, blob_host=None):
-        """(device tape, toff) of the split-bf16 form for the current `_packed`: host conversion of the packed blob + one upload, when
-        the blob is re-packed with the switch on or on the first call with the switch on."""
-        packed, t = self._packed, self._tape
-        if t is None or t[0] is not packed:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("bf16x3 was switched on under graph capture for weights packed without it: run one eager call with "
-                                   "bf16x3 = True first")
-            if blob_host is None:
-                blob_host = packed[1].cpu()
-            tape, toff = capi.split_tape_2d(self._cfg_struct, blob_host, packed[2], packed[3], device)
-            t = self._tape = (packed, tape, toff)
-        return t[1], t[2]
-
-    def _fingerprint(self):
-        ps = [p.detach() for p in self.parameters()]
-        norms = torch._foreach_norm(ps)
-        w = torch.arange(1, len(norms) + 1, device=norms[0].device, dtype=torch.float64)
-        return float((torch.stack([n.double() for n in norms]) * (1.0 + 1e-3 * w)).sum().item())
-
-    def _recheck_weights(self):
-        if self._packed is not None and self._fingerprint() != getattr(self, '_packed_fingerprint', None):
-            self._packed = None
-
-    def invalidate_packed_weights(self):
-        """Drop the packed kernel weights; the next forward re-packs from the current parameters (needed after in-place `.data`
-        updates that bump no tensor version, e.g. the reference's ExponentialMovingAverage.copy_to / restore)."""
-        self._packed = None
-        self._tape = None
+    def _pack_tape(self, blob_host, woff_c, n_woff, device):
+        return capi.split_tape_2d(self._cfg_struct, blob_host, woff_c, n_woff, device)
 
     # -- per-batch descriptor and workspace -----------------------------------------------------------
     def _plan(self, node_mask, edge_mask, device, validate=True):
-        # keyed by the mask's storage (address, shape, stride, device) + version counter like _DGTBase._plan: the single-device
-        # DataParallel wrap hands over a fresh view of the same mask on every call
-        key = (node_mask.data_ptr(), tuple(node_mask.shape), tuple(node_mask.stride()), str(node_mask.device))
-        plan = self._plans.get(key)
-        if plan is not None and plan['mask_version'] == node_mask._version:
-            return plan
-        self._recheck_weights()                          # new batch (= new sampling round): catch `.data` weight updates
-        B, N = node_mask.shape[0], node_mask.shape[1]
-        nm = node_mask.reshape(B, N)
-        n_nodes = nm.sum(1).round().to(torch.int32)
-        if validate:
-            prefix = (torch.arange(N, device=nm.device).unsqueeze(0) < n_nodes.unsqueeze(1)).to(nm.dtype)
-            if not torch.equal(prefix, nm):
-                raise ValueError("node_mask must be a prefix mask (real atoms first), as the samplers build it")
-            em = edge_mask.reshape(B, N, N)
-            want = prefix.unsqueeze(1) * prefix.unsqueeze(2) * (~torch.eye(N, dtype=torch.bool, device=nm.device))
-            if not torch.equal(want.to(em.dtype), em):
-                raise ValueError("edge_mask must be node_mask x node_mask with the diagonal removed")
-        n_host = np.ascontiguousarray(n_nodes.cpu().numpy(), dtype=np.int32)     # one sync per new batch
+        return self._cached_plan(node_mask, edge_mask, validate, lambda n_host, B, N: self._build_plan(n_host, B, N, device))
+
+    def _build_plan(self, n_host, B, N, device):
         L = capi.lib()
         lay = (ctypes.c_int64 * 8)()
         n_ptr = n_host.ctypes.data_as(ctypes.c_void_p)
@@ -184,12 +130,8 @@ class DGT_concat_2D(nn.Module):
         capi.check(L.jodo_dgt2d_fill_desc(ctypes.byref(self._cfg_struct), B, N, n_ptr, ctypes.c_void_p(desc_host.data_ptr()),
                                           ctypes.c_int64(int(lay[0]))), 'jodo_dgt2d_fill_desc')
         plan = dict(desc=desc_host.to(device), ws=torch.zeros(int(lay[1]), dtype=torch.uint8, device=device), n_nodes=n_host, B=B, N=N,
-                    Nn=int(lay[2]), rows=int(lay[3]), h_off=int(lay[4]), e_off=int(lay[5]), pairs=int(lay[6]), mask=node_mask,
-                    mask_version=node_mask._version, flags=torch.zeros(8, dtype=torch.int32, device=device))
-        self._plans.pop(key, None)
-        if len(self._plans) >= 8:                        # bounded cache
-            self._plans.pop(next(iter(self._plans)))
-        self._plans[key] = plan
+                    Nn=int(lay[2]), rows=int(lay[3]), h_off=int(lay[4]), e_off=int(lay[5]), pairs=int(lay[6]),
+                    flags=torch.zeros(8, dtype=torch.int32, device=device))
         if self.pair_attention:
             self._pair_desc(plan, device)
         return plan
@@ -211,11 +153,6 @@ class DGT_concat_2D(nn.Module):
             desc = plan['pair_desc'] = host.to(device)
             plan['pair_groups'] = int(lay[1])
         return desc
-
-    def _replicate_for_data_parallel(self):
-        raise RuntimeError(
-            "jodo_amd %s cannot be replicated by torch.nn.DataParallel over several devices: its descriptors, workspace and packed "
-            "weights belong to one device.  DataParallel(model, device_ids=[one device]) is supported." % type(self).__name__)
 
     # -- forward -------------------------------------------------------------------------------
     def forward(self, t, xh, node_mask, edge_mask, context=None, *args, **kwargs):
@@ -281,53 +218,17 @@ class DGT_concat_2D(nn.Module):
 
     # -- training path (opt-in: hip_training) ------------------------------------------------------------
     def _train_engine(self, node_mask, edge_mask, device):
-        """One TrainEngine2D (jodo_train2d handle + device tables) per batch of atom counts, keyed by the counts themselves like
-        DGT_concat._train_engine; all engines of the module share its two activation workspaces."""
+        """One TrainEngine2D (jodo_train2d handle + device tables) per batch of atom counts, in the module's bounded cache
+        (_runtime.HostRuntime._engine_for_masks)."""
         from ..train import TrainEngine2D
-        B, N = node_mask.shape[0], node_mask.shape[1]
         opts = tuple(sorted((getattr(self, 'train_options', None) or {}).items()))
-        last = self.__dict__.get('_train_last')
-        if (last is not None and last[0] is node_mask and last[1] == node_mask._version and last[2] is edge_mask
-                and last[3] == edge_mask._version and last[4] == opts):
-            return last[5]                                       # the two forwards of a self-conditioned step: no host work
-        hint = getattr(node_mask, '_jodo_counts', None)          # counts the loss already has on the host (losses.process_batch_2D)
-        if hint is not None and len(hint) == B:
-            n_host = np.ascontiguousarray(hint, dtype=np.int32)
-        else:
-            nm = node_mask.reshape(B, N)
-            n_nodes = nm.sum(1).round().to(torch.int32)
-            prefix = (torch.arange(N, device=nm.device).unsqueeze(0) < n_nodes.unsqueeze(1))
-            em = edge_mask.reshape(B, N, N)
-            want = prefix.unsqueeze(1) & prefix.unsqueeze(2) & (~torch.eye(N, dtype=torch.bool, device=nm.device))
-            ok = torch.stack([(prefix.to(nm.dtype) == nm).all(), (want.to(em.dtype) == em).all()]).to(torch.int32)
-            host = torch.cat([n_nodes, ok]).cpu().numpy()        # counts and both mask checks in one transfer
-            if not host[B]:
-                raise ValueError("node_mask must be a prefix mask (real atoms first), as the samplers build it")
-            if not host[B + 1]:
-                raise ValueError("edge_mask must be node_mask x node_mask with the diagonal removed")
-            n_host = np.ascontiguousarray(host[:B])
-        key = (str(device), N, opts) + tuple(int(v) for v in n_host)
-        cache = self.__dict__.setdefault('_train_engines', {})
-        eng = cache.pop(key, None)
-        if eng is None:
-            named = self.__dict__.get('_train_named')
-            if named is None:
-                named = self.__dict__['_train_named'] = TrainEngine2D.named_table([(k, tuple(v.shape)) for k, v in self.state_dict().items()])
-            pool = self.__dict__.setdefault('_train_pool', TrainEngine2D.new_pool())
-            eng = TrainEngine2D(self._cfg_struct, n_host, N, named, device, pool=pool, options=dict(opts))
-            while len(cache) >= 16:
-                cache.pop(next(iter(cache)))
-        cache[key] = eng                                         # most recently used last
-        self.__dict__['_train_last'] = (node_mask, node_mask._version, edge_mask, edge_mask._version, opts, eng)
-        return eng
+        return self._engine_for_masks(TrainEngine2D, self._cfg_struct, node_mask, edge_mask, device, opts)
 
     def _forward_train(self, xh, edge_x, cond_x, cond_edge_x, noise_level, node_mask, edge_mask, wants_grad):
         from ..train import dgt2d_autograd
         f32 = lambda x: None if x is None else x.detach().to(torch.float32).contiguous()
         eng = self._train_engine(node_mask, edge_mask, xh.device)
-        p = float(self.dropout_p) if self.training else 0.0
-        # dropout masks: counter-based, keyed by a seed drawn from torch's generator (so torch.manual_seed reproduces a step)
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if p > 0 else 0
+        p, seed = self._dropout_draw()
         params = list(self.parameters())                         # state_dict order: this tree has no buffers
         args = (eng, p, seed, f32(xh), f32(edge_x), f32(cond_x), f32(cond_edge_x), f32(noise_level))
         if wants_grad:

@@ -133,15 +133,44 @@ class TrainEngine:
         free = [s_ for s_ in pool['slots'] if not s_['live']]
         slot = max(free, key=lambda s_: s_['stamp']) if free else min(pool['slots'], key=lambda s_: s_['stamp'])
         if slot['buf'] is None or slot['buf'].numel() < self.ws_bytes or slot['buf'].device != device:
-            # grow with headroom: a shuffling loader's batches differ by a few per cent in sum n^2, and re-allocating gigabytes
-            # whenever a slightly larger one arrives stalls the step (batch 2 048: 440 ms per step instead of 190 while the
-            # maximum was still being found)
-            first = slot['buf'] is None
+            want = self._grown_bytes(slot['buf'], device)
             slot['buf'] = None                                   # release before growing
-            slot['buf'] = torch.zeros(self.ws_bytes if first else int(self.ws_bytes * 1.2), dtype=torch.uint8, device=device)
+            slot['buf'] = torch.zeros(want, dtype=torch.uint8, device=device)
         pool['stamp'] += 1
         slot['stamp'], slot['live'] = pool['stamp'], bool(keep)
         return slot
+
+    def _grown_bytes(self, buf, device):
+        """The size of the workspace that replaces `buf` (None: the slot's first).  Grown with headroom: a shuffling loader's batches
+        differ by a few per cent in sum n^2, and re-allocating gigabytes whenever a slightly larger one arrives stalls the step
+        (batch 2 048: 440 ms per step instead of 190 while the maximum was still being found)."""
+        return self.ws_bytes if buf is None else int(self.ws_bytes * 1.2)
+
+    def check_free(self):
+        """Called when a cached engine is taken up again.  Nothing to check here: TrainEngineCDGS, whose workspace grows with the padded
+        width, looks at the device's free memory."""
+
+    def _slot_or_raise(self, stamp):
+        slot = self.slot_of(self.stamp if stamp is None else stamp)
+        if slot is None:
+            raise RuntimeError("the activations of this forward were overwritten by later training-path forwards of the same module "
+                               "(%d activation workspaces per module, INTEGRATION.md §5); call backward earlier" % len(self.pool['slots']))
+        return slot
+
+    def _grad_buffer(self, params):
+        """Gradient tensors like `params`, carved from one allocation (the library then zeroes them with a single fill), every slice on
+        a 16-byte boundary — the layout of jodo_amd/optim.py slice_offsets, which the flat optimiser's parameter buffer has too.  The
+        layout is computed once per engine."""
+        from .optim import carve, slice_offsets
+        lay = self.__dict__.get('_grad_layout')
+        if lay is None:
+            offs, total = slice_offsets([p.numel() for p in params])
+            lay = self._grad_layout = ([tuple(p.shape) for p in params], offs, total)
+        flat = torch.empty(lay[2], dtype=torch.float32, device=params[0].device)
+        tail = lay[1][-1] + params[-1].numel()
+        if tail != lay[2]:                                       # padding behind the LAST slice: no gradient buffer follows it, so the
+            flat[tail:].zero_()                                  # library's fill does not reach it, and the norm of `flat` reads it
+        return carve(flat, lay[0], lay[1])
 
     def forward(self, params, xh, edge_x, cond_x, cond_edge_x, noise_level, context, dropout_p, seed, keep=False, save_activations=True):
         """params: contiguous float32 tensors in the order of `named_shapes`.  Returns (out_xh, out_edge); the activations stay
@@ -185,23 +214,8 @@ class TrainEngine:
 
     def backward(self, params, noise_level, d_out_x, d_out_e, dropout_p, seed, stamp=None):
         """Gradients of every parameter for the forward `stamp` (default: this engine's last forward)."""
-        slot = self.slot_of(self.stamp if stamp is None else stamp)
-        if slot is None:
-            raise RuntimeError("the activations of this forward were overwritten by later training-path forwards of the same module "
-                               "(%d activation workspaces per module, INTEGRATION.md §5); call backward earlier" % len(self.pool['slots']))
-        # one allocation for all gradients (the library then zeroes them with a single fill), every slice on a 16-byte boundary — the
-        # layout of jodo_amd/optim.py slice_offsets, which the flat optimiser's parameter buffer has too
-        lay = self.__dict__.get('_grad_layout')
-        if lay is None:
-            from .optim import slice_offsets
-            offs, total = slice_offsets([p.numel() for p in params])
-            lay = self._grad_layout = ([tuple(p.shape) for p in params], offs, total)
-        from .optim import carve
-        flat = torch.empty(lay[2], dtype=torch.float32, device=params[0].device)
-        tail = lay[1][-1] + params[-1].numel()
-        if tail != lay[2]:                                       # padding behind the LAST slice: no gradient buffer follows it, so the
-            flat[tail:].zero_()                                  # library's fill does not reach it, and the norm of `flat` reads it
-        grads = carve(flat, lay[0], lay[1])
+        slot = self._slot_or_raise(stamp)
+        grads = self._grad_buffer(params)
         self._check(self._fn('backward')(
             self.handle, capi.ptr(self.desc), self._ptrs(params), self._ptrs(grads), self.n_params, capi.ptr(noise_level),
             capi.ptr(d_out_x), capi.ptr(d_out_e), ctypes.c_float(dropout_p), ctypes.c_uint64(seed), capi.ptr(slot['buf']),
@@ -239,20 +253,8 @@ class TrainEngineEGNN(TrainEngine):
 
     def backward(self, params, d_out, stamp=None):
         """Gradients of every parameter for d_out [B] and the forward `stamp` (default: this engine's last forward)."""
-        slot = self.slot_of(self.stamp if stamp is None else stamp)
-        if slot is None:
-            raise RuntimeError("the activations of this forward were overwritten by later training-path forwards of the same module "
-                               "(%d activation workspaces per module, INTEGRATION.md §5); call backward earlier" % len(self.pool['slots']))
-        from .optim import carve, slice_offsets
-        lay = self.__dict__.get('_grad_layout')
-        if lay is None:
-            offs, total = slice_offsets([p.numel() for p in params])
-            lay = self._grad_layout = ([tuple(p.shape) for p in params], offs, total)
-        flat = torch.empty(lay[2], dtype=torch.float32, device=params[0].device)
-        tail = lay[1][-1] + params[-1].numel()
-        if tail != lay[2]:
-            flat[tail:].zero_()
-        grads = carve(flat, lay[0], lay[1])
+        slot = self._slot_or_raise(stamp)
+        grads = self._grad_buffer(params)
         self._check(self._fn('backward')(self.handle, capi.ptr(self.desc), self._ptrs(params), self._ptrs(grads), self.n_params,
                                          capi.ptr(d_out), capi.ptr(slot['buf']), self._stream()), self._abi + '_backward')
         slot['live'] = False
@@ -299,26 +301,18 @@ class TrainEngineCDGS(TrainEngine):
         if self.ws_bytes > avail:
             self._refuse(avail)
 
-    def _take_slot(self, device, keep):
-        """TrainEngine._take_slot with the growth checked at the size that is really allocated: the slot the base class will choose is
-        grown here, with the 20 % headroom when that fits, without it when only the exact size fits, and refused (bytes wanted, bytes
-        free) when neither does; the base class then finds the buffer large enough."""
+    def _grown_bytes(self, buf, device):
+        """TrainEngine._grown_bytes checked against the device's free memory: the 20 % headroom when that fits, the exact size when
+        only that fits, refused (bytes wanted, bytes free) when neither does."""
+        want = super()._grown_bytes(buf, device)
         dev = torch.device(device)
         if dev.type == 'cuda':
-            free = [s_ for s_ in self.pool['slots'] if not s_['live']]
-            slot = max(free, key=lambda s_: s_['stamp']) if free else min(self.pool['slots'], key=lambda s_: s_['stamp'])
-            buf = slot['buf']
-            if buf is None or buf.numel() < self.ws_bytes or buf.device != dev:
-                releasing = buf.numel() if buf is not None and buf.device == dev else 0
-                avail = self._available(dev, releasing)
-                want = self.ws_bytes if buf is None else int(self.ws_bytes * 1.2)
-                if want > avail:
-                    want = self.ws_bytes
-                if want > avail:
-                    self._refuse(avail)
-                slot['buf'] = buf = None                          # release before growing
-                slot['buf'] = torch.zeros(want, dtype=torch.uint8, device=dev)
-        return super()._take_slot(device, keep)
+            avail = self._available(dev, buf.numel() if buf is not None and buf.device == dev else 0)
+            if want > avail:
+                want = self.ws_bytes
+            if want > avail:
+                self._refuse(avail)
+        return want
 
     def forward(self, tensors, time_freq, t, x, edge_x, dropout_p, seed, keep=False):
         """tensors: contiguous float32 tensors in the order of `named_shapes` (parameters and buffers).  Returns (atom_score, bond_score);
@@ -336,21 +330,8 @@ class TrainEngineCDGS(TrainEngine):
     def backward(self, tensors, x, edge_x, d_out_x, d_out_e, dropout_p, seed, stamp=None):
         """Gradients of every PARAMETER of `tensors` (state_dict order, the buffers skipped) for the forward `stamp` (default: this
         engine's last forward)."""
-        slot = self.slot_of(self.stamp if stamp is None else stamp)
-        if slot is None:
-            raise RuntimeError("the activations of this forward were overwritten by later training-path forwards of the same module "
-                               "(%d activation workspaces per module, INTEGRATION.md §5); call backward earlier" % len(self.pool['slots']))
-        from .optim import carve, slice_offsets
-        ps = [p for p, buf in zip(tensors, self.is_buffer) if not buf]
-        lay = self.__dict__.get('_grad_layout')
-        if lay is None:
-            offs, total = slice_offsets([p.numel() for p in ps])
-            lay = self._grad_layout = ([tuple(p.shape) for p in ps], offs, total)
-        flat = torch.empty(lay[2], dtype=torch.float32, device=ps[0].device)
-        tail = lay[1][-1] + ps[-1].numel()
-        if tail != lay[2]:
-            flat[tail:].zero_()
-        grads = carve(flat, lay[0], lay[1])
+        slot = self._slot_or_raise(stamp)
+        grads = self._grad_buffer([p for p, buf in zip(tensors, self.is_buffer) if not buf])
         it = iter(grads)
         slots = (ctypes.c_void_p * self.n_params)(*[None if buf else next(it).data_ptr() for buf in self.is_buffer])
         self._check(self._fn('backward')(

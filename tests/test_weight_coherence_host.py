@@ -123,3 +123,103 @@ def test_sub_batch_split_is_keyed_on_mask_storage():
     assert model._split_of(nm.view_as(nm), em, 2) is fresh
     em.mul_(1.0)                                                  # the edge mask's version counts too
     assert model._split_of(nm, em, 2) is not fresh
+
+
+# ---------------------------------------------------------------------------------------------
+# the same contract for the models whose blob is packed on the host (jodo_amd/models/_runtime.py is the one implementation)
+# ---------------------------------------------------------------------------------------------
+def _build(kind):
+    if kind == 'egnn':
+        from jodo_amd.cond_gen.model import EGNN
+        return EGNN(5, 0, 64, n_layers=2, attention=True, node_attr=1).eval()
+    name, cfg = dict(dgt2d=('DGT_concat_2D', 'vpsde_zinc_2d_jodo'), cdgs=('CDGS', 'vpsde_qm9_2d_cdgs'))[kind]
+    return deterministic_init_(get_model_class(name)(make_config(cfg)), seed=3).eval()
+
+
+@pytest.fixture(params=['dgt2d', 'cdgs', 'egnn'])
+def hosted(request, monkeypatch):
+    """(model, calls): counting fakes of the model's host packer and, where the model has one, of its tape packer.  The fake blob is
+    the content of the state_dict it is given and the fake tape is a copy of the blob it is derived from, so a stale blob or tape is
+    told apart from a fresh one by content."""
+    kind = request.param
+    calls = dict(blob=0, tape=0)
+
+    def pack(cfg_struct, state_dict, device=None):
+        calls['blob'] += 1
+        return next(iter(state_dict.values())).detach().double().sum().reshape(1).clone(), None, 0
+
+    def tape(cfg_struct, blob_host, woff, n_woff, device=None):
+        calls['tape'] += 1
+        return blob_host.clone(), None
+
+    monkeypatch.setattr(capi, 'pack_weights_' + dict(dgt2d='2d').get(kind, kind), pack)
+    if kind != 'egnn':
+        monkeypatch.setattr(capi, 'split_tape_' + dict(dgt2d='2d').get(kind, kind), tape)
+        monkeypatch.setattr(torch.cuda, 'is_current_stream_capturing', lambda: False)      # (asks the driver: there is none here)
+    model = _build(kind)
+    if kind != 'egnn':
+        model.bf16x3 = True
+    return model, calls
+
+
+def _check_repacked_once(model, calls, n):
+    """The n-th pack happened exactly once, the blob holds the current weights, and the tape (where there is one) was rebuilt from it."""
+    packed = model._weights('cpu')
+    assert model._weights('cpu') is packed and packed is model._packed
+    has_tape = hasattr(model, '_tape')
+    assert calls == dict(blob=n, tape=n if has_tape else 0)
+    assert float(packed[1]) == float(_content(model))
+    if has_tape:
+        assert model._tape[0] is model._packed
+        tape, _ = model._split_tape('cpu')
+        assert tape is model._tape[1] and float(tape) == float(_content(model)) and calls['tape'] == n
+
+
+def _data_write(model):
+    versions = [p._version for p in model.parameters()]
+    for p in model.parameters():
+        p.data.mul_(2.0)
+    assert [p._version for p in model.parameters()] == versions
+
+
+def test_hosted_blob_follows_version_bumping_writes(hosted):
+    model, calls = hosted
+    _check_repacked_once(model, calls, 1)
+    with torch.no_grad():
+        for p in model.parameters():
+            p.mul_(2.0)
+    _check_repacked_once(model, calls, 2)
+
+
+def test_hosted_blob_follows_data_writes_and_invalidate(hosted):
+    model, calls = hosted
+    _check_repacked_once(model, calls, 1)
+    _data_write(model)
+    assert model._weights('cpu')[1] is not None and calls['blob'] == 1     # nobody told the module: the stale blob is still served
+    model.invalidate_packed_weights()
+    assert model._packed is None and getattr(model, '_tape', None) is None
+    _check_repacked_once(model, calls, 2)
+
+
+@pytest.mark.parametrize('hosted', ['dgt2d', 'cdgs'], indirect=True)
+def test_hosted_blob_follows_the_fingerprint_recheck(hosted):
+    """A `.data` write caught by the fingerprint: whatever drops `_packed` drops the tape derived from it.  (Not the classifier, which
+    never rechecks: its plan lookup is per call, jodo_amd/cond_gen/model.py.)"""
+    model, calls = hosted
+    _check_repacked_once(model, calls, 1)
+    model._recheck_weights()                                      # unchanged weights: the fingerprint matches, nothing is dropped
+    assert model._packed is not None and model._tape[0] is model._packed
+    _check_repacked_once(model, calls, 1)
+    _data_write(model)
+    model._recheck_weights()
+    assert model._packed is None and model._tape is None
+    _check_repacked_once(model, calls, 2)
+
+
+def test_hosted_blob_follows_load_state_dict(hosted):
+    model, calls = hosted
+    _check_repacked_once(model, calls, 1)
+    sd = {k: v.clone() * 2.0 for k, v in model.state_dict().items()}
+    model.load_state_dict(sd)
+    assert model._packed is None and getattr(model, '_tape', None) is None      # the post hook dropped both
+    _check_repacked_once(model, calls, 2)
