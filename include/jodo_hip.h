@@ -397,6 +397,15 @@ int jodo_train_gemm(int tA, int tB, int M, int N, int K, const float* A, int lda
  * like C; dbias (tA = 1, act = 0; C is accumulated into): dbias[m] += sum_k A(k, m), the bias gradient riding on a weight-gradient product */
 int jodo_train_gemm_ex(int tA, int tB, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
                        const float* bias, int act, float* out2, float* dbias, float* ws, size_t ws_floats, void* stream);
+/* the split-bf16 form of the same product (tests; the training step reaches it through jodo_cdgs_train_set_option 3): both fp32
+ * operands are split into hi + mid + lo bf16 terms on their way into LDS, a K = 16 step is the six products h*l, l*h, m*m, h*m, m*h, h*h
+ * on v_mfma_f32_32x32x16_bf16 into fp32 accumulators (dropped: m*l, l*m, l*l <= 3 * 2^-26 |a b|).  Same layouts, tiling, split-K
+ * slices and slice order as jodo_train_gemm, no atomics.  acc as jodo_train_gemm, act / out2 / dbias as jodo_train_gemm_ex (act is not
+ * combined with acc; dbias needs tA = 1 and act = 0 and is always added to); dropout_p / seed / site: the dropout multiplier of
+ * element m N + n on out2 (act 2), train_common.h drop_mul.  An output that is a single product with an exactly-bf16 factor (the other K - 1 terms zero) is exact. */
+int jodo_train_gemm_s(int tA, int tB, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
+                      const float* bias, int acc, int act, float* out2, float* dbias, float dropout_p, uint64_t seed, int site,
+                      float* ws, size_t ws_floats, void* stream);
 
 /* ---- optimiser side of the training step on flat buffers (csrc/train_step.hip; host mirror: jodo_amd/optim.py) ----------------------
  * jodo_adam_step  <- optimizer.step() of the optimisers get_optimizer builds, losses.py:14-26: torch.optim.AdamW(amsgrad=True,
@@ -858,7 +867,14 @@ int jodo_debug_gemm_cdgs(int split, int mode, const jodo_cdgs_cfg* cfg, int B, i
  * (nf 256), n_heads dividing nf, 1 <= n_layers <= 16, edge_ch >= 2.
  * Inputs: time_freq [nf / 2] (the sinusoid's frequencies, caller-made as for jodo_cdgs_pack_weights_host), t [B], x [B, N, atom_ch],
  * edge_x [B, N, N, edge_ch]; the backward reads x and edge_x again (embedding weight gradients).  No input gradients.
- * jodo_cdgs_train_set_option: option 2 only (accepted for parity; the forward keeps the same tensors either way).
+ * jodo_cdgs_train_set_option: option 2 (0 / 1, accepted for parity; the forward keeps the same tensors either way) and option 3 =
+ * the product forms that run in split-bf16 (csrc/train_gemm.hip k_gemm_s: three bf16 terms per fp32 operand, six bf16 MFMAs per K = 16
+ * step, fp32 accumulation, same plan and slice order as the fp32 product, bit-reproducible), a bit mask: 1 forward products (every
+ * Linear / 1x1 convolution, the tanh and SiLU x dropout epilogues included), 2 data gradients, 4 weight gradients with their bias
+ * sums; 0 = every product in exact fp32, the default.  The mask covers EVERY product of the step, the time MLP's and the per-block
+ * time shifts over the B rows included; GINE, attention, the GroupNorms, the random-walk features and all reductions stay fp32 code.
+ * The forward and the backward read the mask when they run.  Values outside 0..7: JODO_ERR_ARG; a non-zero mask on the host build of
+ * the file (no matrix instructions: exact fp32 only): JODO_ERR_UNSUPPORTED.  jodo_cdgs_train_get_option reads an option back (2: 1).
  * jodo_cdgs_train_debug_locate: 0 = h after `layer` blocks [B N, nf], 1 = e after `layer` blocks [B N^2, nf], 2 = alpha of block
  * `layer` [B N^2, n_heads], 3 = xhat of its norm2_edge [B N^2, nf]. */
 typedef struct jodo_cdgs_train jodo_cdgs_train;
@@ -870,6 +886,7 @@ size_t jodo_cdgs_train_workspace_bytes(const jodo_cdgs_train* t);
 const void* jodo_cdgs_train_desc_host(const jodo_cdgs_train* t);
 int jodo_cdgs_train_upload(jodo_cdgs_train* t, void* desc_dev, void* stream);
 int jodo_cdgs_train_set_option(jodo_cdgs_train* t, int option, int value);
+int jodo_cdgs_train_get_option(const jodo_cdgs_train* t, int option, int* value);
 int jodo_cdgs_train_debug_locate(const jodo_cdgs_train* t, int what, int layer, size_t* byte_offset, size_t* count);
 /* tests: out[rows, F] = the dropout multipliers of rows row0 .. row0 + rows - 1 of a [., F] tensor at `site`, element row * F + f */
 int jodo_cdgs_train_debug_drop(float dropout_p, uint64_t seed, int site, int64_t row0, int rows, int F, float* out, void* stream);

@@ -156,6 +156,13 @@ def _bind_cdgs(L):
     chk.restype = size.restype = pack.restype = lay.restype = fill.restype = fwd.restype = i
     _bind_cdgs_split(L)
     bind_cdgs_train(L)
+    try:                                                     # the training GEMM's split-bf16 form on its own (tests, tools)
+        gs = L.jodo_train_gemm_s
+    except AttributeError as e:
+        raise JodoHipError("%s lacks the split-bf16 training GEMM (%s): rebuild it with python -c 'import __graft_entry__ as g; g.build()'"
+                           % (LIB_PATH, e))
+    gs.argtypes = [i] * 5 + [p, i, p, i, p, i, p, i, i, p, p, ctypes.c_float, ctypes.c_uint64, i, p, ctypes.c_size_t, p]
+    gs.restype = i
 
 
 def _bind_cdgs_split(L):
@@ -179,20 +186,22 @@ def bind_cdgs_train(L):
     jodo_amd.train.TrainEngineCDGS to a library handed to it (the host build of the same source the CPU suite drives)."""
     i, p, f, u64, z = ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_uint64, ctypes.c_size_t
     try:
-        create, destroy, dbytes, wbytes, dhost, upload, setopt, locate, fwd, bwd = (getattr(L, 'jodo_cdgs_train_' + n) for n in (
-            'create', 'destroy', 'desc_bytes', 'workspace_bytes', 'desc_host', 'upload', 'set_option', 'debug_locate', 'forward', 'backward'))
+        create, destroy, dbytes, wbytes, dhost, upload, setopt, getopt, locate, fwd, bwd = (getattr(L, 'jodo_cdgs_train_' + n) for n in (
+            'create', 'destroy', 'desc_bytes', 'workspace_bytes', 'desc_host', 'upload', 'set_option', 'get_option', 'debug_locate', 'forward',
+            'backward'))
     except AttributeError as e:
         raise JodoHipError("the library lacks the CDGS training exports (%s): rebuild it with python -c 'import __graft_entry__ as g; g.build()'" % e)
     create.argtypes = [p, i, i, p, p, i, p]
     destroy.argtypes = dbytes.argtypes = wbytes.argtypes = dhost.argtypes = [p]
     upload.argtypes = [p, p, p]
     setopt.argtypes = [p, i, i]
+    getopt.argtypes = [p, i, p]
     locate.argtypes = [p, i, i, p, p]
     fwd.argtypes = [p, p, p, i, p, p, p, p, f, u64, p, p, p, p]
     bwd.argtypes = [p, p, p, p, i, p, p, p, p, f, u64, p, p]
     L.jodo_cdgs_train_debug_drop.argtypes = [f, u64, i, ctypes.c_int64, i, i, p, p]
     L.jodo_cdgs_train_debug_drop.restype = i
-    create.restype = upload.restype = setopt.restype = locate.restype = fwd.restype = bwd.restype = i
+    create.restype = upload.restype = setopt.restype = getopt.restype = locate.restype = fwd.restype = bwd.restype = i
     destroy.restype = None
     dbytes.restype = wbytes.restype = z
     dhost.restype = p

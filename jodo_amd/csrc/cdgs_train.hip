@@ -499,6 +499,7 @@ struct jodo_cdgs_train {
     Lin time0, time1, ecate, eexist, espd, eemb, adeg, acate, arw, aemb, ah[3], bh[3], xh[3];
     std::vector<BlkIx> blk;
     size_t ws_bytes;
+    int split = 0;                    // option 3: product forms in split-bf16 (1 forward, 2 data gradients, 4 weight gradients)
 };
 
 namespace {
@@ -539,30 +540,37 @@ void layout(const jodo_cdgs_train& t, Arena& a, Bufs& b) {
 
 struct Ctx {
     const jodo_cdgs_train& t; Geo g; const float* const* P; float* const* G; Bufs& b; hipStream_t s; float p_drop; unsigned long long seed;
+    int split = 0;                    // jodo_cdgs_train::split: which of the product forms below run as GemmEpi::split
+    GemmEpi epi(int act, float* out2, Drop d, float* dbias, int form) const {
+        GemmEpi e; e.act = act; e.out2 = out2; e.drop = d; e.dbias = dbias; e.split = (split & form) ? 1 : 0;
+        return e;
+    }
     const float* p(int i) const { return P[i]; }
     float* gr(int i) const { return G[i]; }
     Drop drop(int l, int site) const { Drop d; d.p = p_drop; d.seed = seed; d.site = (unsigned)(l * 8 + site); return d; }
     Drop nod() const { Drop d; d.p = 0.f; d.seed = 0; d.site = 0; return d; }
     // Y[rows, N] (ldy) (+)= X[rows, K] (ldx) W[N, K]^T (ldw) + bias
     void lin(const float* X, int ldx, long rows, int K, const float* W, int ldw, int N, const float* bias, float* Y, int ldy, int acc) const {
-        gemm(s, 0, 1, (int)rows, N, K, X, ldx, W, ldw, Y, ldy, bias, acc, b.splitk, b.splitk_floats);
+        const GemmEpi e = epi(0, nullptr, nod(), nullptr, 1);
+        gemm(s, 0, 1, (int)rows, N, K, X, ldx, W, ldw, Y, ldy, bias, acc, b.splitk, b.splitk_floats, &e);
     }
     void lin_tanh(const float* X, long rows, int K, const float* W, int N, float* Y) const {
-        GemmEpi e; e.act = 1; e.out2 = nullptr; e.drop = nod(); e.dbias = nullptr;
+        const GemmEpi e = epi(1, nullptr, nod(), nullptr, 1);
         gemm(s, 0, 1, (int)rows, N, K, X, K, W, K, Y, N, nullptr, 0, b.splitk, b.splitk_floats, &e);
     }
     // pre = X W^T + bias (kept), act = SiLU(pre) * dropout(row N + col); both dense [rows, N]
     void lin_silu(const float* X, long rows, int K, const float* W, int N, const float* bias, float* pre, float* act, Drop d) const {
-        GemmEpi e; e.act = 2; e.out2 = act; e.drop = d; e.dbias = nullptr;
+        const GemmEpi e = epi(2, act, d, nullptr, 1);
         gemm(s, 0, 1, (int)rows, N, K, X, K, W, K, pre, N, bias, 0, b.splitk, b.splitk_floats, &e);
     }
     // dX[rows, K] (ldx) (+)= dY[rows, N] (ldy) W[N, K] (ldw)
     void lin_dx(const float* dY, int ldy, long rows, int N, const float* W, int ldw, int K, float* dX, int ldx, int acc) const {
-        gemm(s, 0, 0, (int)rows, K, N, dY, ldy, W, ldw, dX, ldx, nullptr, acc, b.splitk, b.splitk_floats);
+        const GemmEpi e = epi(0, nullptr, nod(), nullptr, 2);
+        gemm(s, 0, 0, (int)rows, K, N, dY, ldy, W, ldw, dX, ldx, nullptr, acc, b.splitk, b.splitk_floats, &e);
     }
     // dW[N, K] (lddw) += dY[rows, N]^T X[rows, K]; db[N] += column sums of dY
     void lin_dw(const float* dY, int ldy, long rows, int N, const float* X, int ldx, int K, float* dW, int lddw, float* db = nullptr) const {
-        GemmEpi e; e.act = 0; e.out2 = nullptr; e.drop = nod(); e.dbias = db;
+        const GemmEpi e = epi(0, nullptr, nod(), db, 4);
         gemm(s, 1, 0, N, K, (int)rows, dY, ldy, X, ldx, dW, lddw, nullptr, 1, b.splitk, b.splitk_floats, &e);
     }
     // a whole Linear on dense operands: forward, and its backward (weight and bias gradients, dX written or accumulated; dX may be null)
@@ -882,10 +890,26 @@ int jodo_cdgs_train_create(const jodo_cdgs_cfg* cfg, int B, int N, const int32_t
 void jodo_cdgs_train_destroy(jodo_cdgs_train* t) { delete t; }
 size_t jodo_cdgs_train_desc_bytes(const jodo_cdgs_train* t) { return t ? t->tables.size() * sizeof(int) : 0; }
 size_t jodo_cdgs_train_workspace_bytes(const jodo_cdgs_train* t) { return t ? t->ws_bytes : 0; }
-// option 2 only (accepted for parity with jodo_train2d_set_option; the forward keeps the same tensors either way)
+// option 2 (accepted for parity with jodo_train2d_set_option; the forward keeps the same tensors either way) and option 3: the product
+// forms that run in split-bf16 (train_gemm.h GemmEpi::split), a bit mask: 1 forward products, 2 data gradients, 4 weight gradients;
+// read by the forward and by the backward when they run.  The host build of this file has no split form: it stays exact fp32 and refuses.
 int jodo_cdgs_train_set_option(jodo_cdgs_train* t, int option, int value) {
     if (!t) return jodo_set_error(JODO_ERR_ARG, "jodo_cdgs_train_set_option: null handle");
+    if (option == 3) {
+        if (value < 0 || value > 7) return jodo_set_error(JODO_ERR_ARG, "jodo_cdgs_train_set_option: option 3 takes a mask 0..7, got %d", value);
+        if (value != 0 && !gemm_split_built)
+            return jodo_set_error(JODO_ERR_UNSUPPORTED, "jodo_cdgs_train_set_option: the host build has no split-bf16 products (exact fp32 only)");
+        t->split = value;
+        return JODO_OK;
+    }
     if (option != 2 || (value != 0 && value != 1)) return jodo_set_error(JODO_ERR_ARG, "jodo_cdgs_train_set_option: option %d value %d", option, value);
+    return JODO_OK;
+}
+int jodo_cdgs_train_get_option(const jodo_cdgs_train* t, int option, int* value) {
+    if (!t || !value) return jodo_set_error(JODO_ERR_ARG, "jodo_cdgs_train_get_option: null argument");
+    if (option == 2) *value = 1;
+    else if (option == 3) *value = t->split;
+    else return jodo_set_error(JODO_ERR_ARG, "jodo_cdgs_train_get_option: option %d", option);
     return JODO_OK;
 }
 // tests: where a kept tensor lives in the workspace.  0 = h after `layer` blocks [B N, nf] (layer 0 .. n_layers), 1 = e after `layer`
@@ -933,7 +957,7 @@ int jodo_cdgs_train_forward(jodo_cdgs_train* t, const void* desc_dev, const floa
     Arena a{static_cast<char*>(workspace), 0}; Bufs bufs;
     layout(*t, a, bufs);
     const Geo g{t->B, t->N, static_cast<const int*>(desc_dev)};
-    Ctx c{*t, g, params_dev, nullptr, bufs, static_cast<hipStream_t>(stream), dropout_p, seed};
+    Ctx c{*t, g, params_dev, nullptr, bufs, static_cast<hipStream_t>(stream), dropout_p, seed, t->split};
     forward(c, tt, time_freq, x, edge_x, out_x, out_e);
     return jodo_check_launch("jodo_cdgs_train_forward");
 }
@@ -951,7 +975,7 @@ int jodo_cdgs_train_backward(jodo_cdgs_train* t, const void* desc_dev, const flo
     Arena a{static_cast<char*>(workspace), 0}; Bufs bufs;
     layout(*t, a, bufs);
     const Geo g{t->B, t->N, static_cast<const int*>(desc_dev)};
-    Ctx c{*t, g, params_dev, grads_dev, bufs, static_cast<hipStream_t>(stream), dropout_p, seed};
+    Ctx c{*t, g, params_dev, grads_dev, bufs, static_cast<hipStream_t>(stream), dropout_p, seed, t->split};
     backward(c, x, edge_x, d_out_x, d_out_e);
     return jodo_check_launch("jodo_cdgs_train_backward");
 }

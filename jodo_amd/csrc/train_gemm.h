@@ -10,7 +10,15 @@ namespace jt {
 // and out2[m, n] = SiLU(v) * dropout(element m N + n) with out2 laid out like C.  Not combined with acc.
 // dbias (weight-gradient products, tA = 1, act = 0): dbias[m] += sum_k A(k, m) — the bias gradient is the column sum of the very
 // dY tiles the product stages in LDS, so it rides along instead of a reduction pass of its own (accumulated in double per slice).
-struct GemmEpi { int act; float* out2; Drop drop; float* dbias; };
+// split != 0 (opt-in, device library only): the product runs in the three-term bf16 form (train_gemm.hip k_gemm_s) — same plan, same
+// slices, same epilogues, fp32-equivalent arithmetic on v_mfma_f32_32x32x16_bf16.  The host emulation's gemm ignores the field: that
+// build is exact fp32 (gemm_split_built tells the two apart).
+struct GemmEpi { int act; float* out2; Drop drop; float* dbias; int split = 0; };
+#if defined(__HIPCC__)
+constexpr bool gemm_split_built = true;
+#else
+constexpr bool gemm_split_built = false;
+#endif
 void gemm(hipStream_t s, int tA, int tB, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
           const float* bias, int acc, float* ws, size_t ws_floats, const GemmEpi* epi = nullptr);
 // Weight-gradient products queued by the backward and launched together (train_gemm.hip gemm_dw_group):

@@ -13,11 +13,16 @@
 // Bounds are checked on every edge (N = 3, K = 17 and ragged row counts all occur; unaligned operands take an element-wise path);
 // products whose tiles are all whole in K take the branch-free loader (FAST), small launches with four tiles in flight.  The tile order
 // is XCD-aware (k_gemm).
+// Below the fp32 kernels: the opt-in split-bf16 form of the same product (k_gemm_s, GemmEpi::split): 30 720 bytes of LDS per workgroup,
+// four to five workgroups per CU; its section's head comment has the layout.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <cstdio>
 #include <cstdlib>
+#include "../../include/jodo_hip.h"
+#include "jodo_hip_internal.h"
 #include "train_gemm.h"
+#include "dgt_split.h"
 
 namespace jt {
 
@@ -280,6 +285,227 @@ __global__ __launch_bounds__(256) void k_splitk_sum_group(GemmGroup G) {
     splitk_sum_block((long)((int)blockIdx.x - J.sb0), J.M, J.N, J.nz, J.part, J.C, J.ldc, nullptr, 1, e, sh);
 }
 
+// ================================================================ split-bf16 form (GemmEpi::split, opt-in) =====================
+// The same product on v_mfma_f32_32x32x16_bf16: both fp32 operands become hi + mid + lo (three bf16 terms, round-to-nearest-even per
+// term, exact residuals: dgt_split.h split8) ON THE WAY INTO LDS — once per workgroup, not once per reading wave — and a K = 16 step is
+// the six products h*l, l*h, m*m, h*m, m*h, h*h (dgt_split.h mfma_step_s, small terms first; dropped: m*l, l*m, l*l <= 3 * 2^-26 |a b|).
+// Same plan (train_gemm.h gemm_plan: 64 x 64 tiles, 2 x 2 waves of one 32 x 32 block, the same split-K slices summed by k_splitk_sum), the
+// same epilogues with the same element numbering, the same dbias column sum, no atomics.
+//
+// A K tile of 32 is two K = 16 steps: the even step's six products go to accumulator 0 and the odd step's to accumulator 1, issued in
+// turn, so neighbouring MFMAs are independent (dgt_split.h mfma_step_s2 says why) and each accumulator sees mfma_step_s's order for its
+// own k — which is what makes a product with a pure-bf16 factor exact: a_l s, then (a_l + a_m) s = (a - a_h) s, then a s, every partial
+// sum representable.  (Dealing ONE step's six products to two accumulators is not: a_l s + a_h s can need 25 bits.)
+//
+// LDS image per operand: [term hi | mid | lo][64 rows m or n][32 k + 8 pad] bf16 = 3 x 64 x 80 bytes = 15 360; both operands 30 720
+// bytes per workgroup, so LDS allows five workgroups per CU (160 KiB); registers (62 - 72 VGPRs + 32 AGPRs with one tile in flight,
+// DESIGN.md 4n) four to five: 16 - 20 waves per CU.
+// A lane reads 8 consecutive k of its row as one ds_read_b128 (lane map: head of dgt_split.h — row = lane & 31, k = 8 (lane >> 5) + j).
+// ds_read_b128 is served in groups of 16 lanes of one half-wave — rows {0-3, 12-15, 20-27} and {4-11, 16-19, 28-31} — over 64 banks =
+// sixteen 16-byte slots; a row is 5 slots long, 5 is odd, and each group's rows are distinct mod 16, so the 16 reads of a group fall
+// on 16 different slots: conflict-free.  (Unpadded 64-byte rows would put rows r and r + 4 on one slot.)
+// Staging: every thread holds 8 consecutive k of one row per operand and tile, so the split is one split8 and three 16-byte stores.
+// k-contiguous operands (X, dY rows, W rows): row tid / 4, two 16-byte loads; the others (transposed dY, plain B): row tid % 64, eight
+// 4-byte loads, each a coalesced 256-byte row segment per wave — these need no alignment at all.
+// The K tail of a product or slice is zero-filled BEFORE the split (store8), so the tail contributes exact zeros.
+using jd::bf16x8;
+constexpr int SLD = 40;                                      // bf16 per LDS row: 32 k + 8 pad (80 bytes = 5 slots)
+struct alignas(16) TileS { __bf16 t[3][64][SLD]; };
+
+template <bool KC>
+__device__ __forceinline__ void pos8(int tid, int& i, int& kk) {
+    if (KC) { i = tid >> 2; kk = (tid & 3) * 8; }
+    else { i = tid & 63; kk = (tid >> 6) * 8; }
+}
+template <bool KC>
+__device__ __forceinline__ void load8(const float* __restrict__ P, int ld, int i0, int imax, int k0, int kend, bool vec, int tid, float (&r)[8]) {
+    int i, kk;
+    pos8<KC>(tid, i, kk);
+    const int gi = i0 + i, gk = k0 + kk;
+    if (KC) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int gq = gk + 4 * h;
+            if (vec && gi < imax && gq + 3 < kend) {
+                const float4 v = *reinterpret_cast<const float4*>(P + (long)gi * ld + gq);
+                r[h * 4 + 0] = v.x; r[h * 4 + 1] = v.y; r[h * 4 + 2] = v.z; r[h * 4 + 3] = v.w;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) r[h * 4 + j] = (gi < imax && gq + j < kend) ? P[(long)gi * ld + gq + j] : 0.f;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) r[j] = (gi < imax && gk + j < kend) ? P[(long)(gk + j) * ld + gi] : 0.f;
+    }
+}
+// branch-free (FAST): rows past the edge are clamped to the last valid one (they only feed outputs that are never stored); k past the
+// end is clamped to the last valid quad (k-contiguous: K % 4 == 0, gemm_fast_s) or element, and zeroed in store8
+template <bool KC>
+__device__ __forceinline__ void load8_fast(const float* __restrict__ P, int ld, int i0, int imax, int k0, int kend, int tid, float (&r)[8]) {
+    int i, kk;
+    pos8<KC>(tid, i, kk);
+    int gi = i0 + i;
+    gi = gi < imax ? gi : imax - 1;
+    const int gk = k0 + kk;
+    if (KC) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int gq = gk + 4 * h < kend ? gk + 4 * h : kend - 4;
+            const float4 v = *reinterpret_cast<const float4*>(P + (long)gi * ld + gq);
+            r[h * 4 + 0] = v.x; r[h * 4 + 1] = v.y; r[h * 4 + 2] = v.z; r[h * 4 + 3] = v.w;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int k = gk + j < kend ? gk + j : kend - 1;
+            r[j] = P[(long)k * ld + gi];
+        }
+    }
+}
+template <bool KC>
+__device__ __forceinline__ void store8(TileS& S, int tid, const float (&r)[8], int k0, int kend) {
+    int i, kk;
+    pos8<KC>(tid, i, kk);
+    float x[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) x[j] = k0 + kk + j < kend ? r[j] : 0.f;       // the K tail counts as zeros, before the split
+    const jd::Split8 s = jd::split8(x);
+    *reinterpret_cast<bf16x8*>(&S.t[0][i][kk]) = s.h;
+    *reinterpret_cast<bf16x8*>(&S.t[1][i][kk]) = s.m;
+    *reinterpret_cast<bf16x8*>(&S.t[2][i][kk]) = s.l;
+}
+
+template <bool TA, bool TB, bool FAST, int PF>
+__global__ __launch_bounds__(256) void k_gemm_s(int M, int N, int K, int kchunk, const float* __restrict__ A, int lda, const float* __restrict__ B, int ldb,
+                                                float* __restrict__ C, int ldc, const float* __restrict__ bias, int acc, float* __restrict__ part, int vecA, int vecB, GemmEpi epi) {
+    __shared__ TileS As, Bs;
+    int bx = blockIdx.x, by = blockIdx.y;                    // XCD-aware tile order: as k_gemm
+    if (gridDim.x > 1 && gridDim.z == 1) {
+        const int NT = gridDim.x, lin = blockIdx.y * NT + blockIdx.x;
+        if (lin < NT * 8 * ((int)gridDim.y / 8)) {
+            const int xcd = lin & 7, slot = lin >> 3;
+            by = (slot / NT) * 8 + xcd;
+            bx = slot % NT;
+        }
+    }
+    const int bz = (int)blockIdx.z, nz = (int)gridDim.z;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int m0 = by * 64, n0 = bx * 64;
+    const int kbeg = bz * kchunk, kend = min(K, kbeg + kchunk);
+    const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32;
+    f32x16 c0, c1;                                           // even / odd K = 16 steps
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { c0[i] = 0.f; c1[i] = 0.f; }
+    float ra[PF][8], rb[PF][8];
+    double bsum = 0.0;                                       // epi.dbias: as gemm_tile (threads 0 .. 63, the fp32 values rebuilt exactly from their three terms)
+    const bool do_bias = TA && epi.dbias != nullptr && bx == 0 && tid < 64;
+    auto fetch = [&](int u, int k0) {
+        if (FAST) {
+            load8_fast<!TA>(A, lda, m0, M, k0, kend, tid, ra[u]);
+            load8_fast<TB>(B, ldb, n0, N, k0, kend, tid, rb[u]);
+        } else {
+            load8<!TA>(A, lda, m0, M, k0, kend, vecA != 0, tid, ra[u]);
+            load8<TB>(B, ldb, n0, N, k0, kend, vecB != 0, tid, rb[u]);
+        }
+    };
+#pragma unroll
+    for (int u = 0; u < PF; ++u)
+        if (kbeg + u * TK < kend) fetch(u, kbeg + u * TK);
+    const __bf16* ap = &As.t[0][wm + (lane & 31)][8 * (lane >> 5)];
+    const __bf16* bp = &Bs.t[0][wn + (lane & 31)][8 * (lane >> 5)];
+    for (int kb = kbeg; kb < kend; kb += PF * TK) {
+#pragma unroll
+        for (int u = 0; u < PF; ++u) {
+            const int k0 = kb + u * TK;
+            if (k0 < kend) {                                     // (uniform over the workgroup: the barriers below are safe)
+                store8<!TA>(As, tid, ra[u], k0, kend);
+                store8<TB>(Bs, tid, rb[u], k0, kend);
+                __syncthreads();
+                if (do_bias) {
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        const bf16x8 h = *reinterpret_cast<const bf16x8*>(&As.t[0][tid][8 * g]);
+                        const bf16x8 m = *reinterpret_cast<const bf16x8*>(&As.t[1][tid][8 * g]);
+                        const bf16x8 l = *reinterpret_cast<const bf16x8*>(&As.t[2][tid][8 * g]);
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) bsum += ((double)(float)h[j] + (double)(float)m[j]) + (double)(float)l[j];
+                    }
+                }
+                if (k0 + PF * TK < kend) fetch(u, k0 + PF * TK);  // refill the slot just consumed: PF tiles stay in flight
+                bf16x8 a[2][3], b[2][3];
+#pragma unroll
+                for (int st = 0; st < 2; ++st)
+#pragma unroll
+                    for (int t = 0; t < 3; ++t) {
+                        a[st][t] = *reinterpret_cast<const bf16x8*>(ap + t * 64 * SLD + 16 * st);
+                        b[st][t] = *reinterpret_cast<const bf16x8*>(bp + t * 64 * SLD + 16 * st);
+                    }
+#define JT_STEP_S(x, y)                                                              \
+    c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][x], b[0][y], c0, 0, 0, 0); \
+    c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][x], b[1][y], c1, 0, 0, 0);
+                JT_STEP_S(0, 2) JT_STEP_S(2, 0) JT_STEP_S(1, 1) JT_STEP_S(0, 1) JT_STEP_S(1, 0) JT_STEP_S(0, 0)
+#undef JT_STEP_S
+                __syncthreads();
+            }
+        }
+    }
+    if (do_bias && m0 + tid < M) {
+        if (part) part[(long)nz * M * N + (long)bz * M + m0 + tid] = (float)bsum;     // behind the partial tiles
+        else epi.dbias[m0 + tid] += (float)bsum;
+    }
+    // C/D map of the 32x32 forms: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+    const int col = n0 + wn + (lane & 31);
+    if (col >= N) return;
+    const float bv = (bias && !part) ? bias[col] : 0.f;
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+        const int row = m0 + wm + (s & 3) + 8 * (s >> 2) + 4 * (lane >> 5);
+        if (row >= M) continue;
+        const float v = c0[s] + c1[s];
+        if (part) part[((long)bz * M + row) * N + col] = v;
+        else if (epi.act) gemm_epilogue(epi, v + bv, C, (long)row * ldc + col, (long)row * N + col);
+        else {
+            float* o = C + (long)row * ldc + col;
+            *o = acc ? *o + (v + bv) : v + bv;
+        }
+    }
+}
+
+template <bool FAST, int PF>
+static void launch_s(hipStream_t s, int tA, int tB, dim3 grid, int M, int N, int K, int kchunk, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
+                     const float* bias, int acc, float* part, int vecA, int vecB, GemmEpi epi) {
+    const dim3 block(256);
+    if (tA && tB) hipLaunchKernelGGL((k_gemm_s<true, true, FAST, PF>), grid, block, 0, s, M, N, K, kchunk, A, lda, B, ldb, C, ldc, bias, acc, part, vecA, vecB, epi);
+    else if (tA) hipLaunchKernelGGL((k_gemm_s<true, false, FAST, PF>), grid, block, 0, s, M, N, K, kchunk, A, lda, B, ldb, C, ldc, bias, acc, part, vecA, vecB, epi);
+    else if (tB) hipLaunchKernelGGL((k_gemm_s<false, true, FAST, PF>), grid, block, 0, s, M, N, K, kchunk, A, lda, B, ldb, C, ldc, bias, acc, part, vecA, vecB, epi);
+    else hipLaunchKernelGGL((k_gemm_s<false, false, FAST, PF>), grid, block, 0, s, M, N, K, kchunk, A, lda, B, ldb, C, ldc, bias, acc, part, vecA, vecB, epi);
+}
+// the branch-free loader: k-contiguous operands need 16-byte addressable rows and whole quads to clamp to; the others nothing
+static bool gemm_fast_s(int tA, int tB, int K, int vecA, int vecB) {
+    const bool kq = K >= 4 && (K % 4) == 0;
+    return K >= 1 && (tA || (vecA && kq)) && (!tB || (vecB && kq));
+}
+// gemm() with epi.split set: the same plan, scratch layout and slice sum
+static void gemm_s(hipStream_t s, int tA, int tB, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
+                   const float* bias, int acc, float* ws, size_t ws_floats, const GemmEpi& epi) {
+    const GemmPlan p = gemm_plan(tA, M, N, K, ws != nullptr, ws_floats);
+    if (p.rm != 1 || p.rn != 1) { fprintf(stderr, "jodo gemm (split): tile %d x %d is not instantiated\n", p.rm, p.rn); abort(); }
+    float* part = p.nsplit > 1 ? ws : nullptr;
+    const dim3 grid((N + 63) / 64, (M + 63) / 64, p.nsplit);
+    const int vecA = ((reinterpret_cast<uintptr_t>(A) & 15) == 0 && (lda & 3) == 0) ? 1 : 0;
+    const int vecB = ((reinterpret_cast<uintptr_t>(B) & 15) == 0 && (ldb & 3) == 0) ? 1 : 0;
+    const bool fast = gemm_fast_s(tA, tB, K, vecA, vecB);
+    const long wgs = (long)grid.x * grid.y * grid.z;
+    if (fast && wgs <= 512 && (K < p.kchunk ? K : p.kchunk) > 2 * TK) launch_s<true, 4>(s, tA, tB, grid, M, N, K, p.kchunk, A, lda, B, ldb, C, ldc, bias, acc, part, vecA, vecB, epi);
+    else if (fast) launch_s<true, 1>(s, tA, tB, grid, M, N, K, p.kchunk, A, lda, B, ldb, C, ldc, bias, acc, part, vecA, vecB, epi);
+    else launch_s<false, 1>(s, tA, tB, grid, M, N, K, p.kchunk, A, lda, B, ldb, C, ldc, bias, acc, part, vecA, vecB, epi);
+    if (p.nsplit > 1) {
+        const long blocks = ((long)M * N + 31) / 32 + (epi.dbias ? (M + 31) / 32 : 0);
+        hipLaunchKernelGGL(k_splitk_sum, dim3((unsigned)blocks), dim3(256), 0, s, M, N, p.nsplit, part, C, ldc, bias, acc, epi);
+    }
+}
+
 template <bool FAST, int PF>
 static void launch(hipStream_t s, int tA, int tB, dim3 grid, int M, int N, int K, int kchunk, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
                    const float* bias, int acc, float* part, int vecA, int vecB, GemmEpi epi) {
@@ -306,6 +532,7 @@ void gemm(hipStream_t s, int tA, int tB, int M, int N, int K, const float* A, in
     if (shape_log()) { fprintf(shape_log(), "%d %d %d %d %d %d %d %d\n", tA, tB, M, N, K, lda, ldb, ldc); fflush(shape_log()); }
     GemmEpi epi;
     if (epi_in) epi = *epi_in; else { epi.act = 0; epi.out2 = nullptr; epi.drop.p = 0.f; epi.drop.seed = 0; epi.drop.site = 0; epi.dbias = nullptr; }
+    if (epi.split) { gemm_s(s, tA, tB, M, N, K, A, lda, B, ldb, C, ldc, bias, acc, ws, ws_floats, epi); return; }
     const GemmPlan p = gemm_plan(tA, M, N, K, ws != nullptr, ws_floats);
     float* part = p.nsplit > 1 ? ws : nullptr;
     const dim3 grid((N + 64 * p.rn - 1) / (64 * p.rn), (M + 64 * p.rm - 1) / (64 * p.rm), p.nsplit);
@@ -373,3 +600,14 @@ void gemm_dw_group(hipStream_t s, const GemmJob* jobs, int n, float* ws, size_t 
 }
 
 }  // namespace jt
+
+// tests: the split-bf16 form of the product on its own (include/jodo_hip.h)
+extern "C" int jodo_train_gemm_s(int tA, int tB, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc, const float* bias,
+                                 int acc, int act, float* out2, float* dbias, float dropout_p, uint64_t seed, int site, float* ws, size_t ws_floats, void* stream) {
+    if (!A || !B || !C || M < 0 || N < 0 || K < 0 || act < 0 || act > 2 || (act == 2 && !out2) || (act && acc) || (dbias && (!tA || act)) ||
+        !(dropout_p >= 0.f && dropout_p < 1.f) || site < 0)
+        return jodo_set_error(JODO_ERR_ARG, "jodo_train_gemm_s: bad argument");
+    jt::GemmEpi e; e.act = act; e.out2 = out2; e.drop.p = dropout_p; e.drop.seed = seed; e.drop.site = (unsigned)site; e.dbias = dbias; e.split = 1;
+    jt::gemm(static_cast<hipStream_t>(stream), tA, tB, M, N, K, A, lda, B, ldb, C, ldc, bias, acc, ws, ws_floats, &e);
+    return jodo_check_launch("jodo_train_gemm_s");
+}

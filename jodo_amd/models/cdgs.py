@@ -16,6 +16,9 @@ default call `last_flags` is None).  Sample quality under the split form is unte
 Training is opt-in: with `hip_training = True` (set by
 jodo_amd.losses.get_step_fn) a grad-enabled call runs csrc/cdgs_train.hip on the live parameters, keeps the activations, and
 loss.backward() returns every parameter's gradient (jodo_amd/train.py TrainEngineCDGS); unset, a grad-enabled call raises.
+`model.train_bf16x3 = True` (opt-in, runtime state, read per training-path call) runs the forward and data-gradient GEMMs of the training
+path — mask 3; an int 0..7 selects forms itself, 4 = the weight-gradient GEMMs, which measured no faster — in the split-bf16 form (csrc/train_gemm.hip k_gemm_s); `model.last_train_form` reports the
+mask the last training forward ran with.  `bf16x3` alone never changes training: that stays exact fp32.
 
 The edge GroupNorm of the reference normalises the dense padded tensor, so a molecule's scores depend on the width N the caller
 padded the batch to; the kernels reproduce that from the tensors' N.
@@ -135,6 +138,10 @@ class CDGS(TapeRuntime, nn.Module):
         self.split_bf16 = False       # the 3-D models' opt-in form; not built for this model (forward raises when set)
         self.bf16x3 = False           # opt-in, read per call: the split-bf16 (three-term) form of the node-row and edge-row GEMMs
                                       # (kc_gemm_s).  Combines with max_blocks.  The training path ignores it.
+        self.train_bf16x3 = False     # opt-in, read per training-path call: the split-bf16 form of the training products (True = the forms
+                                      # measured faster, mask 3; or a mask 0..7: 1 forward products, 2 data gradients, 4 weight gradients; train.split_mask).
+                                      # Inference calls ignore it; get_step_fn does not set it.
+        self.last_train_form = None   # the mask the last training-path forward ran with, read back from its engine
 
     # -- weights (cache, fingerprint, invalidation and the derived tape: _runtime.TapeRuntime) -----------
     def _key_tensors(self):
@@ -222,9 +229,12 @@ class CDGS(TapeRuntime, nn.Module):
         return self._engine_for_masks(TrainEngineCDGS, self._cfg_struct, node_mask, edge_mask, device)
 
     def _forward_train(self, t, x, edge_x, node_mask, edge_mask, wants_grad):
-        from ..train import cdgs_autograd
+        from ..train import cdgs_autograd, split_mask
         f32 = lambda v: v.detach().to(torch.float32).contiguous()
+        mask = split_mask(self.train_bf16x3)
         eng = self._train_engine(node_mask, edge_mask, x.device)
+        eng.set_form(mask)                                   # every call: the engine may be a cached one that last ran another form
+        self.last_train_form = eng.form
         p, seed = self._dropout_draw()
         freq = self.__dict__.get('_train_freq')
         if freq is None or freq.device != x.device:

@@ -261,15 +261,44 @@ class TrainEngineEGNN(TrainEngine):
         return grads
 
 
+TRAIN_BF16X3_ALL = 3      # what `train_bf16x3 = True` selects: forward products | data gradients.  Not the weight gradients (4): measured
+                          # on MI355X their split form is not faster than the fp32 one; mask 7 or 4 still selects them
+
+
+def split_mask(value):
+    """`CDGS.train_bf16x3` -> the mask of jodo_cdgs_train_set_option 3: False / None 0, True TRAIN_BF16X3_ALL, an int 0..7 itself
+    (1 forward products, 2 data gradients, 4 weight gradients); anything else raises."""
+    if value is None or value is False:
+        return 0
+    if value is True:
+        return TRAIN_BF16X3_ALL
+    if isinstance(value, (int, np.integer)) and 0 <= int(value) <= 7:
+        return int(value)
+    raise ValueError("train_bf16x3 = %r: expected a bool or a mask 0..7 (1 forward products, 2 data gradients, 4 weight gradients)" % (value,))
+
+
 class TrainEngineCDGS(TrainEngine):
     """The same for CDGS (csrc/cdgs_train.hip): `cfg_struct` is a jodo_cdgs_cfg, `named_shapes` lists every tensor of the state_dict
     (the GINE `local_model.eps` buffers included: inputs without a gradient), the inputs are t [B], x [B, N, atom_ch] and
     edge_x [B, N, N, edge_ch] plus the sinusoid's frequency table.  The workspace holds the reference's dense padded tensors (B N^2
     edge rows); `check_free` refuses a workspace larger than the device has free before anything is allocated.  Pool, slots and the
     pinned staging ring are TrainEngine's.  debug_fetch selectors: 0 = h after `layer` blocks [B N, nf], 1 = e after `layer` blocks
-    [B N^2, nf], 2 = alpha of block `layer` [B N^2, n_heads], 3 = xhat of its norm2_edge [B N^2, nf]."""
+    [B N^2, nf], 2 = alpha of block `layer` [B N^2, n_heads], 3 = xhat of its norm2_edge [B N^2, nf].
+
+    Option 3 (`options={3: mask}`, or `set_form(mask)` on an engine that exists — a cached one included) selects the product forms that
+    run in split-bf16 (include/jodo_hip.h; 0 = exact fp32, the default); `form` reads the mask back from the handle.  The forward and the
+    backward read it when they run; the autograd node re-sets its forward's mask before its backward."""
 
     _abi = 'jodo_cdgs_train'
+
+    def set_form(self, mask):
+        self._check(self._fn('set_option')(self.handle, 3, int(mask)), self._abi + '_set_option')
+
+    @property
+    def form(self):
+        v = ctypes.c_int(-1)
+        self._check(self._fn('get_option')(self.handle, 3, ctypes.byref(v)), self._abi + '_get_option')
+        return int(v.value)
 
     def __init__(self, *args, **kwargs):
         if kwargs.get('lib') is not None:
@@ -398,12 +427,13 @@ class _CDGSTrainFn(torch.autograd.Function):
         ts = [p.detach().contiguous() for p in tensors]
         out_x, out_e = engine.forward(ts, time_freq, t, x, edge_x, dropout_p, seed, keep=True)
         ctx.engine, ctx.dropout_p, ctx.seed, ctx.ts, ctx.x, ctx.edge_x = engine, dropout_p, seed, ts, x, edge_x
-        ctx.stamp = engine.stamp
+        ctx.stamp, ctx.form = engine.stamp, engine.form
         ctx.slot_guard = _SlotGuard(engine.pool, engine.stamp)
         return out_x, out_e
 
     @staticmethod
     def backward(ctx, d_out_x, d_out_e):
+        ctx.engine.set_form(ctx.form)                        # the forms this forward ran with, whatever the engine served since
         grads = iter(ctx.engine.backward(ctx.ts, ctx.x, ctx.edge_x, d_out_x.contiguous(), d_out_e.contiguous(), ctx.dropout_p, ctx.seed,
                                          stamp=ctx.stamp))
         return (None,) * 7 + tuple(None if buf else next(grads) for buf in ctx.engine.is_buffer)
