@@ -554,6 +554,31 @@ int jodo_dpm_update_2d(int B, int N, int node_feats, int edge_ch, const int32_t*
                        const float* coef_tab_dev, const int32_t* step_dev, int tab_stride, int tab_col, const float* x_base,
                        const float* edge_base, const float* P, const float* eP, const float* DA, const float* eDA, const float* DB,
                        const float* eDB, float* x_out, float* edge_out, void* stream);
+/* jodo_eps_to_data_2d  <- the conversion that lets DPM_Solver_2D run on a NOISE-predicting 2-D network (CDGS: pred_data = False,
+ *                         self_cond = False): DPM-Solver++ updates data predictions, so each network output eps at time t becomes
+ *                             d = (x - sigma_t * eps) / alpha_t
+ *                         first — three correctly rounded fp32 operations in exactly that order (product, difference, quotient), no
+ *                         contraction: the result equals the framework expression bit for bit.  Node tensors x / eps_x / d_x [B,N,nd]
+ *                         WITHOUT position channels, edge tensors edge_x / eps_e / d_e [B,N,N,ch]; node_feats <= 256, edge_ch <= 4.
+ *                         Coefficients: alpha and sigma by value (coef_tab_dev = step_dev = NULL), or columns tab_col + 5 and
+ *                         tab_col + 6 of row *step_dev of a device table (row stride tab_stride floats) for captured hipGraphs.  A
+ *                         noise-form table row is {a, b, c, c2, t, alpha_t, sigma_t, noise_level}: columns 0 - 3 and 7 are what
+ *                         jodo_dpm_update_2d and jodo_step_begin_at read from a data-form row; 4 - 6, unused there, hold the time and
+ *                         the marginal coefficients of the evaluation that the row's update follows.
+ *                         Read: x, eps_x on real atoms; edge_x, eps_e on cells (b, r, c) with c < r < n_b — the diagonal, the upper
+ *                         triangle and padding of the inputs are never read.  Written: every element of d_x and d_e, each by exactly
+ *                         one thread with plain stores, in ONE launch: the edge value is computed once per unordered pair and stored to
+ *                         both orientations (symmetric bit for bit); the diagonal, padded atoms and padded cells get exact zeros.
+ *                         Aliasing: d_x may be x or eps_x, and d_e may be edge_x or eps_e (in-place conversion): a thread reads only
+ *                         elements it also writes.  Partial overlap is not allowed.
+ * jodo_step_begin_t    <- t_out[b] = table[*step][tab_col + 4] for b < B, and, when noise_level_out is not NULL,
+ *                         noise_level_out[b] = table[*step][tab_col + 7]: the start of a captured evaluation of a network that reads
+ *                         the time (CDGS).  jodo_step_begin_at stays the entry of the networks that read the noise level alone. */
+int jodo_eps_to_data_2d(int B, int N, int node_feats, int edge_ch, const int32_t* n_nodes_dev, float alpha, float sigma,
+                        const float* coef_tab_dev, const int32_t* step_dev, int tab_stride, int tab_col, const float* x,
+                        const float* edge_x, const float* eps_x, const float* eps_e, float* d_x, float* d_e, void* stream);
+int jodo_step_begin_t(int B, const float* coef_tab_dev, const int32_t* step_dev, int tab_stride, int tab_col, float* t_out,
+                      float* noise_level_out, void* stream);
 /* jodo_decode_2d  <- post_process_2D sampling.py:100-141 + the inverse scaler utils.py:71-105 for xh [B,N,atom_types(+1)] without
  *                    positions: the scaler in the framework's fp32 operation order (x * norm, then (x + 1) / 2 when centred, then the
  *                    mask), atom type [B,N] u8 = first maximum, formal charge [B,N] i8 = rintf (0 when include_fc = 0), bond type

@@ -50,6 +50,14 @@ def _bind_2d_sampling(L):
     dec.argtypes = [i] * 7 + [f, f, f] + [p] * 7
     dpm.argtypes = [i, i, i, i, p, p, p, p, i, i] + [p] * 11
     step.restype = dec.restype = dpm.restype = i
+    try:                                                     # the noise-prediction form of the 2-D solver (CDGS under 'dpm_2d')
+        e2d, beg = L.jodo_eps_to_data_2d, L.jodo_step_begin_t
+    except AttributeError as e:
+        raise JodoHipError("%s lacks the noise-form exports of the 2-D solver (%s): rebuild it with python -c 'import __graft_entry__ as g; "
+                           "g.build()'" % (LIB_PATH, e))
+    e2d.argtypes = [i, i, i, i, p, f, f, p, p, i, i] + [p] * 7
+    beg.argtypes = [i, p, p, i, i, p, p, p]
+    e2d.restype = beg.restype = i
 
 
 WALK_DIRECTED, WALK_PAIR = 0, 1                 # enum jodo2d_walk

@@ -616,6 +616,113 @@ extern "C" int jodo_dpm_update_2d(int B, int N, int node_feats, int edge_ch, con
     return jodo_check_launch("k_dpm_2d");
 }
 
+// ---- noise prediction -> data prediction for the 2-D models (jodo_eps_to_data_2d): DPM_Solver_2D on a noise-predicting network (CDGS)
+// turns every network output eps into d = (x - sigma * eps) / alpha before the data-prediction update above.  (alpha, sigma) by value,
+// or columns tab_col + 5 / tab_col + 6 of row *step of a device table: the noise-form rows {a, b, c, c2, t, alpha_t, sigma_t,
+// noise_level} fill the three columns that k_dpm_2d does not read.  The index ranges, the ownership of elements and hence the aliasing
+// rule are k_dpm_2d's: a thread of the first range owns four node channels of one atom, a thread of the second one entry (r >= c) of
+// the lower triangle of one molecule, computed once from cell (b, r, c) and stored to both orientations; zeros on the diagonal and on
+// padding; every output element written by exactly one thread with plain stores; a thread reads only elements it also writes, so d_x
+// may be x or eps_x and d_e may be edge_x or eps_e (no __restrict__ on the tensors).
+namespace {
+// __fmul_rn, __fsub_rn, __fdiv_rn in that order: three operations, each rounded on its own, as the framework expression
+// (x - sigma * eps) / alpha rounds them.  Written with plain operators under contract(off), as dpm_value_2d is: the intrinsics are
+// inline functions of the runtime's headers, compiled under the default -ffp-contract=fast, and the pragma governs only the operations
+// written in THIS function — with the intrinsics the product went into the difference as one v_fma_f32.  The quotient is the
+// compiler's correctly rounded fp32 division (v_div_scale / v_div_fmas / v_div_fixup), fp32 denormals kept.
+__device__ __forceinline__ float eps_to_data(float alpha, float sigma, float x, float eps) {
+#pragma clang fp contract(off)
+    const float t0 = sigma * eps;
+    const float t1 = x - t0;
+    return t1 / alpha;
+}
+
+__global__ __launch_bounds__(256) void k_eps_to_data_2d(int B, int N, int nd, int ch, const int* __restrict__ n_nodes, float alpha,
+                                                        float sigma, const float* __restrict__ tab, const int* __restrict__ step,
+                                                        int stride, int col, const float* x, const float* e, const float* eps_x,
+                                                        const float* eps_e, float* d_x, float* d_e) {
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int nq = (nd + 3) >> 2;
+    const size_t tri = (size_t)N * (N + 1) / 2;
+    const size_t n_quad = (size_t)B * N * nq, n_tri = (size_t)B * tri;
+    if (g >= n_quad + n_tri) return;
+    if (tab) {
+        const float* r = tab + (size_t)(*step) * stride + col;
+        alpha = r[5]; sigma = r[6];
+    }
+    if (g < n_quad) {
+        const int q = (int)(g % nq);
+        const size_t atom = g / nq;
+        const int i = (int)(atom % N), b = (int)(atom / N);
+        const bool real = i < n_nodes[b];
+        const int k1 = min(4 * q + 4, nd);
+        for (int f = 4 * q; f < k1; ++f) {
+            const size_t o = atom * nd + f;
+            d_x[o] = real ? eps_to_data(alpha, sigma, x[o], eps_x[o]) : 0.f;
+        }
+    } else {
+        const size_t pg = g - n_quad;
+        const int b = (int)(pg / tri);
+        const size_t t = pg % tri;
+        // row of triangle entry t, as in k_dpm_2d: the float root corrected to the exact integer
+        int r = (int)((sqrtf(8.f * (float)t + 1.f) - 1.f) * 0.5f);
+        r = min(max(r, 0), N - 1);
+        while ((size_t)r * (r + 1) / 2 > t) --r;
+        while ((size_t)(r + 1) * (r + 2) / 2 <= t) ++r;
+        const int c = (int)(t - (size_t)r * (r + 1) / 2);
+        const size_t lo = (((size_t)b * N + r) * N + c) * ch;           // cell (b, r, c): the one that is read
+        if (r == c) {
+            for (int f = 0; f < ch; ++f) d_e[lo + f] = 0.f;
+            return;
+        }
+        const size_t up = (((size_t)b * N + c) * N + r) * ch;           // its mirror (b, c, r)
+        const bool real = r < n_nodes[b];                               // c < r
+        for (int f = 0; f < ch; ++f) {
+            const float v = real ? eps_to_data(alpha, sigma, e[lo + f], eps_e[lo + f]) : 0.f;
+            d_e[lo + f] = v;
+            d_e[up + f] = v;
+        }
+    }
+}
+
+__global__ void k_step_begin_t(int B, const float* __restrict__ tab, const int* __restrict__ step, int stride, int col,
+                               float* __restrict__ t_out, float* __restrict__ noise_level) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const float* r = tab + (size_t)(*step) * stride + col;
+    t_out[b] = r[4];
+    if (noise_level) noise_level[b] = r[7];
+}
+}  // namespace
+
+extern "C" int jodo_eps_to_data_2d(int B, int N, int node_feats, int edge_ch, const int32_t* n_nodes_dev, float alpha, float sigma,
+                                   const float* coef_tab_dev, const int32_t* step_dev, int tab_stride, int tab_col, const float* x,
+                                   const float* edge_x, const float* eps_x, const float* eps_e, float* d_x, float* d_e, void* stream) {
+    if (B <= 0 || N <= 0 || node_feats < 1 || edge_ch < 1) return jodo_set_error(JODO_ERR_ARG, "eps_to_data_2d: bad shape");
+    if (!n_nodes_dev || !x || !edge_x || !eps_x || !eps_e || !d_x || !d_e) return jodo_set_error(JODO_ERR_ARG, "eps_to_data_2d: null argument");
+    if ((coef_tab_dev == nullptr) != (step_dev == nullptr))
+        return jodo_set_error(JODO_ERR_ARG, "eps_to_data_2d: pass both the device table and the step counter, or neither");
+    if (coef_tab_dev && (tab_stride < 8 || tab_col < 0 || tab_col + 8 > tab_stride))
+        return jodo_set_error(JODO_ERR_ARG, "eps_to_data_2d: the 8 columns from tab_col do not fit a table row of tab_stride floats");
+    if (edge_ch > 4 || node_feats > 256)
+        return jodo_set_error(JODO_ERR_UNSUPPORTED, "eps_to_data_2d: at most 4 edge channels and 256 node channels");
+    const size_t tot = (size_t)B * N * ((node_feats + 3) / 4) + (size_t)B * ((size_t)N * (N + 1) / 2);
+    if ((tot + 255) / 256 > 0x7fffffffull) return jodo_set_error(JODO_ERR_UNSUPPORTED, "eps_to_data_2d: batch too large for one launch");
+    hipLaunchKernelGGL(k_eps_to_data_2d, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, B, N, node_feats, edge_ch,
+                       n_nodes_dev, alpha, sigma, coef_tab_dev, step_dev, tab_stride, tab_col, x, edge_x, eps_x, eps_e, d_x, d_e);
+    return jodo_check_launch("k_eps_to_data_2d");
+}
+
+extern "C" int jodo_step_begin_t(int B, const float* coef_tab_dev, const int32_t* step_dev, int tab_stride, int tab_col, float* t_out,
+                                 float* noise_level_out, void* stream) {
+    if (B <= 0 || !coef_tab_dev || !step_dev || !t_out) return jodo_set_error(JODO_ERR_ARG, "step_begin_t: bad argument");
+    if (tab_stride < 8 || tab_col < 0 || tab_col + 8 > tab_stride)
+        return jodo_set_error(JODO_ERR_ARG, "step_begin_t: the 8 columns from tab_col do not fit a table row of tab_stride floats");
+    hipLaunchKernelGGL(k_step_begin_t, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, B, coef_tab_dev, step_dev, tab_stride,
+                       tab_col, t_out, noise_level_out);
+    return jodo_check_launch("k_step_begin_t");
+}
+
 extern "C" int jodo_decode(int B, int N, int atom_types, int include_fc, int edge_ch, int compress_edge, int centered,
                            float pos_norm, float atom_norm, float fc_norm, float edge_norm, const int32_t* n_nodes_dev,
                            const float* xh, const float* edge_x, float* pos_out, uint8_t* atom_type_out, int8_t* fc_out,

@@ -325,3 +325,48 @@ def dpm_update_2d(solver, coef, x_base, edge_base, P, DA, DB, n_nodes_dev):
                                              capi.ptr(xo), capi.ptr(eo), capi.current_stream_ptr()), 'jodo_dpm_update_2d')
     del t
     return xo, eo
+
+
+class _DataBuffers2D:
+    """Output buffers of eps_to_data_2d: a ring of data predictions.  The solver holds at most three at a time (single-step order 3:
+    the predictions at t, s1 and s2 of one outer step; multistep order 2: the newest and the one before), so with depth 4 a conversion
+    never writes a prediction that an update still reads."""
+
+    def __init__(self, x, edge_x, depth=4):
+        new = lambda t: torch.empty(t.shape, dtype=torch.float32, device=t.device)
+        self.x = [new(x) for _ in range(depth)]
+        self.e = [new(edge_x) for _ in range(depth)]
+        self.cur = 0
+
+
+def eps_to_data_2d(solver, alpha, sigma, x, edge_x, eps_x, eps_e, n_nodes_dev, out=None):
+    """jodo_eps_to_data_2d (include/jodo_hip.h) in its host-scalar form: d = (x - sigma * eps) / alpha on the node tensor [B,N,nd] and the
+    edge tensor [B,N,N,ch], the noise prediction of a 2-D network turned into the data prediction that DPM-Solver++ updates.  alpha / sigma
+    are floats; n_nodes_dev = int32 [B] atom counts of THIS round.  The outputs come from a ring of their own on `solver` (_DataBuffers2D),
+    or are `out` = (d_x, d_e), which may be the (x, edge_x) or (eps_x, eps_e) pair itself; they are symmetric, with zero padding and
+    diagonal, whatever the inputs hold there.  Returns (d_x, d_e)."""
+    if x.dim() != 3 or edge_x.dim() != 4:
+        raise ValueError("eps_to_data_2d: node tensors are [B,N,nd], edge tensors [B,N,N,ch]")
+    B, N, nd = x.shape
+    ch = edge_x.shape[-1]
+    if edge_x.shape != (B, N, N, ch) or eps_x.shape != x.shape or eps_e.shape != edge_x.shape:
+        raise ValueError("eps_to_data_2d: shape mismatch")
+    if n_nodes_dev.shape[0] != B or n_nodes_dev.device != x.device or n_nodes_dev.dtype != torch.int32:
+        raise ValueError("eps_to_data_2d: n_nodes_dev does not belong to this batch")
+    # contiguous fp32 views stay bound to names until the launch is enqueued (see dpm_update)
+    t = [_f32c(v, n) for v, n in ((x, 'x'), (edge_x, 'edge_x'), (eps_x, 'eps_x'), (eps_e, 'eps_e'))]
+    if out is None:
+        bufs = getattr(solver, '_data_bufs', None)
+        if bufs is None or bufs.x[0].shape != x.shape or bufs.e[0].shape != edge_x.shape or bufs.x[0].device != x.device:
+            bufs = solver._data_bufs = _DataBuffers2D(x, edge_x)
+        bufs.cur = (bufs.cur + 1) % len(bufs.x)
+        dx, de = bufs.x[bufs.cur], bufs.e[bufs.cur]
+    else:
+        dx, de = out
+        if dx.shape != x.shape or de.shape != edge_x.shape or _f32c(dx, 'd_x') is not dx or _f32c(de, 'd_e') is not de:
+            raise ValueError("eps_to_data_2d: out = (d_x, d_e), contiguous float32 GPU tensors of the inputs' shapes")
+    capi.check(capi.lib().jodo_eps_to_data_2d(B, N, nd, ch, capi.ptr(n_nodes_dev), float(alpha), float(sigma), None, None, 0, 0,
+                                              *[capi.ptr(v) for v in t], capi.ptr(dx), capi.ptr(de), capi.current_stream_ptr()),
+               'jodo_eps_to_data_2d')
+    del t
+    return dx, de

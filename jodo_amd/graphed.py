@@ -386,7 +386,17 @@ class GraphedDPMRound2D:
     7) indexed by a device step counter.  The first step (no self-conditioning input yet: another kernel path) runs eagerly through the
     solver's own methods, one warm-up step runs on a side stream, the rest is replay.  Nothing is drawn, so there is no noise option, and
     a replayed round ends in the very state of the eager DPM_Solver_2D.sampling: same kernels, same coefficients.  Other variants raise
-    NotImplementedError, as GraphedDPMRound does."""
+    NotImplementedError, as GraphedDPMRound does.
+
+    Noise form (solver.noise_form: a noise-predicting network without self-conditioning, CDGS): the same two variants.  A table row is
+    {a, b, c, c2, t, alpha_t, sigma_t, noise level}; an evaluation is jodo_step_begin_t (the network reads the TIME, column 4), the
+    forward, and jodo_eps_to_data_2d in its table form (columns 5, 6) into a static prediction buffer.
+      single-step, order 2   fetch, forward, convert into d0, update to x1; fetch, forward on x1, convert into d1, update in place with
+                             P = DB = d0, DA = d1; jodo_step_end.
+      multistep, order 2     fetch, forward, convert into d, update in place with DB = the previous prediction, which lives in a
+                             static buffer of its own (there are no self-conditioning buffers), hand-over copy, jodo_step_end.
+    The eager first step also packs whatever the network derives from its weights (the bf16x3 tape of CDGS), so the captured step
+    finds it."""
 
     @staticmethod
     def supports(solver):
@@ -399,7 +409,12 @@ class GraphedDPMRound2D:
         self.node_mask, self.edge_mask, self.context = node_mask, edge_mask, context
         self.single = solver.method == 'singlestep_fixed'
         ns = solver.noise_schedule
-        row = lambda a, b, c, c2, t: torch.tensor([float(a), float(b), float(c), float(c2), 0.0, 0.0, 0.0, float(ns.get_noiseLevel(t))])
+        self.noise_form = bool(getattr(solver, 'noise_form', False))
+        if self.noise_form:
+            row = lambda a, b, c, c2, t: torch.tensor([float(a), float(b), float(c), float(c2), float(t)]
+                                                      + [float(v) for v in solver.marginal_coefficients(t)] + [float(ns.get_noiseLevel(t))])
+        else:
+            row = lambda a, b, c, c2, t: torch.tensor([float(a), float(b), float(c), float(c2), 0.0, 0.0, 0.0, float(ns.get_noiseLevel(t))])
         if self.single:
             K = solver.steps // 2
             outer = solver.get_time_steps('time_uniform', ns.T, 1. / ns.total_N, K, 'cpu')
@@ -438,9 +453,31 @@ class GraphedDPMRound2D:
                                                  capi.ptr(self.step), self.tab.shape[1], col, *tens, capi.current_stream_ptr()),
                    'jodo_dpm_update_2d')
 
+    def _eval_noise(self, col, x, e, d):
+        """One evaluation of the noise form at the time of table columns `col`..: d = (d_x, d_e) receives the data prediction."""
+        L, B = capi.lib(), self.x.shape[0]
+        st = capi.current_stream_ptr()
+        capi.check(L.jodo_step_begin_t(B, capi.ptr(self.tab), capi.ptr(self.step), self.tab.shape[1], col, capi.ptr(self.t), capi.ptr(self.nl),
+                                       st), 'jodo_step_begin_t')
+        eps = self.model(self.t, x, self.node_mask, self.edge_mask, edge_x=e, noise_level=self.nl, context=self.context)
+        eps_x, eps_e = fused._f32c(eps[0], 'eps_x'), fused._f32c(eps[1], 'eps_e')      # bound to names until the launch is enqueued
+        capi.check(L.jodo_eps_to_data_2d(B, self.x.shape[1], self.x.shape[2], self.e.shape[-1], capi.ptr(self.n_nodes), 0.0, 0.0,
+                                         capi.ptr(self.tab), capi.ptr(self.step), self.tab.shape[1], col, capi.ptr(x), capi.ptr(e),
+                                         capi.ptr(eps_x), capi.ptr(eps_e), capi.ptr(d[0]), capi.ptr(d[1]), st), 'jodo_eps_to_data_2d')
+        return d
+
     def _step(self):
         """One captured unit on the static buffers; identical code runs eagerly (warm-up) and under capture."""
-        if self.single:
+        if self.noise_form and self.single:
+            d0 = self._eval_noise(0, self.x, self.e, self.d0)
+            self._up(0, d0, d0, d0, self.x1, self.e1)
+            d1 = self._eval_noise(8, self.x1, self.e1, self.d1)
+            self._up(8, d0, d1, d0, self.x, self.e)            # in place: the state is the update's base
+        elif self.noise_form:
+            p = self._eval_noise(0, self.x, self.e, self.d0)
+            self._up(0, p, p, self.prev, self.x, self.e)       # in place; DB = the previous prediction
+            self.prev[0].copy_(p[0]); self.prev[1].copy_(p[1])  # handed over to the next step
+        elif self.single:
             p0 = self._eval(0, self.x, self.e)
             self.cx.copy_(p0[0]); self.cex.copy_(p0[1])        # self-conditioning input of the next evaluation
             c0 = (self.cx, self.cex)
@@ -484,7 +521,16 @@ class GraphedDPMRound2D:
         if self.K > 1:
             new = lambda t: torch.empty(t.shape, dtype=torch.float32, device=dev)
             self.x, self.e = x.contiguous().clone(), edge_x.contiguous().clone()
-            self.cx, self.cex = sv.cond_x.contiguous().clone(), sv.cond_edge_x.contiguous().clone()
+            if self.noise_form:                              # static prediction buffers; nothing is self-conditioned
+                self.cx = self.cex = None
+                self.d0 = (new(self.x), new(self.e))
+                if self.single:
+                    self.d1 = (new(self.x), new(self.e))
+                else:
+                    self.prev = (m0[0].contiguous().clone(), m0[1].contiguous().clone())
+                self.t = torch.empty(self.x.shape[0], device=dev)
+            else:
+                self.cx, self.cex = sv.cond_x.contiguous().clone(), sv.cond_edge_x.contiguous().clone()
             if self.single:
                 self.x1, self.e1 = new(self.x), new(self.e)
             self.nl = torch.empty(self.x.shape[0], device=dev)

@@ -327,7 +327,15 @@ class DPM_Solver_2D(DPM_Solver_hybrid):
     `steps` = NFE.  The 2-D configs carry neither `sampling.dpm_solver_method` nor `sampling.dpm_solver_order` (like the reference's):
     they default to 'singlestep_fixed' and 2.  Methods: 'singlestep_fixed' at orders 1 - 3, 'multistep' at order 2 (order-1 warm-up).
     fused=True: on GPU tensors an update is one kernel (jodo_dpm_update_2d); CPU tensors take the op-by-op path (host tests with a
-    CPU model).  `sampling` returns clones, as the 3-D class does."""
+    CPU model).  `sampling` returns clones, as the 3-D class does.
+
+    Two model kinds are taken: (pred_data, self_cond) = (True, True), the data form described above, and (False, False), the noise
+    form (CDGS).  In the noise form an evaluation calls the network with the time and the noise level and no self-conditioning input,
+    carries nothing to the next evaluation, and turns the output eps into the data prediction d = (x - sigma_t * eps) / alpha_t with
+    alpha_t = exp(marginal_log_mean_coeff(t)), sigma_t = marginal_std(t) — the schedule calls the update coefficients are made of
+    (jodo_eps_to_data_2d on GPU tensors, the same three operations per element otherwise).  Everything after that is the data form's
+    code.  The conversion divides by alpha_t, about 1 / 150 at t = T under the linear schedule: the network's error is amplified by
+    that much in d, and the update's b = alpha_end * expm1(-h) brings it back.  The mixed kinds are refused."""
 
     def __init__(self, noise_schedule, config, fused=True):
         self.noise_schedule = noise_schedule
@@ -342,8 +350,11 @@ class DPM_Solver_2D(DPM_Solver_hybrid):
         self.steps = config.sampling.steps
         self.method = getattr(config.sampling, 'dpm_solver_method', 'singlestep_fixed')
         self.fused = fused
-        assert config.model.pred_data, "Not support in current version."
-        assert config.model.self_cond, "Not support in current version."
+        # (pred_data, self_cond) = (True, True): the data form; (False, False): the noise form (CDGS).  The mixed ones stay refused.
+        self.noise_form = not config.model.pred_data and not config.model.self_cond
+        if not self.noise_form:
+            assert config.model.pred_data, "Not support in current version."
+            assert config.model.self_cond, "Not support in current version."
         if self.method == 'singlestep_fixed':
             if self.order not in (1, 2, 3) or self.steps < self.order:
                 raise ValueError("DPM_Solver_2D: singlestep_fixed takes dpm_solver_order 1, 2 or 3 and steps >= order")
@@ -355,6 +366,37 @@ class DPM_Solver_2D(DPM_Solver_hybrid):
 
     def noise_draws_per_round(self):
         return 0
+
+    # -- the noise form: every evaluation is a noise prediction turned into a data prediction -------------------------------------
+    def marginal_coefficients(self, t):
+        """(alpha_t, sigma_t) of the conversion, by the schedule calls that the update coefficients are made of."""
+        ns = self.noise_schedule
+        return torch.exp(ns.marginal_log_mean_coeff(t)), ns.marginal_std(t)
+
+    def get_model_fn(self, model):
+        if not self.noise_form:
+            return super().get_model_fn(model)
+
+        def model_fn(x, node_mask, edge_mask, edge_x, context, vec_t, noise_level):
+            # no self-conditioning input, and nothing is carried from one evaluation to the next
+            return model(vec_t, x, node_mask, edge_mask, edge_x=edge_x, noise_level=noise_level, context=context)
+        return model_fn
+
+    def _predict(self, model_fn, x, node_mask, edge_mask, edge_x, context, t):
+        """Data form: the base class's evaluation.  Noise form: the network's eps at (x, t) as d = (x - sigma_t * eps) / alpha_t, one
+        kernel on GPU tensors (jodo_eps_to_data_2d, into buffers of its own), the framework expression otherwise; the op order is the
+        same in both paths."""
+        pred = super()._predict(model_fn, x, node_mask, edge_mask, edge_x, context, t)
+        if not self.noise_form:
+            return pred
+        eps_x, eps_e = pred
+        alpha_t, sigma_t = self.marginal_coefficients(t)
+        if self.fused and x.is_cuda:
+            from . import fused
+            if self._n_nodes_dev is None or self._n_nodes_dev.shape[0] != x.shape[0]:
+                self._n_nodes_dev = fused.n_nodes_from_mask(node_mask)      # direct callers of the update methods
+            return fused.eps_to_data_2d(self, float(alpha_t), float(sigma_t), x, edge_x, eps_x, eps_e, self._n_nodes_dev)
+        return (x - sigma_t * eps_x) / alpha_t, (edge_x - sigma_t * eps_e) / alpha_t
 
     def _update(self, x_pos, x_base, edge_base, P, DA, DB, PP, node_mask, t_from, t_to, last_step, a, b, c=None, c2=None):
         """a * base - b * P - c * (c2 * (DA - DB)) on the node tensor and the edge tensor; x_pos / PP / the times / last_step belong to

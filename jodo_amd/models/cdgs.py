@@ -6,7 +6,9 @@ Same constructor argument, parameter names / shapes / registration order (one `a
     model(t, x, node_mask, edge_mask, context=None, edge_x=...) -> (atom_score [B,N,atom_types], bond_score [B,N,N,edge_ch])
 The arithmetic runs in libjodo_hip.so (csrc/cdgs_forward.hip, `jodo_cdgs_forward`) on the current HIP stream: the weights are packed
 once (csrc/cdgs_pack.cpp), a descriptor and a workspace are built per batch of atom counts.  Exact fp32 by default; there is no CPU or
-eager fallback and no graph replay, and the 3-D models' `split_bf16` switch is not taken by this model — those raise.
+eager fallback, and the 3-D models' `split_bf16` switch is not taken by this model — those raise.  The forward can be captured into a
+HIP graph once an eager call has built the batch's plan and packed the weights (GraphedDPMRound2D does, for sampling.method 'dpm_2d');
+the ancestral round has no graph replay.
 
 `model.bf16x3 = True` (opt-in, runtime state, read per call) selects the three-term bf16 form of every row GEMM over node rows and edge
 rows (`jodo_cdgs_forward_split`, kernel kc_gemm_s) from a weight tape derived from the packed blob; the time-embedding GEMMs, GINE,

@@ -25,6 +25,10 @@ step inside jodo_sampler_step_2d_rng), `hip_graph=True` (GraphedAncestralRound2D
 `sampling.steps` = NFE, `sampling.dpm_solver_method` / `dpm_solver_order` default to 'singlestep_fixed' / 2) in place of the ancestral
 sampler, everything around it unchanged; with `hip_graph=True` GraphedDPMRound2D.  `method='fast'` keeps naming the hybrid solver with
 its position part and raises on a 2-D config: the reference's 'fast' would treat the first three atom channels as coordinates.
+'dpm_2d' takes both kinds of 2-D model: the self-conditioned data-predicting one (DGT_concat_2D) and the noise-predicting one without
+self-conditioning (CDGS: every output eps becomes x0 = (x - sigma_t eps) / alpha_t before the update, jodo_eps_to_data_2d), with the
+same round options for both.  The ancestral sampler of a noise-predicting model stays on the framework expression and has no graph
+replay.
 """
 import random
 
@@ -236,7 +240,8 @@ def get_sampling_fn(config, noise_scheduler, nodes_dist, batch_size, n_samples, 
     it is this rank's.  The same needs and refusals as stability=.
 
     config.sampling.method: 'ancestral' (both kinds of model), 'fast' (the hybrid DPM-Solver++ of the 3-D + edge models; raises on a
-    2-D config) or 'dpm_2d' (2-D configs only: DPM-Solver++ without a position part, see _get_sampling_fn_2d; sampling.steps = NFE)."""
+    2-D config) or 'dpm_2d' (2-D configs only, DGT_concat_2D and CDGS alike: DPM-Solver++ without a position part, see
+    _get_sampling_fn_2d; sampling.steps = NFE)."""
     device = config.device
     steps = config.sampling.steps
     atom_types = config.data.atom_types
@@ -461,7 +466,12 @@ def _get_sampling_fn_2d(config, noise_scheduler, nodes_dist, batch_size, n_sampl
     (cpu_noise included), sharding, seeding and the decode are the code above.  The solver draws nothing after the initial state: a
     'parity' rank with an empty share of a round consumes the initial draw only, device_noise has no effect (accepted and ignored; True on
     a CPU device still raises) and hip_graph=True (GraphedDPMRound2D: single-step order 2 and multistep order 2) goes with any noise
-    option."""
+    option.  Both kinds of 2-D model are taken — (pred_data, self_cond) = (True, True) and (False, False), the latter CDGS in the
+    solver's noise form — with every option above: cpu_noise, shard in both modes (parity shares of a model that declares
+    `depends_on_padded_width` are padded to the round's width), shard_assign, seed, fused_decode, return_raw, the single-device
+    DataParallel wrapper, and hip_graph=True for the two supported variants (others raise NotImplementedError).  hip_graph=True with
+    the ANCESTRAL sampler of a noise-predicting model keeps raising NotImplementedError: graph replay of such a model exists for
+    'dpm_2d' only."""
     if config.sampling.method == 'fast':
         raise NotImplementedError("sampling.method='fast' (the hybrid DPM-solver with a position part) is not implemented for the 2-D "
                                   "sampling path; sampling.method='dpm_2d' is the DPM-solver for 2-D graphs")

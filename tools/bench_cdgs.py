@@ -21,6 +21,13 @@ one shared warm-up of both forms), and writes cdgs_<workload>_b<B>_split.json: e
 per form the run-to-run spread (max - min of its legs) - a difference between the forms counts only beyond that spread.  No dense leg in
 these modes.  With `both`, --kernel-stats / --kernel-stats-exact take the kernel tables of profiled `--split on` / `--split off
 --no-baseline` runs of the same workload, batch, steps and warm-up.
+--round --nfe N [--graph] [--split off|on|both] [--repeats R]: complete DPM-Solver++ rounds (sampling.method 'dpm_2d', N network
+evaluations, the solver's default single-step order 2) of the same histogram batch at every size of --batches: DPM_Solver_2D.sampling
+("eager") and, with --graph, GraphedDPMRound2D.run ("replayed": one capture per round, as the public entry does it), each timed
+max(R, 2) times in this one process with the forms alternating, after one untimed round of each.  The ancestral step (--steps /
+--warmup, as above) is timed in the same command on the same batch.  Writes profiles/cdgs_dpm_round_<workload>_nfe<N>.json: per batch
+and per weight form seconds per round of every leg, their mean and spread (max - min), ms per evaluation (round / N), the ancestral
+ms/step, and the 1000-step ancestral round as step time x 1000 (labelled: it is not run).
 """
 import argparse
 import csv
@@ -128,6 +135,55 @@ def split_record(args, model, sampler, z, edge_z, nm, em, base):
     return out
 
 
+def time_round(run, z, edge_z):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    with torch.no_grad():
+        x, e = run(z, edge_z)
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, bool(torch.isfinite(x).all() and torch.isfinite(e).all()), (x, e)
+
+
+def round_record(args, cfg, model, ns, sampler, z, edge_z, nm, em):
+    """--round: the legs of one batch, per weight form; returns {weight form: record}"""
+    from jodo_amd.graphed import GraphedDPMRound2D
+    from jodo_amd.mix_dpm_solver import DPM_Solver_2D
+    cfg_r = configs.get(WORKLOADS[args.workload])
+    cfg_r.sampling.method, cfg_r.sampling.steps = 'dpm_2d', args.nfe
+    solver = DPM_Solver_2D(ns, cfg_r)
+    runs = {'eager': lambda a, b: solver.sampling(model, a, nm, em, b, None)}
+    if args.graph:
+        runs['replayed'] = lambda a, b: GraphedDPMRound2D(solver, model, nm, em).run(a, b)
+    repeats, out = max(args.repeats, 2), {}
+    for form in {'off': ['exact'], 'on': ['split'], 'both': ['exact', 'split']}[args.split]:
+        model.bf16x3 = form == 'split'
+        anc_ms, _ = time_steps(sampler, model, z, edge_z, nm, em, args.warmup, args.steps)
+        ends = {k: time_round(run, z, edge_z)[2] for k, run in runs.items()}            # one untimed round of each
+        legs, finite = {k: [] for k in runs}, True
+        for _ in range(repeats):
+            for k, run in runs.items():                                                  # eager, replayed, eager, replayed, ...
+                sec, ok, _ = time_round(run, z, edge_z)
+                legs[k].append(round(sec, 4))
+                finite = finite and ok
+        rec = dict(split_form_ran=None if model.last_flags is None else int(model.last_flags[3].item()), finite=finite,
+                   ancestral_ms_per_step=round(anc_ms, 3), ancestral_steps_timed=args.steps,
+                   ancestral_1000_step_round_s_as_step_time_x_1000_not_run=round(anc_ms, 3))
+        for k in runs:
+            mean = sum(legs[k]) / len(legs[k])
+            rec.update({k + '_s_per_round_legs': legs[k], k + '_s_per_round': round(mean, 4),
+                        k + '_spread_s': round(max(legs[k]) - min(legs[k]), 4), k + '_ms_per_evaluation': round(mean / args.nfe * 1e3, 3),
+                        k + '_ms_per_evaluation_over_ancestral_step': round(mean / args.nfe * 1e3 / anc_ms, 4)})
+        if args.graph:
+            spread = max(rec['eager_spread_s'], rec['replayed_spread_s'])
+            rec.update(replayed_over_eager_time=round(rec['replayed_s_per_round'] / rec['eager_s_per_round'], 4), spread_s=spread,
+                       replay_faster_beyond_spread=bool(rec['eager_s_per_round'] - rec['replayed_s_per_round'] > spread),
+                       replayed_equals_eager=bool(torch.equal(ends['eager'][0], ends['replayed'][0])
+                                                  and torch.equal(ends['eager'][1], ends['replayed'][1])))
+        out[form] = rec
+    model.bf16x3 = False
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--workload', default='qm9', choices=sorted(WORKLOADS))
@@ -141,6 +197,9 @@ def main():
     ap.add_argument('--split', default='off', choices=['off', 'on', 'both'], help='the opt-in split-bf16 form (model.bf16x3)')
     ap.add_argument('--repeats', type=int, default=3, help='--split on | both: timed legs per form')
     ap.add_argument('--kernel-stats-exact', default=None, help='--split both: kernel-stats CSV of the exact form\'s profiled run')
+    ap.add_argument('--round', action='store_true', help="complete 'dpm_2d' rounds instead of single ancestral steps")
+    ap.add_argument('--nfe', type=int, default=50, help='--round: network evaluations per round')
+    ap.add_argument('--graph', action='store_true', help='--round: also time the replayed form (GraphedDPMRound2D)')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     cfg = configs.get(WORKLOADS[args.workload])
@@ -151,6 +210,9 @@ def main():
     sampler = AncestralSampler_2D(ns, torch.linspace(ns.T, 1e-3, cfg.sampling.steps), cfg.model.pred_data, cfg.model.self_cond)
     dist = get_node_dist(load_dataset_info(cfg.data.info_name))
     batches = [int(b) for b in args.batches.split(',')]
+    rounds = dict(tool='tools/bench_cdgs.py', workload=args.workload, config=WORKLOADS[args.workload], method='dpm_2d',
+                  solver='singlestep_fixed order 2', nfe=args.nfe, repeats=max(args.repeats, 2), graph=bool(args.graph), split=args.split,
+                  batches={})
     for B in batches:
         torch.manual_seed(42)
         n_nodes = dist.sample(B).tolist()
@@ -160,6 +222,17 @@ def main():
         edge_z = sample_symmetric_edge_feature_noise(B, N, cfg.model.edge_ch, em)
         pairs = sum(n * (n - 1) for n in n_nodes)
         flops, pair_flops = flops_per_step(model, n_nodes)
+        if args.round:
+            rec = dict(batch=B, padded_width=N, atoms=sum(n_nodes), ordered_pairs=pairs)
+            rec.update(round_record(args, cfg, model, ns, sampler, z, edge_z, nm, em))
+            rounds['batches'][str(B)] = rec
+            os.makedirs(args.out_dir, exist_ok=True)
+            with open(os.path.join(args.out_dir, 'cdgs_dpm_round_%s_nfe%d.json' % (args.workload, args.nfe)), 'w') as f:
+                json.dump(rounds, f, indent=1)
+            print(json.dumps(rec), flush=True)
+            del z, edge_z
+            torch.cuda.empty_cache()
+            continue
         if args.split != 'off':
             base = dict(tool='tools/bench_cdgs.py', workload=args.workload, config=WORKLOADS[args.workload], batch=B, padded_width=N,
                         atoms=sum(n_nodes), ordered_pairs=pairs, edge_rows_executed=sum(n * n for n in n_nodes), steps=args.steps,
