@@ -579,6 +579,34 @@ int jodo_eps_to_data_2d(int B, int N, int node_feats, int edge_ch, const int32_t
                         const float* edge_x, const float* eps_x, const float* eps_e, float* d_x, float* d_e, void* stream);
 int jodo_step_begin_t(int B, const float* coef_tab_dev, const int32_t* step_dev, int tab_stride, int tab_col, float* t_out,
                       float* noise_level_out, void* stream);
+/* jodo_prop_sample  <- the conditioning targets of a round, drawn on the device from the property prior (DistributionProperty,
+ *                      jodo_amd/cond_gen/property_distribution.py; the reference's cond_gen/property_distribution.py draws them one
+ *                      molecule and property at a time on the host): out[b, p] = one draw of property p for molecule b, normalised.
+ *                      ONE launch, one thread per (molecule, property); no atomics, no LDS, no scratch.  A value depends only on
+ *                      (seed, global index of the molecule, property column, the tables): not on B, the batch's composition or order.
+ *   Tables (device): cum     uint32 [n_prop, n_slots, n_bins]  inclusive cumulative integer weights of the bins; the total T of a row
+ *                                                              (its last entry) satisfies 0 < T < 2^31
+ *                    minmax  f32    [n_prop, n_slots, 2]       (min, max) of the property at the slot's atom count
+ *                    norm    f32    [n_prop, 2]                (mean, mad) of the property; (0, 1) = no normalisation
+ *   Per molecule:    slot[b] in [0, n_slots): the table slot of its atom count (slots_host: the same B values on the host, checked
+ *                    here before anything is launched; slots_dev: their device copy, which the kernel reads);
+ *                    global index g = indices_dev[b] (device int64 [B]) when indices_dev is not NULL, else first_index + b.
+ *   Draw:   w = philox4x32_10(counter (g lo, g hi, p, 3), key (seed lo, seed hi))   -- stream 3 beside the sampler's 0 / 1 / 2
+ *           a = w[0] >> 8,  u2 = (w[1] >> 8) * 2^-24
+ *           (words_dev not NULL, uint32 [B, n_prop, 2]: w[0], w[1] are read from it and Philox is skipped -- tests put a draw
+ *           exactly on a bin boundary this way)
+ *   Bin:    r = (uint64(a) * T) >> 24;  idx = the smallest bin with cum[idx] > r (binary search): a bin of weight 0 is never chosen,
+ *           a = 0 gives the first bin of non-zero weight and a = 2^24 - 1 the last
+ *   Value:  the reference's _idx2value with u2 for torch.rand, every fp32 operation rounded on its own (no contraction):
+ *           left = fl32(idx / n_bins) * (max - min) + min;  right = fl32((idx + 1) / n_bins) * (max - min) + min
+ *           val = u2 * (right - left) + left;  out = (val - mean) / mad   (a correctly rounded division)
+ *   Errors, all before any launch: B < 1, n_prop < 1, n_bins < 1, n_slots < 1, a null table / slots / out pointer, a slot outside
+ *           [0, n_slots) -> JODO_ERR_ARG; n_prop > 16 or n_bins > 65536 -> JODO_ERR_UNSUPPORTED. */
+#define JODO_PROP_MAX_PROPS 16
+#define JODO_PROP_MAX_BINS 65536
+int jodo_prop_sample(int B, int n_prop, int n_bins, int n_slots, const uint32_t* cum_dev, const float* minmax_dev, const float* norm_dev,
+                     const int32_t* slots_host, const int32_t* slots_dev, const int64_t* indices_dev, uint64_t first_index, uint64_t seed,
+                     const uint32_t* words_dev, float* out, void* stream);
 /* jodo_decode_2d  <- post_process_2D sampling.py:100-141 + the inverse scaler utils.py:71-105 for xh [B,N,atom_types(+1)] without
  *                    positions: the scaler in the framework's fp32 operation order (x * norm, then (x + 1) / 2 when centred, then the
  *                    mask), atom type [B,N] u8 = first maximum, formal charge [B,N] i8 = rintf (0 when include_fc = 0), bond type

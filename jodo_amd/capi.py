@@ -34,6 +34,7 @@ def lib():
         _bind_eval(_lib)
         _bind_geometry(_lib)
         _bind_cdgs(_lib)
+        _bind_prop(_lib)
     return _lib
 
 
@@ -58,6 +59,21 @@ def _bind_2d_sampling(L):
     e2d.argtypes = [i, i, i, i, p, f, f, p, p, i, i] + [p] * 7
     beg.argtypes = [i, p, p, i, i, p, p, p]
     e2d.restype = beg.restype = i
+
+
+PROP_MAX_PROPS, PROP_MAX_BINS = 16, 65536       # JODO_PROP_MAX_PROPS, JODO_PROP_MAX_BINS
+
+
+def _bind_prop(L):
+    """Argument types of the property prior's draw (jodo_prop_sample; include/jodo_hip.h)."""
+    i, p, u64 = ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64
+    try:
+        ps = L.jodo_prop_sample
+    except AttributeError as e:
+        raise JodoHipError("%s lacks the property-prior export (%s): rebuild it with python -c 'import __graft_entry__ as g; g.build()'"
+                           % (LIB_PATH, e))
+    ps.argtypes = [i, i, i, i, p, p, p, p, p, p, u64, u64, p, p, p]
+    ps.restype = i
 
 
 WALK_DIRECTED, WALK_PAIR = 0, 1                 # enum jodo2d_walk

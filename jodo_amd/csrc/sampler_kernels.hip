@@ -723,6 +723,81 @@ extern "C" int jodo_step_begin_t(int B, const float* coef_tab_dev, const int32_t
     return jodo_check_launch("k_step_begin_t");
 }
 
+// ---- the property prior's draw (jodo_prop_sample; contract in include/jodo_hip.h): one thread per (molecule, property) ------------
+// Per thread: one Philox evaluation (or two words of the test form), a binary search over one row of the cumulative table (at most
+// 17 dependent 4-byte loads: n_bins <= 65536) and the reference's bin -> value expression.  tests/prop_dist_common.py restates it.
+namespace {
+enum { RNG_PROP = 3 };
+
+// the reference's _idx2value + normalize_tensor (cond_gen/property_distribution.py:69-73, :93-98) with u2 for torch.rand.  Plain
+// operators under contract(off), as eps_to_data above: every product, sum and quotient is rounded on its own.  fl32(idx / n_bins):
+// the reference forms the quotient in double and the product rounds it to fp32; for integers below 2^24 that double rounding is
+// innocuous (53 >= 2 * 24 + 2 bits), so the correctly rounded fp32 quotient is the same number.
+__device__ __forceinline__ float prop_value(unsigned idx, int n_bins, float mn, float mx, float u2, float mean, float mad) {
+#pragma clang fp contract(off)
+    const float range = mx - mn;
+    const float fl = (float)idx / (float)n_bins;
+    const float fr = (float)(idx + 1u) / (float)n_bins;
+    const float tl = fl * range;
+    const float left = tl + mn;
+    const float tr = fr * range;
+    const float right = tr + mn;
+    const float width = right - left;
+    const float t = u2 * width;
+    const float val = t + left;
+    const float c = val - mean;
+    return c / mad;
+}
+
+__global__ __launch_bounds__(256) void k_prop_sample(int B, int n_prop, int n_bins, int n_slots, const unsigned* __restrict__ cum,
+                                                     const float* __restrict__ minmax, const float* __restrict__ norm,
+                                                     const int* __restrict__ slots, const long long* __restrict__ indices,
+                                                     unsigned long long first_index, unsigned long long seed,
+                                                     const unsigned* __restrict__ words, float* __restrict__ out) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (size_t)B * n_prop) return;
+    const int b = (int)(t / n_prop), p = (int)(t % n_prop);
+    const int slot = slots[b];
+    if (slot < 0 || slot >= n_slots) { out[t] = __int_as_float(0x7fc00000); return; }   // (the host entry has refused it already)
+    unsigned w0, w1;
+    if (words) { w0 = words[2 * t]; w1 = words[2 * t + 1]; }
+    else {
+        const unsigned long long g = indices ? (unsigned long long)indices[b] : first_index + (unsigned long long)b;
+        unsigned w[4];
+        philox4x32_10((unsigned)g, (unsigned)(g >> 32), (unsigned)p, RNG_PROP, (unsigned)seed, (unsigned)(seed >> 32), w);
+        w0 = w[0]; w1 = w[1];
+    }
+    const size_t row = (size_t)p * n_slots + slot;
+    const unsigned* c = cum + row * n_bins;
+    const unsigned T = c[n_bins - 1];
+    const unsigned r = (unsigned)(((unsigned long long)(w0 >> 8) * T) >> 24);         // r < T
+    int lo = 0, hi = n_bins - 1;                              // the smallest bin whose cumulative weight exceeds r
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (c[mid] > r) hi = mid; else lo = mid + 1;
+    }
+    const float u2 = (float)(w1 >> 8) * (1.0f / 16777216.0f);
+    out[t] = prop_value((unsigned)lo, n_bins, minmax[2 * row], minmax[2 * row + 1], u2, norm[2 * p], norm[2 * p + 1]);
+}
+}  // namespace
+
+extern "C" int jodo_prop_sample(int B, int n_prop, int n_bins, int n_slots, const uint32_t* cum_dev, const float* minmax_dev,
+                                const float* norm_dev, const int32_t* slots_host, const int32_t* slots_dev, const int64_t* indices_dev,
+                                uint64_t first_index, uint64_t seed, const uint32_t* words_dev, float* out, void* stream) {
+    if (B < 1 || n_prop < 1 || n_bins < 1 || n_slots < 1) return jodo_set_error(JODO_ERR_ARG, "prop_sample: bad shape");
+    if (!cum_dev || !minmax_dev || !norm_dev || !slots_host || !slots_dev || !out)
+        return jodo_set_error(JODO_ERR_ARG, "prop_sample: null argument");
+    if (n_prop > JODO_PROP_MAX_PROPS) return jodo_set_error(JODO_ERR_UNSUPPORTED, "prop_sample: at most 16 properties");
+    if (n_bins > JODO_PROP_MAX_BINS) return jodo_set_error(JODO_ERR_UNSUPPORTED, "prop_sample: at most 65536 bins");
+    for (int b = 0; b < B; ++b)
+        if (slots_host[b] < 0 || slots_host[b] >= n_slots) return jodo_set_error(JODO_ERR_ARG, "prop_sample: slot outside the table");
+    const size_t tot = (size_t)B * n_prop;
+    hipLaunchKernelGGL(k_prop_sample, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, B, n_prop, n_bins, n_slots,
+                       cum_dev, minmax_dev, norm_dev, slots_dev, (const long long*)indices_dev, (unsigned long long)first_index,
+                       (unsigned long long)seed, words_dev, out);
+    return jodo_check_launch("k_prop_sample");
+}
+
 extern "C" int jodo_decode(int B, int N, int atom_types, int include_fc, int edge_ch, int compress_edge, int centered,
                            float pos_norm, float atom_norm, float fc_norm, float edge_norm, const int32_t* n_nodes_dev,
                            const float* xh, const float* edge_x, float* pos_out, uint8_t* atom_type_out, int8_t* fc_out,

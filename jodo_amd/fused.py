@@ -73,6 +73,71 @@ class DeviceNoise:
         return d
 
 
+PROP_CONTEXT_TAG = 0x70726F70                                 # 'prop': sampling.py keys a run's context draws by mix64(seed, this)
+
+
+class PropTables:
+    """The property prior's tables on one device (jodo_prop_sample, include/jodo_hip.h), uploaded once from
+    DistributionProperty.host_tables(): cum int32 [P, S, K] (the kernel's uint32), minmax f32 [P, S, 2], norm f32 [P, 2].
+    `PropTables.uploads` counts the uploads of the process (tests: a second draw from an unchanged prior uploads nothing)."""
+    uploads = 0
+
+    def __init__(self, host, device):
+        cum, minmax, norm = host['cum'], host['minmax'], host['norm']
+        self.n_prop, self.n_slots, self.n_bins = (int(v) for v in cum.shape)
+        if cum.dtype != torch.int32 or minmax.shape != (self.n_prop, self.n_slots, 2) or norm.shape != (self.n_prop, 2):
+            raise ValueError("PropTables: cum int32 [P,S,K], minmax f32 [P,S,2], norm f32 [P,2]")
+        self.device = torch.device(device)
+        self.cum = cum.contiguous().to(self.device)
+        self.minmax = minmax.to(torch.float32).contiguous().to(self.device)
+        self.norm = norm.to(torch.float32).contiguous().to(self.device)
+        PropTables.uploads += 1
+
+
+def prop_sample(tables, slots, seed, first_index=0, indices=None, words=None, out=None):
+    """jodo_prop_sample: [B, n_prop] float32 conditioning targets on tables.device, one launch.  slots: CPU int32 [B] table slots (checked
+    by the host entry, then uploaded); molecule i has global index indices[i] (CPU integers [B], uploaded as int64) when given, else
+    first_index + i.  words (tests): uint32 [B, n_prop, 2] as a CPU or device int32 / int64 tensor, taken instead of Philox's first two
+    words.  out: a contiguous float32 [B, n_prop] tensor on the device to write into."""
+    if not isinstance(tables, PropTables):
+        raise TypeError("prop_sample: tables is a fused.PropTables")
+    slots = torch.as_tensor(slots)
+    if slots.is_cuda or slots.dtype != torch.int32 or slots.dim() != 1:
+        raise TypeError("prop_sample: slots is a CPU int32 [B] tensor")
+    slots = slots.contiguous()
+    B, P, dev = int(slots.shape[0]), tables.n_prop, tables.device
+    if out is None:
+        out = torch.empty(B, P, dtype=torch.float32, device=dev)
+    elif out.shape != (B, P) or out.device != dev or _f32c(out, 'out') is not out:
+        raise ValueError("prop_sample: out is a contiguous float32 [B, n_prop] tensor on the tables' device")
+    if B == 0:
+        return out
+    idx_dev = None
+    if indices is not None:
+        idx = torch.as_tensor(indices, dtype=torch.int64).reshape(-1)
+        if idx.shape[0] != B:
+            raise ValueError("prop_sample: %d indices for %d molecules" % (idx.shape[0], B))
+        idx_dev = idx.to(dev)
+    words_dev = None
+    if words is not None:
+        words = torch.as_tensor(words)
+        if tuple(words.shape) != (B, P, 2):
+            raise ValueError("prop_sample: words is [B, n_prop, 2]")
+        if words.dtype != torch.int32:                        # uint32 values held in a wider integer: keep the low 32 bits
+            w = words.to(torch.int64) & 0xFFFFFFFF
+            words = torch.where(w >= (1 << 31), w - (1 << 32), w).to(torch.int32)
+        words_dev = words.contiguous().to(dev)
+    slots_dev = slots.to(dev)
+    with torch.cuda.device(dev):
+        capi.check(capi.lib().jodo_prop_sample(
+            B, P, tables.n_bins, tables.n_slots, capi.ptr(tables.cum), capi.ptr(tables.minmax), capi.ptr(tables.norm), capi.ptr(slots),
+            capi.ptr(slots_dev), capi.ptr(idx_dev), int(first_index) & 0xFFFFFFFFFFFFFFFF, int(seed) & 0xFFFFFFFFFFFFFFFF,
+            capi.ptr(words_dev), capi.ptr(out), capi.current_stream_ptr()), 'jodo_prop_sample')
+    # slots_dev / idx_dev / words_dev were allocated and are read on the current stream: the caching allocator hands their memory out
+    # again only to work queued behind this launch
+    return out
+
+
 def split_replayed_noise(node_noise, edge_noise):
     """Recorded reference noise (node [B,N,3+nd] masked + CoM-free, edge [B,N,N,ch] symmetric + masked) as the RAW draws the
     kernels take: masking, centre-of-mass removal and lower-triangle mirroring are idempotent on them."""

@@ -12,7 +12,9 @@ Additions that do not change the reference behaviour:
   * `shard=(rank, world)` on `get_sampling_fn`: each process samples a contiguous slice of every
     round's batch (jodo_amd/dist.py gathers the results) — replaces nn.DataParallel;
   * masks are built vectorised rather than with a Python loop over the batch (:195-196);
-  * `hip_graph=True` on `get_sampling_fn`: the ancestral loop replays one captured HIP graph per step.
+  * `hip_graph=True` on `get_sampling_fn`: the ancestral loop replays one captured HIP graph per step;
+  * `device_context=True` on `get_sampling_fn` (3-D path): a round's conditioning targets are drawn from the property prior by one
+    kernel (jodo_prop_sample) instead of the reference's per-molecule host draws.
 
 The 2-D experiments (`config.only_2D`, model DGT_concat_2D): `AncestralSampler_2D` (:599-660), `post_process_2D` (:100-141),
 `mol_process_2D` (:35-50) and the 2-D sampling function of `get_sampling_fn` (:234-276), with the reference's RNG use.  The
@@ -203,7 +205,8 @@ class _ParityNoise2D(_ParityNoise):
 
 def get_sampling_fn(config, noise_scheduler, nodes_dist, batch_size, n_samples, inverse_scaler, eps=1e-3,
                     prop_dist=None, shard=None, return_raw=False, fused_decode=True, hip_graph=False,
-                    shard_mode='perf', shard_assign='contiguous', seed=None, device_noise=None, cpu_noise=False, stability=None, geometry=None):
+                    shard_mode='perf', shard_assign='contiguous', seed=None, device_noise=None, cpu_noise=False, stability=None, geometry=None,
+                    device_context=None):
     """sampling.py:148-232.  Without `shard` this is the reference's procedure, RNG use included.
 
     shard=(rank, world) — one process per GPU (replaces nn.DataParallel).  Seeding contract: every rank passes the SAME
@@ -238,6 +241,20 @@ def get_sampling_fn(config, noise_scheduler, nodes_dist, batch_size, n_samples, 
     the decode's device tensors, and `sampling_fn.last_geometry` holds its result over this call's rounds ('values': per symbol one
     device f32 tensor, the rounds concatenated; 'counts', 'dropped', 'n_mols' summed) — what sub_geometry_metric takes.  With `shard`
     it is this rank's.  The same needs and refusals as stability=.
+
+    device_context — where a round's conditioning targets come from (3-D path, with a prop_dist).  Off: prop_dist.sample_batch(n_nodes),
+    the reference's host draw on torch's generator (one multinomial and one rand per molecule and property).  On: one kernel per round,
+    prop_dist.sample_batch_device(n_nodes, device, seed=mix64(seed, fused.PROP_CONTEXT_TAG), indices=<global indices of the round's
+    molecules>) (jodo_amd.cond_gen.DistributionProperty, jodo_prop_sample): a molecule's targets depend only on (seed, its global index,
+    its atom count, the prior), so every world size and either shard_assign give each global index the targets of the unsharded
+    device_context=True run, and a perf-sharded rank draws its own molecules only instead of all rounds * batch_size on the host.  True
+    needs a GPU config.device and a prior with sample_batch_device, and is refused with shard_mode='parity' (which replays the reference's
+    host draws); anything else raises ValueError naming the reason.  None (default): on exactly when shard is given with
+    shard_mode='perf', the prior has the method and config.device is a GPU; off otherwise — an unsharded or parity run with any prior
+    consumes torch's generator like the reference.  `sampling_fn.last_context` holds, for every round this process ran in the last
+    call, the context tensor it ran with (None without a prior), on or off: concatenated, its rows are the molecules of `last_indices`
+    in that order.  Under `shard` the entries are this rank's shares, and in shard_mode='parity' a round of which the rank has no molecule
+    adds no entry, so the list can be shorter than the number of rounds.  `sampling_fn.device_context` tells how the default resolved.
 
     config.sampling.method: 'ancestral' (both kinds of model), 'fast' (the hybrid DPM-Solver++ of the 3-D + edge models; raises on a
     2-D config) or 'dpm_2d' (2-D configs only, DGT_concat_2D and CDGS alike: DPM-Solver++ without a position part, see
@@ -287,8 +304,34 @@ def get_sampling_fn(config, noise_scheduler, nodes_dist, batch_size, n_samples, 
 
     if device_noise is None:
         device_noise = shard is not None and shard_mode == 'perf'
+    on_gpu = torch.device(device).type == 'cuda'
+    has_device_prior = prop_dist is not None and hasattr(prop_dist, 'sample_batch_device')
+    if device_context is None:
+        device_context = shard is not None and shard_mode == 'perf' and has_device_prior and on_gpu
+    elif device_context:
+        if prop_dist is None:
+            raise ValueError("device_context=True needs a prop_dist: there is no prior to draw the context from")
+        if not has_device_prior:
+            raise ValueError("device_context=True needs a prior with sample_batch_device (jodo_amd.cond_gen.DistributionProperty); %s has "
+                             "none" % type(prop_dist).__name__)
+        if not on_gpu:
+            raise ValueError("device_context=True draws the context on a GPU: config.device is %s and there is no CPU fallback" % (device,))
+        if shard is not None and shard_mode == 'parity':
+            raise ValueError("device_context=True does not go with shard_mode='parity', which replays the reference's host draws")
+    device_context = bool(device_context)
     rounds = int(np.ceil(n_samples / batch_size))
     round_counter = [0]
+    contexts = []                # the context tensor of every round of the current call (None without a prior)
+
+    def round_context(n_nodes, indices):
+        """The round's [B, cond_ch] context on `device`: the device draw keyed by the molecules' global indices, or the reference's."""
+        if prop_dist is None:
+            return None
+        if device_context:
+            from .fused import PROP_CONTEXT_TAG, mix64
+            base = int(config.seed if seed is None else seed)
+            return prop_dist.sample_batch_device(n_nodes, device, seed=mix64(base, PROP_CONTEXT_TAG), indices=indices)
+        return prop_dist.sample_batch(n_nodes).to(device)
     if config.sampling.method == 'ancestral':
         # schedule scalars are computed on the host: the VP coefficients near t -> 0 are ill-conditioned
         # in fp32 (sigma_s = sqrt(1 - exp(2 log alpha_s)) with log alpha_s ~ 1e-7), so their low bits depend
@@ -305,6 +348,7 @@ def get_sampling_fn(config, noise_scheduler, nodes_dist, batch_size, n_samples, 
         """n_nodes molecules (this process's share of a round) -> list of decoded molecule tuples."""
         bs = len(n_nodes)
         max_n = int(max(n_nodes))
+        contexts.append(context)
         node_mask, edge_mask = build_masks(n_nodes, max_n, device)
         if noise is None:
             z = sample_combined_position_feature_noise(bs, max_n, node_nf, node_mask)
@@ -376,6 +420,8 @@ def get_sampling_fn(config, noise_scheduler, nodes_dist, batch_size, n_samples, 
         mols = []
         del decoded_rounds[:]
         sampling_fn.last_decoded = decoded_rounds
+        del contexts[:]
+        sampling_fn.last_context = contexts
         if stability is not None:
             from .evaluation import COUNT_KEYS
             stability_totals.clear()
@@ -390,7 +436,7 @@ def get_sampling_fn(config, noise_scheduler, nodes_dist, batch_size, n_samples, 
                 n_nodes_all = nodes_dist.sample(total)
                 for r in range(rounds):
                     n_nodes = n_nodes_all[r * batch_size:(r + 1) * batch_size]
-                    context = prop_dist.sample_batch(n_nodes).to(device) if prop_dist is not None else None
+                    context = round_context(n_nodes, range(r * batch_size, (r + 1) * batch_size))
                     mols += one_round(model, n_nodes, context)
                     print('Generate {}, Total {}.'.format(len(mols), n_samples))
                 sampling_fn.last_indices = list(range(total))
@@ -404,7 +450,9 @@ def get_sampling_fn(config, noise_scheduler, nodes_dist, batch_size, n_samples, 
             torch.manual_seed(base)                            # identical on every rank
             n_nodes_all = nodes_dist.sample(total)
             if shard_mode == 'perf':
-                context_all = prop_dist.sample_batch(n_nodes_all) if prop_dist is not None else None
+                # the reference-mode draw covers ALL molecules on every rank (one generator stream, identical lists); the device draw is
+                # keyed by global index, so each round below draws its own molecules only
+                context_all = prop_dist.sample_batch(n_nodes_all) if prop_dist is not None and not device_context else None
                 from .dist import assign_lpt, shard_range
                 if shard_assign == 'lpt':
                     mine = assign_lpt(n_nodes_all.tolist(), world)[rank]
@@ -416,7 +464,7 @@ def get_sampling_fn(config, noise_scheduler, nodes_dist, batch_size, n_samples, 
                                                                # hash of (seed, rank), any seed / rank size
                 for r0 in range(0, len(mine), batch_size):
                     idx = torch.as_tensor(mine[r0:r0 + batch_size], dtype=torch.long)
-                    context = context_all[idx].to(device) if context_all is not None else None
+                    context = context_all[idx].to(device) if context_all is not None else round_context(n_nodes_all[idx], idx)
                     mols += one_round(model, n_nodes_all[idx], context)
                     if rank == 0:
                         print('Generate {} on rank 0, Total {}.'.format(len(mols), n_samples))
@@ -440,6 +488,8 @@ def get_sampling_fn(config, noise_scheduler, nodes_dist, batch_size, n_samples, 
 
     sampling_fn.last_indices = None
     sampling_fn.last_decoded = decoded_rounds
+    sampling_fn.last_context = contexts
+    sampling_fn.device_context = device_context
     sampling_fn.last_stability = None
     sampling_fn.last_geometry = None
     return sampling_fn
