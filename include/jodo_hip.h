@@ -43,7 +43,12 @@ typedef struct {
                             16 or 32 (at nf 128, and at nf 256 with L >= 8, this means even L); the Python module further asks for
                             L <= 16 and a head input of 96..480 except 448.  Tested: L = 6 (nf 128), 8 and 10 (nf 256), 10 (nf 384) */
     int32_t n_heads;     /* H (16)                                              */
-    int32_t n_extra;     /* XH: adjacency heads (2)                             */
+    int32_t n_extra;     /* XH: adjacency heads: 2 (DGT_concat, cond_DGT_concat: 14 learned heads of 18 channels + 2, three coordinate
+                            heads) or 0 (DGT_concat_sim: 16 learned heads of 16 channels, one coordinate head; lin_query / lin_key
+                            [nf, nf], lin_edge0 [nf, nf/4], coord_mlp.2 [1, nf]).  0 is built for nf 256, layout 0, n_layers >= 8,
+                            cond_ch 0, exact fp32 only: anything else -> JODO_ERR_UNSUPPORTED, as are JODO_OPT_SPLIT_BF16,
+                            JODO_OPT_ATTN_VARIANT != 0, jodo_plan_set_split_weights and the split tapes on such a configuration;
+                            spatial_cut_off / edge_quan_th are not read by its kernels */
     int32_t mlp_ratio;   /* r                                                   */
     int32_t in_node_dim; /* nd = atom_types + include_fc_charge                 */
     int32_t edge_ch;     /* ch                                                  */

@@ -48,10 +48,18 @@ constexpr int ATT_LANES = 128;
 static_assert(ATT_LANES == PAIR_GROUP_LANES, "group size");
 constexpr float ATT_NEG = -3.0e38f;                    // "no source yet": exp(ATT_NEG - m) == 0 for every real m
 
-template <int D_, bool WQK_, int VAR_ = 0>
+// SIM_ (DGT_concat_sim, Trans_Layer of models/layers.py:13-89; tuned nf = 256 arrangement, VAR 0 only): 16 learned heads of 16 channels and
+// no adjacency heads.  q / k / lin_edge0 are eight full 32-row blocks, half h of block b = head 2b + h, no tail block: every head's sum
+// is register-local and slot k of a half-lane (head 2k + half) is block k's sum.  The edge flags are not read.  Blocks 0 .. 6 run in the
+// same loop as the mixed arrangement's main blocks (SB1 = 7) and block 7 behind it, where the mixed arrangement has its tail block: as an
+// eighth iteration of the unrolled loop the kernel spilled (2 124 bytes of scratch per lane in pair mode, 584 in directed mode), in this
+// form it needs none and fewer registers than its counterpart.
+template <int D_, bool WQK_, int VAR_ = 0, bool SIM_ = false>
 struct AttnT {
     static constexpr int D = D_, De = D_ / 4, NE = D_ / 128, HE = D_ / 8, ND = D_ / 32, HD = D_ / 2, C = D_ / 16;
     static constexpr bool WQK = WQK_;
+    static constexpr bool SIM = SIM_;
+    static_assert(!SIM_ || (!WQK_ && D_ == 256 && VAR_ == 0), "no adjacency heads: tuned nf 256 arrangement, resident weights");
     // weight residency / hand-over granularity (nf = 256, tuned arrangement only; the others stream everything):
     //   VAR 0: edge_emb + lin_edge0 in LDS (96 KiB), messages handed over block by block (double buffered, a barrier each)
     //   VAR 1: lin_edge0 in LDS (64 KiB), edge_emb streamed, messages handed over four blocks at a time (64 KiB)
@@ -216,9 +224,11 @@ __device__ __forceinline__ void attn_scores(AttnW<X>& w, const float (&x)[X::HE]
                                             const BRow& kj, int half, int f1, int f2, float (&S1)[16], float (&S2)[16],
                                             QKRows& R, const Split8* xs = nullptr) {
     // R holds block b on entry to iteration b: block 0 was requested by the caller
-    float m1[X::WQK ? 1 : 7], m2[X::WQK ? 1 : 7];       // blocks reduced per head / per head pair
+    float m1[X::WQK ? 1 : (X::SIM ? 8 : 7)], m2[X::WQK ? 1 : (X::SIM ? 8 : 7)];       // blocks reduced per head / per head pair
+    if constexpr (!X::SIM) {
     S1[0] = (f1 & 1) ? 1.f : -1e10f; S1[1] = (f1 & 2) ? 1.f : -1e10f;           // extra heads, 0 -> -1e10 (layers.py:170-174)
     S2[0] = (f2 & 1) ? 1.f : -1e10f; S2[1] = (f2 & 2) ? 1.f : -1e10f;
+    }
 #pragma unroll
     for (int b = X::SB0; b < X::SB1; ++b) {
         float a1[16], a2[16];
@@ -261,7 +271,25 @@ __device__ __forceinline__ void attn_scores(AttnW<X>& w, const float (&x)[X::HE]
         }
         pipeline_fence();
     }
-    if constexpr (!X::WQK) {                           // tuned: half h of block b = head 2b + h (channels 0..15); tail block:
+    if constexpr (X::SIM) {                            // all 16 channels of head 2b + h are half h of block b: nothing crosses the halves
+        {                                              // block 7 (its rows were requested by iteration 6): heads 14 and 15
+            f32x16 acc = attn_block<X, X::LDS_TAIL>(w, w.wL0 + (7 * X::KQE) * 64, w.oL0 + (unsigned)(7 * X::KQE) * 1024, w.oL1, x, zero16());
+            float tt[16];
+            tanh16(acc, tt);
+            float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+            for (int s = 0; s < 16; ++s) {
+                s1 = fmaf(tt[s], R.qi[s] * R.kj[s], s1);
+                if (BOTH) s2 = fmaf(tt[s], R.qj[s] * R.ki[s], s2);
+            }
+            m1[7] = s1; m2[7] = s2;
+        }
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            S1[2 * b] = S1[2 * b + 1] = m1[b] * X::INV_SQRT_C;
+            S2[2 * b] = S2[2 * b + 1] = BOTH ? m2[b] * X::INV_SQRT_C : 0.f;
+        }
+    } else if constexpr (!X::WQK) {                    // tuned: half h of block b = head 2b + h (channels 0..15); tail block:
         float tl1[14], tl2[14];                        // register g of half h = head g, channel 16 + h
         f32x16 acc;
         if constexpr (X::SPLIT) acc = splitc::block4(w.T, w.g, xs, zero16());
@@ -378,8 +406,10 @@ __device__ __forceinline__ void attn_item(const KArgs& A, const float4* wl, floa
     auto request = [&]() {
         load_nat<X::NE>(A.e + (PAIR ? cur.r_out : cur.r_in) * X::De, half, e);
         pu = reinterpret_cast<const float4*>(A.pos_out)[cur.u];
+        if constexpr (!X::SIM) {                       // (adjacency bits of the two directions: the extra heads' scores)
         f1 = A.eflag[cur.r_in];
         if (PAIR) f2 = A.eflag[cur.r_out];
+        }
     };
     if constexpr (PREF) request();
     APT_INIT
@@ -601,9 +631,9 @@ __device__ __forceinline__ void attn_item(const KArgs& A, const float4* wl, floa
 // (ai_dir: every lane visits all its sources, no hand-over), so that symmetric inputs need one launch whatever the sizes.
 // PAIR = false: the directed launch (ad_* items), runs when the inputs are asymmetric (and for ad_big items: molecules larger than
 // a group when the pair launch does not carry them, i.e. fixed-chunk plans)
-template <int D, bool WQK, bool PAIR, int VAR = 0>
+template <int D, bool WQK, bool PAIR, int VAR = 0, bool SIM = false>
 __global__ __launch_bounds__(ATT_WAVES * 64, 1) void k_edge_attn(KArgs A) {
-    using X = AttnT<D, WQK, VAR>;
+    using X = AttnT<D, WQK, VAR, SIM>;
     const bool asym = A.flags[FLAG_ASYM] != 0;
     if (PAIR ? asym : !(asym || A.pd.ad_big[blockIdx.x])) return;
     // pair mode under the plan's wrap-around schedule: this workgroup is slot blockIdx.x and works through its items (the

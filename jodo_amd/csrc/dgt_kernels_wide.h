@@ -481,8 +481,11 @@ __global__ __launch_bounds__(64) void k_fold_coord(KArgs A, FoldOffs F, float* o
 
 // ------------------------------------------------------------------------------------------------
 // edge side (directed: rows r = eoff + a*n + c, a = source / row atom, c = target / column atom)
-template <int D, int R>
+// NC: coordinate heads of coord_mlp.2 — 3 (MultiCondEquiUpdate: iota = mean over [1, adj2d, adjsp] of the three tanh heads) or 1
+// (CondEquiUpdate of DGT_concat_sim, mol_gnn.py:16-48: iota = tanh(w . y), no adjacency weighting, the edge flags are not read)
+template <int D, int R, int NC = 3>
 __global__ __launch_bounds__(64, 1) void k_edge_update(KArgs A) {
+    static_assert(NC == 1 || NC == 3, "coordinate heads");
     if (!A.flags[FLAG_ASYM]) return;                            // symmetric inputs: k_edge_update_sym runs instead
     using X = Dim<D>;
     constexpr int NCH = R * X::De / 64;                   // edge FFN hidden chunks of 64
@@ -611,22 +614,29 @@ __global__ __launch_bounds__(64, 1) void k_edge_update(KArgs A) {
             float bb[16], k0[16], k1[16], k2[16];
             load16(b0_ + b * 32 + half * 16, bb);
             load16(w2_ + b * 32 + half * 16, k0);
+            if constexpr (NC == 3) {
             load16(w2_ + D + b * 32 + half * 16, k1);
             load16(w2_ + 2 * D + b * 32 + half * 16, k2);
+            }
             f32x16 acc = mfma_block_p<X::KQD>(wp, ws, wcur, wnx, uu, zero16());
 #pragma unroll
             for (int s = 0; s < 16; ++s) {
                 const float ys = silu_f(acc[s] + bb[s]);
                 c0 = fmaf(ys, k0[s], c0);
+                if constexpr (NC == 3) {
                 c1 = fmaf(ys, k1[s], c1);
                 c2 = fmaf(ys, k2[s], c2);
+                }
             }
         }
         c0 = tanh_f(pair_sum(c0));
+        float iota = c0;
+        if constexpr (NC == 3) {
         c1 = tanh_f(pair_sum(c1));
         c2 = tanh_f(pair_sum(c2));
         const int fl = A.eflag[r];
-        const float iota = (c0 + ((fl & 1) ? c1 : 0.f) + ((fl & 2) ? c2 : 0.f)) * (1.f / 3.f);
+        iota = (c0 + ((fl & 1) ? c1 : 0.f) + ((fl & 2) ? c2 : 0.f)) * (1.f / 3.f);
+        }
         const float nrm = fmaxf(sqrtf(d2), 1e-8f);
         const float f = ok ? cscale * iota / nrm : 0.f;
         dax = fmaf(dx, f, dax);
@@ -647,8 +657,9 @@ __global__ __launch_bounds__(64, 1) void k_edge_update(KArgs A) {
 // waves.  Every wave evaluates the shared trunk and the LayerNorm statistics; the output blocks of the per-pair coord_mlp.0
 // projection Z and their SiLU / coord_mlp.2 tails — half of a folded item's matrix work, 56 % of an unfolded one's — are dealt to
 // the waves, whose partial dot products meet in LDS in a fixed order (wave 0 finishes the item and does every store).
-template <int D, int R, bool FOLD = false, bool ROT = false, int ZW = 1>
+template <int D, int R, bool FOLD = false, bool ROT = false, int ZW = 1, int NC = 3>
 __global__ __launch_bounds__(ZW * 64, 1) void k_edge_update_sym(KArgs A) {
+    static_assert(NC == 3 || (NC == 1 && (D == 256 || FOLD)), "one coordinate head (DGT_concat_sim): the hoisted forms");
     static_assert(FOLD || !ROT, "the rotated statistics need the shared modulation row");
     static_assert(ZW == 1 || D == 256 || FOLD, "the Z split needs the hoisted form (one coord_mlp.0 per pair)");
     if (A.flags[FLAG_ASYM]) return;
@@ -688,11 +699,11 @@ __global__ __launch_bounds__(ZW * 64, 1) void k_edge_update_sym(KArgs A) {
     __shared__ float4 pl[PLB > 0 ? PLB * 4 * 64 : 1];
     // coord_mlp.2 (3 x D, the same for every item): read 16 times per pair offset by the tails right where it is needed; from
     // global memory each read was an exposed L1 round trip between two MFMA blocks, from LDS it is a short ds_read
-    __shared__ float4 w2s[HOIST ? 3 * D / 4 : 1];
+    __shared__ float4 w2s[HOIST ? NC * D / 4 : 1];
     __shared__ float zred[ZW > 1 ? (ZW - 1) * 12 * 64 : 1];     // partial coord_mlp.2 dot products of waves 1 .. ZW - 1
     if constexpr (HOIST) {
         const float4* src = reinterpret_cast<const float4*>(A.W + A.wb[JB_C2_W]);
-        for (int i = threadIdx.x; i < 3 * D / 4; i += ZW * 64) w2s[i] = src[i];
+        for (int i = threadIdx.x; i < NC * D / 4; i += ZW * 64) w2s[i] = src[i];
         __syncthreads();
     }
     // (Tried and dropped: the trunk's other item-invariant vectors — modulation chunks, biases, Gaussian table, 3 KiB — from an
@@ -951,7 +962,8 @@ __global__ __launch_bounds__(ZW * 64, 1) void k_edge_update_sym(KArgs A) {
                     };
                     const int fo = b * 32 + half * 16 + hq * 8;
                     const float* w2l = reinterpret_cast<const float*>(w2s);
-                    ld8(w2l + fo, k0); ld8(w2l + D + fo, k1); ld8(w2l + 2 * D + fo, k2);
+                    ld8(w2l + fo, k0);
+                    if constexpr (NC == 3) { ld8(w2l + D + fo, k1); ld8(w2l + 2 * D + fo, k2); }
 #pragma unroll
                     for (int s = 0; s < 8; s += 2) {               // element pairs on the packed fp32 pipe; the three dot products
                         const f32x2 bs2 = pk2(bsb[hq * 8 + s], bsb[hq * 8 + s + 1]);   // keep even / odd partial sums
@@ -965,8 +977,10 @@ __global__ __launch_bounds__(ZW * 64, 1) void k_edge_update_sym(KArgs A) {
                         const f32x2 pre = pk2(z[hq * 8 + s], z[hq * 8 + s + 1]) + pk2(t0[hq * 8 + s], t0[hq * 8 + s + 1]);
                         const f32x2 ys0 = silu_f2(__builtin_elementwise_fma(pre, (f32x2)(rstd0), pk2(ca[s], ca[s + 1])));
                         c00 = __builtin_elementwise_fma(ys0, pk2(k0[s], k0[s + 1]), c00);
+                        if constexpr (NC == 3) {
                         c01 = __builtin_elementwise_fma(ys0, pk2(k1[s], k1[s + 1]), c01);
                         c02 = __builtin_elementwise_fma(ys0, pk2(k2[s], k2[s + 1]), c02);
+                        }
                     }
                     pipeline_fence();
 #pragma unroll
@@ -981,8 +995,10 @@ __global__ __launch_bounds__(ZW * 64, 1) void k_edge_update_sym(KArgs A) {
                         const f32x2 pre = pk2(z[hq * 8 + s], z[hq * 8 + s + 1]) + pk2(t1[hq * 8 + s], t1[hq * 8 + s + 1]);
                         const f32x2 ys1 = silu_f2(__builtin_elementwise_fma(pre, (f32x2)(rstd1), pk2(ca[s], ca[s + 1])));
                         c10 = __builtin_elementwise_fma(ys1, pk2(k0[s], k0[s + 1]), c10);
+                        if constexpr (NC == 3) {
                         c11 = __builtin_elementwise_fma(ys1, pk2(k1[s], k1[s + 1]), c11);
                         c12 = __builtin_elementwise_fma(ys1, pk2(k2[s], k2[s + 1]), c12);
+                        }
                     }
                     pipeline_fence();
                 }
@@ -1011,11 +1027,14 @@ __global__ __launch_bounds__(ZW * 64, 1) void k_edge_update_sym(KArgs A) {
 #pragma unroll
             for (int dir = 0; dir < 2; ++dir) {
                 const float c0 = tanh_f(pair_sum(dir == 0 ? c00.x + c00.y : c10.x + c10.y));
+                const size_t rr = dir == 0 ? P.rij : P.rji;
+                float iota = c0;
+                if constexpr (NC == 3) {
                 const float c1 = tanh_f(pair_sum(dir == 0 ? c01.x + c01.y : c11.x + c11.y));
                 const float c2 = tanh_f(pair_sum(dir == 0 ? c02.x + c02.y : c12.x + c12.y));
-                const size_t rr = dir == 0 ? P.rij : P.rji;
                 const int fl = A.eflag[rr];
-                const float iota = (c0 + ((fl & 1) ? c1 : 0.f) + ((fl & 2) ? c2 : 0.f)) * (1.f / 3.f);
+                iota = (c0 + ((fl & 1) ? c1 : 0.f) + ((fl & 2) ? c2 : 0.f)) * (1.f / 3.f);
+                }
                 const float f = cscale * iota / nrm;
                 const float sgn = dir == 0 ? 1.f : -1.f;          // x_a - x_c
                 if (P.ok && half == 0 && zw == 0)

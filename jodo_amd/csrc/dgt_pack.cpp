@@ -423,7 +423,8 @@ int pack(const jodo_cfg* cfg, const jodo_tensor* tensors, int n_tensors, Packer&
         proj(b + ".equi_update.input_lin.weight", D, KIN, nat_in(D, D), nat_out(D));
         P.put(S(W(b + ".equi_update.input_lin.bias", D)), D);
         proj(b + ".equi_update.coord_mlp.0.weight", D, D, nat_in(D), nat_out(D)); P.put(S(W(b + ".equi_update.coord_mlp.0.bias", D)), D);
-        P.put(S(W(b + ".equi_update.coord_mlp.2.weight", (int64_t)3 * D)), (size_t)3 * D);
+        // coord_mlp.2: one row per coordinate head, 1 + n_extra of them (3, or 1 for the model without adjacency heads)
+        P.put(S(W(b + ".equi_update.coord_mlp.2.weight", (int64_t)(1 + d.XH) * D)), (size_t)(1 + d.XH) * D);
         P.put(S(W(b + ".equi_update.coord_norm.scale", 1)), 1);
         const OMap omn = nat_out(d.cnp, cn), ome = nat_out(32, ce);
         proj("node_" + std::to_string(l) + ".weight", cn, D, nat_in(D), omn); P.put_vec(S(W("node_" + std::to_string(l) + ".bias", cn)), omn);
@@ -538,6 +539,7 @@ static int pack_split_tape(const jodo_cfg* cfg, const jodo_tensor* tensors, int 
     int rc = dgt_dims_from_cfg(cfg, &d);
     if (rc != JODO_OK) return rc;
     if ((d.D != 256 && d.D != 384) || d.cond_ch != 0) return jodo_set_error(JODO_ERR_UNSUPPORTED, "split-bf16 form: built for nf = 256 / 384 unconditional models (got nf %d, cond_ch %d)", d.D, d.cond_ch);
+    if (d.XH == 0) return jodo_set_error(JODO_ERR_UNSUPPORTED, "split-bf16 form: not built for the model without extra heads (n_extra_heads=0)");
     const int D = d.D, De = d.De, L = d.L, r = d.r, ce = (2 * De) / L, KIN = 2 * D + 2 * De;
     Lookup lk;
     for (int i = 0; i < n_tensors; ++i) {
@@ -683,6 +685,7 @@ extern "C" int jodo_dgt_split_size(const jodo_cfg* cfg, size_t* total_bytes, siz
     const int rc = dgt_dims_from_cfg(cfg, &d);
     if (rc != JODO_OK) return rc;
     if ((d.D != 256 && d.D != 384) || d.cond_ch != 0) return jodo_set_error(JODO_ERR_UNSUPPORTED, "split-bf16 form: built for nf = 256 / 384 unconditional models (got nf %d, cond_ch %d)", d.D, d.cond_ch);
+    if (d.XH == 0) return jodo_set_error(JODO_ERR_UNSUPPORTED, "split-bf16 form: not built for the model without extra heads (n_extra_heads=0)");
     *pair_block_bytes = (size_t)split_tape_steps(d) * 3072;
     *node_block_bytes = (size_t)split_node_tape_steps(d) * 3072;
     *attn_block_bytes = (size_t)split_attn_tape_steps(d) * 3072;

@@ -43,8 +43,14 @@ int dgt_dims_from_cfg(const jodo_cfg* c, DgtDims* d) {
     if (c->nf != 128 && c->nf != 256 && c->nf != 384)
         return jodo_set_error(JODO_ERR_UNSUPPORTED, "nf=%d: kernels are built for nf=128, nf=256 and nf=384", c->nf);
     if (c->layout != 0 && c->layout != 1) return jodo_set_error(JODO_ERR_ARG, "layout=%d (0 or 1)", c->layout);
-    if (c->n_heads != 16 || c->n_extra != 2)
-        return jodo_set_error(JODO_ERR_UNSUPPORTED, "n_heads=%d n_extra_heads=%d: kernels are built for 16/2", c->n_heads, c->n_extra);
+    // n_extra 2: DGT_concat / cond_DGT_concat (14 learned heads + two adjacency heads); n_extra 0: DGT_concat_sim (16 learned heads,
+    // one coordinate head), built on the tuned nf = 256 kernel set only
+    if (c->n_heads != 16 || (c->n_extra != 2 && c->n_extra != 0))
+        return jodo_set_error(JODO_ERR_UNSUPPORTED, "n_heads=%d n_extra_heads=%d: kernels are built for 16/2 and 16/0", c->n_heads, c->n_extra);
+    if (c->n_extra == 0 && c->nf != 256)
+        return jodo_set_error(JODO_ERR_UNSUPPORTED, "nf=%d without extra heads: the kernels without adjacency heads are built for nf=256", c->nf);
+    if (c->n_extra == 0 && c->cond_ch != 0)
+        return jodo_set_error(JODO_ERR_UNSUPPORTED, "cond_ch=%d without extra heads: there is no conditional model without adjacency heads", c->cond_ch);
     if (c->mlp_ratio != 2 && c->mlp_ratio != 4)
         return jodo_set_error(JODO_ERR_UNSUPPORTED, "mlp_ratio=%d: supported 2, 4", c->mlp_ratio);
     if (c->n_layers < 1 || c->n_layers > 32) return jodo_set_error(JODO_ERR_ARG, "n_layers=%d", c->n_layers);
@@ -61,6 +67,9 @@ int dgt_dims_from_cfg(const jodo_cfg* c, DgtDims* d) {
     if (d->cep > 32) return jodo_set_error(JODO_ERR_UNSUPPORTED, "n_layers=%d at nf=%d: edge readout width %d beyond one 32-row block", d->L, d->D, ce);
     // the nf = 256 node kernels of dgt_kernels_node.h are written for the 64-wide node readout
     d->wide = (c->nf != 256 || c->layout == 1 || d->cnp != 64) ? 1 : 0;
+    if (d->XH == 0 && d->wide)
+        return jodo_set_error(JODO_ERR_UNSUPPORTED, "n_extra_heads=0 with layout=%d, n_layers=%d: the kernels without adjacency heads exist in the "
+                              "tuned nf=256 set only (layout 0, n_layers >= 8)", c->layout, d->L);
     int tail = d->SC - 16;
     d->QKP = d->wide ? d->SH * 32 : (d->SH / 2 + (tail + 1) / 2) * 32;      // wide: one head per 32-row block
     d->ndp = (2 * d->nd + 7) / 8 * 8;
@@ -571,6 +580,9 @@ extern "C" int jodo_plan_set_option(jodo_plan* p, int option, int value) {
         return jodo_set_error(JODO_ERR_ARG, "plan_set_option: a pin is 0 (none), 1 or 2, got %d", value);
     if (option == JODO_OPT_ATTN_VARIANT && (value < 0 || value > 3))
         return jodo_set_error(JODO_ERR_ARG, "plan_set_option: attention variant must be 0..3, got %d", value);
+    // the model without adjacency heads (n_extra 0) is built in the exact-fp32 form with the default attention variant only
+    if (p->dims.XH == 0 && value != 0 && (option == JODO_OPT_SPLIT_BF16 || option == JODO_OPT_ATTN_VARIANT))
+        return jodo_set_error(JODO_ERR_UNSUPPORTED, "plan_set_option: option %d is not built for the model without extra heads (n_extra_heads=0)", option);
     p->opt[option] = value;
     return JODO_OK;
 }
@@ -632,6 +644,7 @@ extern "C" int jodo_debug_attn_schedule(const jodo_plan* p, int64_t* o) {
 }
 extern "C" int jodo_plan_set_split_weights(jodo_plan* p, const void* tape_dev, size_t bytes) {
     if (!p) return jodo_set_error(JODO_ERR_ARG, "null plan");
+    if (tape_dev && p->dims.XH == 0) return jodo_set_error(JODO_ERR_UNSUPPORTED, "set_split_weights: the split-bf16 form is not built for the model without extra heads (n_extra_heads=0)");
     if (tape_dev) {
         size_t total = 0, per_block = 0, node_block = 0, attn_block = 0;
         // (a conditional plan takes the conditional tape: jodo_dgt_pack_split_cond_host)

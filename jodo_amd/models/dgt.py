@@ -1,7 +1,7 @@
 """MI355X-native Diffusion Graph Transformer score networks, registered under the reference's names.
 
-`DGT_concat` / `Cond_DGT_concat` are drop-in replacements for the classes of the same registry name
-in /root/reference/models/mol_gnn.py (:410-594, :597-794):
+`DGT_concat` / `Cond_DGT_concat` / `DGT_concat_sim` are drop-in replacements for the classes of the same registry name
+in /root/reference/models/mol_gnn.py (:410-594, :597-794, :949-1124):
 
   * same constructor argument (`config`) and the same config keys are read;
   * same parameter names, shapes and registration order (state_dict keys, EMA shadow-list order,
@@ -105,35 +105,45 @@ _UNSUPPORTED = (('dist_gbf', True), ('cond_time', True), ('pred_data', True), ('
 
 class _DGTBase(HostRuntime, nn.Module):
     conditional = False
+    extra_heads = None                # None: config.model.n_extra_heads (2); 0: the class never reads the key (DGT_concat_sim)
     _derived = ('_split_tape',)       # (pack generation, device uint8 tensor): the split form's static weight tape
 
     def __init__(self, config):
         super().__init__()
         m = config.model
+        sim = self.extra_heads is not None        # no adjacency heads: softmax_inf, trans_name, n_extra_heads, edge_quan_th are never read
         for key, want in _UNSUPPORTED:
+            if sim and key == 'softmax_inf':
+                continue
             if getattr(m, key) != want:
                 raise NotImplementedError(
                     "config.model.%s=%r: the HIP path implements %r only (the JODO configs' setting)"
                     % (key, getattr(m, key), want))
-        if not self.conditional and getattr(m, 'trans_name', 'TransMixLayer') != 'TransMixLayer':
+        if not self.conditional and not sim and getattr(m, 'trans_name', 'TransMixLayer') != 'TransMixLayer':
             raise NotImplementedError("config.model.trans_name=%r: only TransMixLayer is implemented" % m.trans_name)
         in_node_dim = config.data.atom_types + int(m.include_fc_charge)
         D, De, L = m.nf, m.nf // 4, m.n_layers
         T = D * 4
         cond_ch = int(m.cond_ch) if self.conditional else 0
-        if D not in (128, 256, 384) or m.n_heads != 16 or m.n_extra_heads != 2 or m.mlp_ratio not in (2, 4):
+        n_extra = self.extra_heads if sim else m.n_extra_heads
+        if D not in (128, 256, 384) or m.n_heads != 16 or n_extra != (0 if sim else 2) or m.mlp_ratio not in (2, 4):
             raise NotImplementedError("HIP kernels are built for nf in {128, 256, 384}, n_heads=16, n_extra_heads=2, "
                                       "mlp_ratio in {2,4} (got nf=%d heads=%d/%d ratio=%d)" %
-                                      (D, m.n_heads, m.n_extra_heads, m.mlp_ratio))
+                                      (D, m.n_heads, n_extra, m.mlp_ratio))
         # kernel_layout (not a reference key): 'wide' runs the width-generic kernel set at nf=256 too (tests)
         wide = getattr(m, 'kernel_layout', 'auto') == 'wide'
-        self.dims = ModelDims(D, L, m.n_heads, m.n_extra_heads, m.mlp_ratio, in_node_dim, m.edge_ch, cond_ch, wide=wide)
+        self.dims = ModelDims(D, L, m.n_heads, n_extra, m.mlp_ratio, in_node_dim, m.edge_ch, cond_ch, wide=wide)
+        if n_extra == 0 and self.dims.wide:
+            raise NotImplementedError("DGT_concat_sim at nf=%d, n_layers=%d, kernel_layout=%r: the kernels without adjacency heads are built "
+                                      "for the tuned nf=256 set only (nf=256, n_layers >= 8, the default layout)"
+                                      % (D, L, getattr(m, 'kernel_layout', 'auto')))
         if self.dims.cep > 32 or self.dims.KEH % 32 or not 3 <= self.dims.KEH // 32 <= 15 or self.dims.KEH // 32 == 14 or L > 16:
             raise NotImplementedError("n_layers=%d at nf=%d: the edge head input (De + n_layers x %d = %d) must be a multiple of 32 in "
                                       "[96, 480] and the per-block edge readout (%d) at most 32 wide" %
                                       (L, D, self.dims.cep, self.dims.KEH, self.dims.ce))
-        self.edge_th = float(m.edge_quan_th)
-        self.spatial_cut_off = float(m.spatial_cut_off)
+        # (without adjacency heads both thresholds only feed an adjacency nobody reads: constants, so that the keys have no effect)
+        self.edge_th = 0.0 if sim else float(m.edge_quan_th)
+        self.spatial_cut_off = 0.0 if sim else float(m.spatial_cut_off)
         self.n_layers = L
         self.dropout_p = m.dropout           # identity at inference; kept for config parity
 
@@ -143,7 +153,7 @@ class _DGTBase(HostRuntime, nn.Module):
         self.dist_layer = _GaussianParams(De, T)
         cat_node, cat_edge = (D * 2) // L, (De * 2) // L
         for i in range(L):
-            self.add_module("e_block_%d" % i, _BlockParams(D, De, T, m.n_extra_heads, m.n_heads, m.mlp_ratio))
+            self.add_module("e_block_%d" % i, _BlockParams(D, De, T, n_extra, m.n_heads, m.mlp_ratio))
             self.add_module("node_%d" % i, nn.Linear(D, cat_node))
             self.add_module("edge_%d" % i, nn.Linear(De, cat_edge))
         self.node_pred_mlp = _mlp3(cat_node * L + D, D, D // 2, in_node_dim)
@@ -498,3 +508,21 @@ class DGT_concat(_DGTBase):
 class Cond_DGT_concat(_DGTBase):
     """Conditional Diffusion Graph Transformer with self-conditioning (HIP)."""
     conditional = True
+
+
+@utils.register_model(name='DGT_concat_sim')
+class DGT_concat_sim(_DGTBase):
+    """Diffusion Graph Transformer with self-conditioning, without extra attention heads (HIP): the reference's EquivariantBlock /
+    Trans_Layer / CondEquiUpdate (mol_gnn.py:949-1124, :97-208, :16-48; layers.py:13-89).  16 learned heads of nf / 16 channels, softmax over
+    the real incoming edges, one coordinate head; `n_extra_heads`, `trans_name`, `softmax_inf` and `edge_quan_th` are never read and
+    `spatial_cut_off` has no effect.  Built for nf = 256 (both 3-D JODO configs), inference only, exact fp32."""
+    conditional = False
+    extra_heads = 0
+
+    def forward(self, t, xh, node_mask, edge_mask, context=None, *args, **kwargs):
+        if self.split_bf16:
+            raise NotImplementedError("DGT_concat_sim has no split-bf16 form: leave model.split_bf16 = False (the exact-fp32 kernels)")
+        if (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())) or (self.training and self.dropout_p > 0):
+            raise NotImplementedError("DGT_concat_sim is built for inference: call it under torch.no_grad() in eval() mode "
+                                      "(training this model on the GPU is not implemented)")
+        return super().forward(t, xh, node_mask, edge_mask, context, *args, **kwargs)
