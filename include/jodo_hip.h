@@ -354,7 +354,12 @@ int jodo_decode(int B, int N, int atom_types, int include_fc, int edge_ch, int c
  * regenerated, not stored: pass the same (dropout_p, seed) to the backward.  flags_out (optional): int32[8], [0] = NaN guard
  * fired (mol_gnn.py:587-589: positions zeroed, their gradient is zero), [3] = self-conditioning distances present (0 => the
  * first-step branch of :544).  workspace: jodo_train_workspace_bytes() bytes, kept by the caller between forward and backward.
- * desc_dev: jodo_train_desc_bytes() bytes of device memory filled by jodo_train_upload (synchronises the stream once). */
+ * desc_dev: jodo_train_desc_bytes() bytes of device memory filled by jodo_train_upload (synchronises the stream once).
+ * jodo_train_create takes cfg->n_extra = 2 (DGT_concat, cond_DGT_concat) or 0 (DGT_concat_sim: EquivariantBlock / Trans_Layer /
+ * CondEquiUpdate, mol_gnn.py:949-1124, :97-208, :16-48 — 16 learned heads, the adjacency flags never read, one coordinate head:
+ * coord_mlp.2.weight [1, nf], the kept coordinate activation [R, 1]; dropout in the two feed-forwards as above).  n_extra = 0 is taken
+ * with nf 256, n_heads 16, n_layers >= 8, layout 0 and cond_ch 0 only; every other n_extra and every other combination ->
+ * JODO_ERR_UNSUPPORTED naming the values. */
 typedef struct jodo_train jodo_train;
 int jodo_train_create(const jodo_cfg* cfg, int B, int N, const int32_t* n_nodes_host, const jodo_tensor* params, int n_params,
                       jodo_train** out);

@@ -79,6 +79,7 @@ struct jodo_train {
     jodo_cfg cfg;
     int B, N, Nn, R;
     int D, De, T, L, H, XH, SC, QK, C, r, nd, ch, cc, cn, ce, catn, cate, half;
+    int NCo;                          // coordinate heads (rows of coord_mlp.2, columns of the kept inv): 1 + XH — 3 for DGT_concat, 1 for DGT_concat_sim
     std::vector<int> tables;          // node_off | edge_off | nn | node_mol | edge_mol | edge_a | edge_c | ec_off | ec_mol_off
     size_t o_node_off, o_edge_off, o_nn, o_node_mol, o_edge_mol, o_edge_a, o_edge_c, o_ec_off, o_ec_mol_off;
     int NC;                           // chunks of edge rows (two-level per-molecule sums)
@@ -120,7 +121,7 @@ void layout(const jodo_train& t, Arena& a, Bufs& b) {
         k.t0 = a.f(R * QK); k.t1 = a.f(R * D); k.alpha = a.f(R * H); k.hhat = a.f(Nn * D); k.n2e = a.f(Nn * De);
         k.xh_hn = a.f(Nn * D); k.rs_hn = a.f(Nn); k.hn = a.f(Nn * D); k.f1 = a.f(Nn * r * D); k.a1 = a.f(Nn * r * D); k.f2 = a.f(Nn * D);
         k.xh_en = a.f(R * De); k.rs_en = a.f(R); k.en = a.f(R * De); k.f3 = a.f(R * r * De); k.a3 = a.f(R * r * De); k.f4 = a.f(R * De);
-        k.xh_pre = a.f(R * D); k.rs_pre = a.f(R); k.u = a.f(R * D); k.c0pre = a.f(R * D); k.c0a = a.f(R * D); k.inv = a.f(R * 3);
+        k.xh_pre = a.f(R * D); k.rs_pre = a.f(R); k.u = a.f(R * D); k.c0pre = a.f(R * D); k.c0a = a.f(R * D); k.inv = a.f(R * t.NCo);
     }
     b.nh1pre = a.f(Nn * D); b.nh1 = a.f(Nn * D); b.nh2pre = a.f(Nn * D / 2); b.nh2 = a.f(Nn * D / 2); b.atom = a.f(Nn * nd);
     for (int s = 0; s < 2; ++s) { b.x1pre[s] = a.f(R * De); b.x1[s] = a.f(R * De); b.x2pre[s] = a.f(R * De / 2); b.x2[s] = a.f(R * De / 2); }
@@ -158,7 +159,7 @@ void layout(const jodo_train& t, Arena& a, Bufs& b) {
         if (b.finpart_floats < need) b.finpart_floats = need;
     }
     b.finpart = a.f(b.finpart_floats); b.fin_used = 0; b.defer_fin = false;
-    const FusedDims fd{t.D, t.De, t.r, t.QK, t.ce, t.L};
+    const FusedDims fd{t.D, t.De, t.r, t.QK, t.ce, t.L, t.NCo};
     b.fpack_block = fused_pack_layout(fd).total_bwd;
     b.fpack = a.f(b.fpack_block * L);
     for (int s = 0; s < 3; ++s) b.tE_De2[s] = a.f(R * De);
@@ -437,7 +438,7 @@ void forward(const Ctx& c, const float* xh, const float* edge_x, const float* co
     for (int l = 0; l < L; ++l) {
         const BlkIx& ix = t.blk[l]; BlkBuf& k = b.blk[l];
         // distances, Gaussian basis, edge_emb([G, e]) and the two modulated LayerNorms (:279-296)
-        const FusedDims fd{D, De, r, QK, t.ce, L};
+        const FusedDims fd{D, De, r, QK, t.ce, L, t.NCo};
         FusedBlockParams fp;
         FusedTopo ft{R, tp.edge_a, tp.edge_c, tp.edge_mol, t.save_activations};
         float* fpk = b.fpack + (size_t)l * b.fpack_block;
@@ -542,10 +543,12 @@ void forward(const Ctx& c, const float* xh, const float* edge_x, const float* co
             c.stats(R, D, b.tE_D[1], b.tRow[0], k.rs_pre);
             c.ln_mod(R, D, b.tE_D[1], b.tRow[0], k.rs_pre, tp.edge_mol, k.qmod, 2 * D, 0, D, k.xh_pre, k.u);
             c.lin_silu(k.u, D, R, D, c.p(ix.eq_c0.w), D, D, c.p(ix.eq_c0.b), k.c0pre, k.c0a, nod);
-            c.lin_tanh(k.c0a, D, R, D, c.p(ix.eq_c2), D, 3, nullptr, k.inv);
+            c.lin_tanh(k.c0a, D, R, D, c.p(ix.eq_c2), D, t.NCo, nullptr, k.inv);
         }
-        JT_LAUNCH(k_coord_fwd, R, s, tp, (const float*)b.pos[l], (const float*)k.inv, (const float*)b.adj2d, (const float*)b.adjsp,
-                           c.p(ix.eq_scale), b.tE3[0]);
+        if (t.NCo == 1) JT_LAUNCH(k_coord_fwd<1>, R, s, tp, (const float*)b.pos[l], (const float*)k.inv, (const float*)b.adj2d, (const float*)b.adjsp,
+                                  c.p(ix.eq_scale), b.tE3[0]);
+        else JT_LAUNCH(k_coord_fwd<3>, R, s, tp, (const float*)b.pos[l], (const float*)k.inv, (const float*)b.adj2d, (const float*)b.adjsp,
+                       c.p(ix.eq_scale), b.tE3[0]);
         JT_LAUNCH(k_coord_sum, (long)Nn * 3, s, tp, (const float*)b.pos[l], (const float*)b.tE3[0], b.tN3[0]);
         JT_LAUNCH(k_center, (long)B * 3, s, tp, (const float*)b.tN3[0], (const int*)nullptr, b.pos[l + 1]);
         // readouts written into the head inputs in place (:569-570)
@@ -608,7 +611,7 @@ void gbf_bwd(const Ctx& c, long rows, const float* d2, const float* gm, int mean
 void backward(const Ctx& c, const float* nl, const float* d_out_xh, const float* d_out_edge, float p_drop, unsigned long long seed) {
     const jodo_train& t = c.t; Bufs& b = c.b; const Topo& tp = c.tp; hipStream_t s = c.s;
     const int B = t.B, Nn = t.Nn, R = t.R, D = t.D, De = t.De, T = t.T, L = t.L, QK = t.QK, H = t.H, r = t.r, nd = t.nd, ch = t.ch;
-    const int F17 = 2 * t.half + 1, ldin = 2 * ch + De;
+    const int F17 = 2 * t.half + 1, ldin = 2 * ch + De, NCo = t.NCo;
     const Drop nod = c.drop(0.f, 0, 0, 0);
     // gradients are accumulated below: zero them first — adjacent buffers (a caller that carves all gradients out of one
     // allocation, as jodo_amd/train.py does) in one fill instead of one per tensor
@@ -658,10 +661,12 @@ void backward(const Ctx& c, const float* nl, const float* d_out_xh, const float*
         // ---- equivariant update, backwards: centring, position sums, CoorsNorm, tanh, coord_mlp, LayerNorm + modulate, input_lin
         float *dxp = b.tN3[3], *dinv = b.tE3[0], *ddiff = b.tE3[1];
         JT_LAUNCH(k_center, (long)B * 3, s, tp, (const float*)dpos, (const int*)nullptr, dxp);
-        JT_LAUNCH(k_coord_bwd, R, s, tp, (const float*)b.pos[l], (const float*)k.inv, (const float*)b.adj2d, (const float*)b.adjsp,
-                           c.p(ix.eq_scale), (const float*)dxp, dinv, ddiff, b.tRow[2]);
+        if (NCo == 1) JT_LAUNCH(k_coord_bwd<1>, R, s, tp, (const float*)b.pos[l], (const float*)k.inv, (const float*)b.adj2d, (const float*)b.adjsp,
+                                c.p(ix.eq_scale), (const float*)dxp, dinv, ddiff, b.tRow[2]);
+        else JT_LAUNCH(k_coord_bwd<3>, R, s, tp, (const float*)b.pos[l], (const float*)k.inv, (const float*)b.adj2d, (const float*)b.adjsp,
+                       c.p(ix.eq_scale), (const float*)dxp, dinv, ddiff, b.tRow[2]);
         c.colsum(b.tRow[2], 1, nullptr, 0, R, 1, c.g(ix.eq_scale));
-        const FusedDims fd{D, De, r, QK, t.ce, L};
+        const FusedDims fd{D, De, r, QK, t.ce, L, t.NCo};
         FusedBlockParams fp;
         FusedTopo ft{R, tp.edge_a, tp.edge_c, tp.edge_mol};
         float* fpk = b.fpack + (size_t)l * b.fpack_block;
@@ -676,13 +681,13 @@ void backward(const Ctx& c, const float* nl, const float* d_out_xh, const float*
             // chain C': tanh', coord_mlp.2^T, SiLU', coord_mlp.0^T, LayerNorm + modulate backward, input_lin[e ; G]^T — one kernel; it leaves
             // dinv (in place), dc0, du, dpre for the weight-gradient products and the modulation sums below, adds into de and writes dG
             fused_bwd_c(s, fd, ft, fp, fpk, k.inv, dinv, k.c0pre, k.xh_pre, k.rs_pre, k.qmod, dc0, du, dpre, de, dG);
-            c.lin_dw(dinv, 3, R, 3, k.c0a, D, D, c.g(ix.eq_c2), D);
+            c.lin_dw(dinv, NCo, R, NCo, k.c0a, D, D, c.g(ix.eq_c2), D);
             c.lin_dw(dc0, D, R, D, k.u, D, D, c.g(ix.eq_c0.w), D, c.g(ix.eq_c0.b));
             c.seg2_edge(D, du, k.xh_pre, dqmod, Mt, 0, D);
         } else {
-            JT_LAUNCH(k_tanh_bwd, (long)R * 3, s, (long)R * 3, (const float*)k.inv, dinv);
-            c.lin_dw(dinv, 3, R, 3, k.c0a, D, D, c.g(ix.eq_c2), D);
-            c.lin_dx(dinv, 3, R, 3, c.p(ix.eq_c2), D, D, dc0, D, 0);
+            JT_LAUNCH(k_tanh_bwd, (long)R * NCo, s, (long)R * NCo, (const float*)k.inv, dinv);
+            c.lin_dw(dinv, NCo, R, NCo, k.c0a, D, D, c.g(ix.eq_c2), D);
+            c.lin_dx(dinv, NCo, R, NCo, c.p(ix.eq_c2), D, D, dc0, D, 0);
             c.silu_bwd((long)R * D, k.c0pre, dc0, dc0, nod);
             c.lin_dw(dc0, D, R, D, k.u, D, D, c.g(ix.eq_c0.w), D, c.g(ix.eq_c0.b));
             c.lin_dx(dc0, D, R, D, c.p(ix.eq_c0.w), D, D, du, D, 0);
@@ -883,8 +888,14 @@ extern "C" {
 
 int jodo_train_create(const jodo_cfg* cfg, int B, int N, const int32_t* n_nodes, const jodo_tensor* params, int n_params, jodo_train** out) {
     if (!cfg || !n_nodes || !params || !out || B <= 0 || N <= 0) return jodo_set_error(JODO_ERR_ARG, "jodo_train_create: null / non-positive argument");
-    if (cfg->nf % cfg->n_heads || cfg->nf % 4 || cfg->n_heads <= cfg->n_extra || cfg->n_extra != 2)
+    if (cfg->nf % cfg->n_heads || cfg->nf % 4 || cfg->n_heads <= cfg->n_extra || (cfg->n_extra != 2 && cfg->n_extra != 0))
         return jodo_set_error(JODO_ERR_UNSUPPORTED, "jodo_train_create: nf %d / n_heads %d / n_extra_heads %d", cfg->nf, cfg->n_heads, cfg->n_extra);
+    // n_extra_heads 0 is DGT_concat_sim (16 learned heads, one coordinate head), built as the module builds it: nf 256, 16 heads, at least
+    // 8 blocks, the default layout, no context
+    if (cfg->n_extra == 0 && (cfg->nf != 256 || cfg->n_heads != 16 || cfg->n_layers < 8 || cfg->layout != 0 || cfg->cond_ch != 0))
+        return jodo_set_error(JODO_ERR_UNSUPPORTED, "jodo_train_create: n_extra_heads 0 (DGT_concat_sim) is built for nf 256, n_heads 16, n_layers >= 8, the "
+                              "default layout and no context (got nf %d, n_heads %d, n_layers %d, layout %d, cond_ch %d)", cfg->nf, cfg->n_heads,
+                              cfg->n_layers, cfg->layout, cfg->cond_ch);
     // k_row_part / k_ln_bwd_part (train_ops.h) cut a LayerNorm row of De = nf / 4 features into eight equal parts, and the MLP heads
     // halve D and De: a width that is not a multiple of 32 would silently drop trailing features from the statistics
     if (cfg->n_layers < 1 || cfg->n_layers > 16)
@@ -893,7 +904,7 @@ int jodo_train_create(const jodo_cfg* cfg, int B, int N, const int32_t* n_nodes,
         return jodo_set_error(JODO_ERR_UNSUPPORTED, "jodo_train_create: nf %d is not a multiple of 32 (LayerNorm rows of nf / 4 features are reduced in eight equal parts)", cfg->nf);
     jodo_train* t = new jodo_train();
     t->cfg = *cfg; t->B = B; t->N = N;
-    t->D = cfg->nf; t->De = cfg->nf / 4; t->T = cfg->nf * 4; t->L = cfg->n_layers; t->H = cfg->n_heads; t->XH = cfg->n_extra;
+    t->D = cfg->nf; t->De = cfg->nf / 4; t->T = cfg->nf * 4; t->L = cfg->n_layers; t->H = cfg->n_heads; t->XH = cfg->n_extra; t->NCo = 1 + cfg->n_extra;
     t->C = t->D / t->H; t->SC = (t->H * t->C) / (t->H - t->XH); t->QK = (t->H - t->XH) * t->SC; t->r = cfg->mlp_ratio; t->nd = cfg->in_node_dim;
     t->ch = cfg->edge_ch; t->cc = cfg->cond_ch; t->cn = (2 * t->D) / t->L; t->ce = (2 * t->De) / t->L; t->catn = t->D + t->L * t->cn;
     t->cate = t->De + t->L * t->ce;
@@ -978,7 +989,7 @@ int jodo_train_create(const jodo_cfg* cfg, int B, int N, const int32_t* n_nodes,
         k.ff1 = lin(p + "ff_linear1", r * D, D); k.ff2 = lin(p + "ff_linear2", D, r * D); k.ff3 = lin(p + "ff_linear3", r * De, De); k.ff4 = lin(p + "ff_linear4", De, r * De);
         k.eq_scale = find(p + "equi_update.coord_norm.scale", 1); k.eq_time = lin(p + "equi_update.time_mlp.1", 2 * D, T);
         k.eq_in = lin(p + "equi_update.input_lin", D, 2 * D + 2 * De); k.eq_c0 = lin(p + "equi_update.coord_mlp.0", D, D);
-        k.eq_c2 = find(p + "equi_update.coord_mlp.2.weight", 3 * D);
+        k.eq_c2 = find(p + "equi_update.coord_mlp.2.weight", (size_t)t->NCo * D);
         k.node_time = lin(p + "node_time_mlp.1", 6 * D, T); k.edge_time = lin(p + "edge_time_mlp.1", 6 * De, T);
         k.gbf_means = find(p + "dist_layer.means.weight", De - 1); k.gbf_stds = find(p + "dist_layer.stds.weight", De - 1);
         k.gbf_time = lin(p + "dist_layer.time_mlp.1", 2, T);
@@ -986,7 +997,7 @@ int jodo_train_create(const jodo_cfg* cfg, int B, int N, const int32_t* n_nodes,
     }
     if (!missing.empty()) { delete t; return jodo_set_error(JODO_ERR_ARG, "jodo_train_create: parameter '%s' missing or mis-sized", missing.c_str()); }
     {
-        const FusedDims fd{t->D, t->De, t->r, t->QK, t->ce, t->L};
+        const FusedDims fd{t->D, t->De, t->r, t->QK, t->ce, t->L, t->NCo};
         t->fused = fused_available(fd) ? 1 : 0;
         t->fused_bwd = t->fused;
         t->save_activations = 1;
@@ -1023,12 +1034,12 @@ int jodo_train_set_option(jodo_train* t, int option, int value) {
     if (option == 3) { t->group_dw = value; return JODO_OK; }
     if (option == 5) { t->gbf_chunk = value; return JODO_OK; }
     if (option == 4) {
-        if (value && !(fused_available(FusedDims{t->D, t->De, t->r, t->QK, t->ce, t->L}) && fused_attention_available(t->D, t->H, t->N)))
+        if (value && !(fused_available(FusedDims{t->D, t->De, t->r, t->QK, t->ce, t->L, t->NCo}) && fused_attention_available(t->D, t->H, t->N)))
             return jodo_set_error(JODO_ERR_UNSUPPORTED, "jodo_train_set_option: the fused attention kernels are not built for this shape");
         t->fused_attn = value;
         return JODO_OK;
     }
-    const FusedDims fd{t->D, t->De, t->r, t->QK, t->ce, t->L};
+    const FusedDims fd{t->D, t->De, t->r, t->QK, t->ce, t->L, t->NCo};
     if (value && !fused_available(fd)) return jodo_set_error(JODO_ERR_UNSUPPORTED, "jodo_train_set_option: fused chains are not built for this shape");
     if (option == 0) t->fused = value; else t->fused_bwd = value;
     return JODO_OK;

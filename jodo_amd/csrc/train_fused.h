@@ -19,7 +19,8 @@
 
 namespace jt {
 
-struct FusedDims { int D, De, r, QK, ce, L; };
+struct FusedDims { int D, De, r, QK, ce, L; int nco = 3; };      // nco: coordinate heads of chain C / C' (rows of coord_mlp.2): 3 with the two
+                                                                  // adjacency heads (DGT_concat), 1 without them (DGT_concat_sim)
 
 // floats of packed operands per block; offsets (floats) of the pieces inside a block's slice
 struct FusedPackLayout { size_t ee, l0, l1, ff3, ff4, ero, in_eg, c0, tab, total;                      // forward images
@@ -47,7 +48,7 @@ void fused_chain_a(hipStream_t s, const FusedDims& d, const FusedTopo& t, const 
 void fused_chain_b(hipStream_t s, const FusedDims& d, const FusedTopo& t, const FusedBlockParams& p, const float* packed, const float* e_in, const float* n2e,
                    const float* emod, Drop drop_a3, Drop drop_f4, float* xh_en, float* rs_en, float* en, float* f3, float* a3, float* f4, float* e_out,
                    float* eh, int ld_eh, int eh_col);
-// chain C.  hr / hc [Nn, D] = W_row h, W_col h; qmod [B, 2 D] (shift at 0, scale at D)
+// chain C.  hr / hc [Nn, D] = W_row h, W_col h; qmod [B, 2 D] (shift at 0, scale at D); inv [R, d.nco]
 void fused_chain_c(hipStream_t s, const FusedDims& d, const FusedTopo& t, const FusedBlockParams& p, const float* packed, const float* e_in, const float* G,
                    const float* hr, const float* hc, const float* qmod, float* xh_pre, float* rs_pre, float* u, float* c0pre, float* c0a, float* inv);
 
@@ -56,7 +57,7 @@ void fused_chain_c(hipStream_t s, const FusedDims& d, const FusedTopo& t, const 
 // wave and stores exactly the arrays the remaining launches read: the dY operands of the weight-gradient products (which stay GEMMs: their
 // contraction index is the row) and of the per-molecule modulation sums.
 // chain C':  dinv (in place: x (1 - inv^2)) -> d coord_mlp.0 output dc0 [R, D] -> du = W0^T dc0 [R, D] -> LayerNorm + modulate backward ->
-//            dpre [R, D] -> de += W_e^T dpre, dG = W_g^T dpre
+//            dpre [R, D] -> de += W_e^T dpre, dG = W_g^T dpre.   inv, dinv [R, d.nco]
 void fused_bwd_c(hipStream_t s, const FusedDims& d, const FusedTopo& t, const FusedBlockParams& p, const float* packed, const float* inv, float* dinv,
                  const float* c0pre, const float* xh_pre, const float* rs_pre, const float* qmod, float* dc0, float* du, float* dpre, float* de, float* dG);
 // chain B':  de_out -> f4d = dropout(f4) (for d g2), df4 = g2 de_out mask -> dhid = (W4^T df4) mask3 SiLU'(f3) [R, r De] -> den = de_out + W3^T dhid

@@ -234,7 +234,8 @@ struct ArgsC {
     float *xh, *rs, *u, *c0pre, *c0a, *inv;
 };
 
-template <int D>
+// NC: coordinate heads = rows of coord_mlp.2 (3: DGT_concat; 1: DGT_concat_sim), as NC in the inference kernels (dgt_kernels_wide.h)
+template <int D, int NC>
 __global__ __launch_bounds__(64, 1) void k_chain_c(ArgsC A) {
     using X = FD<D>;
     const int lane = threadIdx.x & 63, j = lane & 31, half = lane >> 5;
@@ -270,30 +271,34 @@ __global__ __launch_bounds__(64, 1) void k_chain_c(ArgsC A) {
     const float* mr = A.qmod + (long)mol * 2 * D;
     modulate<X::ND>(u, mr, mr + D, half);
     if (keep) store_nat<X::ND>(A.u + r * D, half, u);
-    float c0 = 0.f, c1 = 0.f, c2 = 0.f;
+    float ch[NC];
+#pragma unroll
+    for (int h = 0; h < NC; ++h) ch[h] = 0.f;
 #pragma unroll 1
     for (int b = 0; b < X::ND; ++b) {                                 // coord_mlp.0 -> SiLU -> coord_mlp.2
         const unsigned cur = A.c.oC0 + (unsigned)(b * X::KQD) * 1024;
         const int f0 = b * 32 + half * 16;
-        float bb[16], k0[16], k1[16], k2[16], pre[16], act[16];
+        float bb[16], kw[NC][16], pre[16], act[16];
         load16(A.b0 + f0, bb);
-        load16(A.w2 + f0, k0);
-        load16(A.w2 + D + f0, k1);
-        load16(A.w2 + 2 * D + f0, k2);
+#pragma unroll
+        for (int h = 0; h < NC; ++h) load16(A.w2 + h * D + f0, kw[h]);
         f32x16 acc = mfma_block_p<X::KQD>(wp, ws, cur, b + 1 < X::ND ? cur + X::KQD * 1024 : A.c.oC0, u, zero16());
 #pragma unroll
         for (int s = 0; s < 16; s += 2) {
             const f32x2 p = pk2(acc[s], acc[s + 1]) + pk2(bb[s], bb[s + 1]);
             const f32x2 v = silu_f2(p);
             pre[s] = p.x; pre[s + 1] = p.y; act[s] = v.x; act[s + 1] = v.y;
-            c0 = fmaf(v.x, k0[s], c0); c0 = fmaf(v.y, k0[s + 1], c0);
-            c1 = fmaf(v.x, k1[s], c1); c1 = fmaf(v.y, k1[s + 1], c1);
-            c2 = fmaf(v.x, k2[s], c2); c2 = fmaf(v.y, k2[s + 1], c2);
+#pragma unroll
+            for (int h = 0; h < NC; ++h) { ch[h] = fmaf(v.x, kw[h][s], ch[h]); ch[h] = fmaf(v.y, kw[h][s + 1], ch[h]); }
         }
         if (keep) { store16(A.c0pre + r * D + f0, pre); store16(A.c0a + r * D + f0, act); }
     }
-    c0 = tanh_f(pair_sum(c0)); c1 = tanh_f(pair_sum(c1)); c2 = tanh_f(pair_sum(c2));
-    if (valid && half == 0) { A.inv[r * 3] = c0; A.inv[r * 3 + 1] = c1; A.inv[r * 3 + 2] = c2; }
+#pragma unroll
+    for (int h = 0; h < NC; ++h) ch[h] = tanh_f(pair_sum(ch[h]));
+    if (valid && half == 0) {
+#pragma unroll
+        for (int h = 0; h < NC; ++h) A.inv[r * NC + h] = ch[h];
+    }
 }
 
 // d/dx x sigmoid(x) = s (1 + x (1 - s)), element pairs on the packed pipe
@@ -348,7 +353,7 @@ struct ArgsBC {
     float *dinv, *dc0, *du, *dpre, *de, *dG;
 };
 
-template <int D>
+template <int D, int NC>
 __global__ __launch_bounds__(64, 1) void k_bwd_c(ArgsBC A) {
     using X = FD<D>;
     const int lane = threadIdx.x & 63, j = lane & 31, half = lane >> 5;
@@ -356,10 +361,11 @@ __global__ __launch_bounds__(64, 1) void k_bwd_c(ArgsBC A) {
     const bool valid = r < A.c.R;
     const long rc = valid ? r : (long)A.c.R - 1;
     const int mol = A.c.em[rc];
-    float d0, d1, d2;
-    {
-        const float i0 = A.inv[rc * 3], i1 = A.inv[rc * 3 + 1], i2 = A.inv[rc * 3 + 2];
-        d0 = A.dinv[rc * 3] * (1.f - i0 * i0); d1 = A.dinv[rc * 3 + 1] * (1.f - i1 * i1); d2 = A.dinv[rc * 3 + 2] * (1.f - i2 * i2);
+    float dh[NC];
+#pragma unroll
+    for (int h = 0; h < NC; ++h) {
+        const float iv = A.inv[rc * NC + h];
+        dh[h] = A.dinv[rc * NC + h] * (1.f - iv * iv);
     }
     const WSrc ws = make_wsrc(A.c.packed, lane);
     WPipe<X::PG> wp;
@@ -368,19 +374,27 @@ __global__ __launch_bounds__(64, 1) void k_bwd_c(ArgsBC A) {
 #pragma unroll
     for (int b = 0; b < X::ND; ++b) {                                 // dc0 = (W2^T dinv') SiLU'(c0pre)
         const int f0 = b * 32 + half * 16;
-        float k0[16], k1[16], k2[16], pre[16], o[16];
-        load16(A.w2 + f0, k0); load16(A.w2 + D + f0, k1); load16(A.w2 + 2 * D + f0, k2);
+        float kw[NC][16], pre[16], o[16];
+#pragma unroll
+        for (int h = 0; h < NC; ++h) load16(A.w2 + h * D + f0, kw[h]);
         load16(A.c0pre + rc * D + f0, pre);
 #pragma unroll
         for (int s = 0; s < 16; s += 2) {
-            const f32x2 da = pk2(fmaf(d0, k0[s], fmaf(d1, k1[s], d2 * k2[s])), fmaf(d0, k0[s + 1], fmaf(d1, k1[s + 1], d2 * k2[s + 1])));
+            // W2^T dinv' summed from the last head down: dh[0] k0 + (dh[1] k1 + dh[2] k2) with three heads
+            float da0 = dh[NC - 1] * kw[NC - 1][s], da1 = dh[NC - 1] * kw[NC - 1][s + 1];
+#pragma unroll
+            for (int h = NC - 2; h >= 0; --h) { da0 = fmaf(dh[h], kw[h][s], da0); da1 = fmaf(dh[h], kw[h][s + 1], da1); }
+            const f32x2 da = pk2(da0, da1);
             const f32x2 g = da * dsilu_f2(pk2(pre[s], pre[s + 1]));
             o[s] = g.x; o[s + 1] = g.y; v[b * 16 + s] = g.x; v[b * 16 + s + 1] = g.y;
         }
         if (valid) store16(A.dc0 + r * D + f0, o);
     }
     __syncthreads();                                                  // (one wave: orders the in-place dinv update behind every lane's read)
-    if (valid && half == 0) { A.dinv[r * 3] = d0; A.dinv[r * 3 + 1] = d1; A.dinv[r * 3 + 2] = d2; }
+    if (valid && half == 0) {
+#pragma unroll
+        for (int h = 0; h < NC; ++h) A.dinv[r * NC + h] = dh[h];
+    }
     float u[X::HD];
 #pragma unroll
     for (int b = 0; b < X::ND; ++b) {                                 // du = W0^T dc0
@@ -735,7 +749,7 @@ FusedPackLayout fused_pack_layout(const FusedDims& d) {
 
 bool fused_available(const FusedDims& d) {
     return (d.D == 128 || d.D == 256 || d.D == 384) && (d.r == 2 || d.r == 4) && d.De == d.D / 4 && d.ce >= 1 && d.ce <= 32 && d.QK % 2 == 0 &&
-           d.QK <= d.D && (d.r * d.De) % 64 == 0;
+           d.QK <= d.D && (d.r * d.De) % 64 == 0 && (d.nco == 1 || d.nco == 3);
 }
 
 void fused_pack_block(hipStream_t s, const FusedDims& d, const FusedBlockParams& p, float* packed) {
@@ -794,9 +808,10 @@ void fused_chain_c(hipStream_t s, const FusedDims& d, const FusedTopo& t, const 
     A.e_in = e_in; A.G = G; A.hr = hr; A.hc = hc; A.in_b = p.in_b; A.qmod = qmod; A.b0 = p.c0_b; A.w2 = p.c2_w;
     A.xh = xh_pre; A.rs = rs_pre; A.u = u; A.c0pre = c0pre; A.c0a = c0a; A.inv = inv;
     const dim3 grid((unsigned)((t.R + 31) / 32));
-    if (d.D == 128) hipLaunchKernelGGL(k_chain_c<128>, grid, dim3(64), 0, s, A);
-    else if (d.D == 256) hipLaunchKernelGGL(k_chain_c<256>, grid, dim3(64), 0, s, A);
-    else hipLaunchKernelGGL(k_chain_c<384>, grid, dim3(64), 0, s, A);
+#define JT_C(DD) do { if (d.nco == 1) hipLaunchKernelGGL((k_chain_c<DD, 1>), grid, dim3(64), 0, s, A); \
+                      else hipLaunchKernelGGL((k_chain_c<DD, 3>), grid, dim3(64), 0, s, A); } while (0)
+    if (d.D == 128) JT_C(128); else if (d.D == 256) JT_C(256); else JT_C(384);
+#undef JT_C
 }
 
 void fused_pack_block_bwd(hipStream_t s, const FusedDims& d, const FusedBlockParams& p, float* packed) {
@@ -827,9 +842,10 @@ void fused_bwd_c(hipStream_t s, const FusedDims& d, const FusedTopo& t, const Fu
     A.inv = inv; A.c0pre = c0pre; A.xh = xh_pre; A.rs = rs_pre; A.qmod = qmod; A.w2 = p.c2_w;
     A.dinv = dinv; A.dc0 = dc0; A.du = du; A.dpre = dpre; A.de = de; A.dG = dG;
     const dim3 grid((unsigned)((t.R + 31) / 32));
-    if (d.D == 128) hipLaunchKernelGGL(k_bwd_c<128>, grid, dim3(64), 0, s, A);
-    else if (d.D == 256) hipLaunchKernelGGL(k_bwd_c<256>, grid, dim3(64), 0, s, A);
-    else hipLaunchKernelGGL(k_bwd_c<384>, grid, dim3(64), 0, s, A);
+#define JT_C(DD) do { if (d.nco == 1) hipLaunchKernelGGL((k_bwd_c<DD, 1>), grid, dim3(64), 0, s, A); \
+                      else hipLaunchKernelGGL((k_bwd_c<DD, 3>), grid, dim3(64), 0, s, A); } while (0)
+    if (d.D == 128) JT_C(128); else if (d.D == 256) JT_C(256); else JT_C(384);
+#undef JT_C
 }
 
 void fused_bwd_b(hipStream_t s, const FusedDims& d, const FusedTopo& t, const FusedBlockParams& p, const float* packed, const float* de_out, const float* f4,

@@ -720,7 +720,10 @@ __global__ void k_attn_bwd_t0(Topo t, int H, int XH, int SC, float inv_sqrt_c, c
 }
 
 // ================================================================ coordinate update (MultiCondEquiUpdate, mol_gnn.py:85-92) =====
-// trans[(a, c)] = CoorsNorm(x_a - x_c) * mean(inv * [1, adj2d, adjsp])    (0 on the diagonal)
+// trans[(a, c)] = CoorsNorm(x_a - x_c) * iota    (0 on the diagonal)
+//   NH = 3 (MultiCondEquiUpdate, inv [R, 3]): iota = mean(inv * [1, adj2d, adjsp]);   NH = 1 (CondEquiUpdate, mol_gnn.py:16-48, inv [R, 1]): iota = inv, the
+//   adjacency flags are not read
+template <int NH>
 __global__ void k_coord_fwd(Topo t, const float* __restrict__ pos, const float* __restrict__ inv, const float* __restrict__ adj2d,
                             const float* __restrict__ adjsp, const float* __restrict__ scale, float* __restrict__ trans) {
     JT_IDX(t.R);
@@ -729,7 +732,9 @@ __global__ void k_coord_fwd(Topo t, const float* __restrict__ pos, const float* 
         const float* pa = pos + (long)t.edge_a[i_] * 3; const float* pc = pos + (long)t.edge_c[i_] * 3;
         const float dx = pa[0] - pc[0], dy = pa[1] - pc[1], dz = pa[2] - pc[2];
         const float nrm = fmaxf(sqrtf(dx * dx + dy * dy + dz * dz), 1e-8f);
-        const float iota = (inv[i_ * 3] + inv[i_ * 3 + 1] * adj2d[i_] + inv[i_ * 3 + 2] * adjsp[i_]) / 3.f;
+        float iota;
+        if constexpr (NH == 1) iota = inv[i_];
+        else iota = (inv[i_ * 3] + inv[i_ * 3 + 1] * adj2d[i_] + inv[i_ * 3 + 2] * adjsp[i_]) / 3.f;
         const float s = scale[0];
         o0 = dx / nrm * s * iota; o1 = dy / nrm * s * iota; o2 = dz / nrm * s * iota;
     }
@@ -763,7 +768,9 @@ __global__ void k_nan_flag(long n, const float* __restrict__ x, int* __restrict_
     if (x[i_] != x[i_]) flag[0] = 1;
 }
 // backward of the coordinate update for one edge row, given dxp = d loss / d x_pre (already centred):
-//   dtrans = dxp[a];  dinv[k] = s (u . dtrans) adj_k / 3;  part of ddiff through CoorsNorm;  ds partial = iota (u . dtrans)
+//   dtrans = dxp[a];  dinv[k] = s (u . dtrans) adj_k / 3  (NH = 1: dinv = s (u . dtrans), [R, 1]);  part of ddiff through CoorsNorm;
+//   ds partial = iota (u . dtrans)
+template <int NH>
 __global__ void k_coord_bwd(Topo t, const float* __restrict__ pos, const float* __restrict__ inv, const float* __restrict__ adj2d,
                             const float* __restrict__ adjsp, const float* __restrict__ scale, const float* __restrict__ dxp,
                             float* __restrict__ dinv, float* __restrict__ ddiff, float* __restrict__ dscale_row) {
@@ -775,18 +782,24 @@ __global__ void k_coord_bwd(Topo t, const float* __restrict__ pos, const float* 
         const float raw = sqrtf(dx * dx + dy * dy + dz * dz);
         const float nrm = fmaxf(raw, 1e-8f);
         const float ux = dx / nrm, uy = dy / nrm, uz = dz / nrm;
-        const float iota = (inv[i_ * 3] + inv[i_ * 3 + 1] * adj2d[i_] + inv[i_ * 3 + 2] * adjsp[i_]) / 3.f;
+        float iota;
+        if constexpr (NH == 1) iota = inv[i_];
+        else iota = (inv[i_ * 3] + inv[i_ * 3 + 1] * adj2d[i_] + inv[i_ * 3 + 2] * adjsp[i_]) / 3.f;
         const float s = scale[0];
         const float* dt = dxp + (long)t.edge_a[i_] * 3;
         const float ud = ux * dt[0] + uy * dt[1] + uz * dt[2];
-        const float di = s * ud / 3.f;
-        di0 = di; di1 = di * adj2d[i_]; di2 = di * adjsp[i_];
+        if constexpr (NH == 1) di0 = s * ud;
+        else {
+            const float di = s * ud / 3.f;
+            di0 = di; di1 = di * adj2d[i_]; di2 = di * adjsp[i_];
+        }
         ds = iota * ud;
         const float w = s * iota / nrm;
         if (raw > 1e-8f) { g0 = w * (dt[0] - ux * ud); g1 = w * (dt[1] - uy * ud); g2 = w * (dt[2] - uz * ud); }
         else { g0 = w * dt[0]; g1 = w * dt[1]; g2 = w * dt[2]; }
     }
-    dinv[i_ * 3] = di0; dinv[i_ * 3 + 1] = di1; dinv[i_ * 3 + 2] = di2;
+    if constexpr (NH == 1) dinv[i_] = di0;
+    else { dinv[i_ * 3] = di0; dinv[i_ * 3 + 1] = di1; dinv[i_ * 3 + 2] = di2; }
     ddiff[i_ * 3] = g0; ddiff[i_ * 3 + 1] = g1; ddiff[i_ * 3 + 2] = g2;
     dscale_row[i_] = ds;
 }

@@ -151,11 +151,12 @@ def get_step_fn(noise_scheduler, train, optimize_fn, scaler, config, prop_dist=N
     def step_fn(state, batch):
         model = state['model']
         if train:
-            if config.only_2D:
-                # asking for a training step is the opt-in to the 2-D model's HIP training path (models/dgt2d.py hip_training)
-                inner = getattr(model, 'module', model)
-                if hasattr(inner, 'hip_training'):
-                    inner.hip_training = True
+            # asking for a training step is the opt-in to the HIP training path of the modules that have the switch: the 2-D models
+            # (models/dgt2d.py, models/cdgs.py) and, among the 3-D ones, DGT_concat_sim (models/dgt.py).  DGT_concat and
+            # cond_DGT_concat have no such attribute: their grad-enabled calls always train
+            inner = getattr(model, 'module', model)
+            if hasattr(inner, 'hip_training'):
+                inner.hip_training = True
             optimizer = state['optimizer']
             optimizer.zero_grad()
             loss = loss_fn(model, batch)

@@ -14,7 +14,8 @@ in /root/reference/models/mol_gnn.py (:410-594, :597-794, :949-1124):
 The arithmetic is NOT done by these torch modules: `forward` packs the weights once (MFMA operand
 order, csrc/dgt_pack.cpp), builds a plan per batch of atom counts, and calls
 `jodo_dgt_forward` in libjodo_hip.so on the current HIP stream.  There is no CPU or eager fallback:
-on a non-GPU tensor, with gradients enabled, or with an unsupported config, forward raises.
+on a non-GPU tensor, with an unsupported config, or — DGT_concat_sim without its `hip_training` opt-in — with gradients enabled,
+forward raises; a grad-enabled call otherwise runs the HIP training path (csrc/dgt_train.hip, jodo_amd/train.py).
 """
 import ctypes
 
@@ -515,14 +516,25 @@ class DGT_concat_sim(_DGTBase):
     """Diffusion Graph Transformer with self-conditioning, without extra attention heads (HIP): the reference's EquivariantBlock /
     Trans_Layer / CondEquiUpdate (mol_gnn.py:949-1124, :97-208, :16-48; layers.py:13-89).  16 learned heads of nf / 16 channels, softmax over
     the real incoming edges, one coordinate head; `n_extra_heads`, `trans_name`, `softmax_inf` and `edge_quan_th` are never read and
-    `spatial_cut_off` has no effect.  Built for nf = 256 (both 3-D JODO configs), inference only, exact fp32."""
+    `spatial_cut_off` has no effect.  Built for nf = 256 (both 3-D JODO configs), exact fp32.
+
+    Training is opt-in: with `model.hip_training = True` (jodo_amd.losses.get_step_fn sets it when asked for a training step) a
+    grad-enabled call — and, under model.train() with dropout > 0, the no-grad self-conditioning call too — runs csrc/dgt_train.hip
+    through jodo_amd.train.TrainEngine like DGT_concat's (dropout in the two feed-forwards; the reference builds this block's Trans_Layer
+    without a dropout argument, mol_gnn.py:116), and `loss.backward()` fills every parameter's gradient; a default module keeps refusing
+    such calls."""
     conditional = False
     extra_heads = 0
+
+    def __init__(self, config):
+        super().__init__(config)
+        self.hip_training = False     # opt-in: grad-enabled calls go through the HIP training path (csrc/dgt_train.hip with n_extra = 0)
 
     def forward(self, t, xh, node_mask, edge_mask, context=None, *args, **kwargs):
         if self.split_bf16:
             raise NotImplementedError("DGT_concat_sim has no split-bf16 form: leave model.split_bf16 = False (the exact-fp32 kernels)")
-        if (torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())) or (self.training and self.dropout_p > 0):
-            raise NotImplementedError("DGT_concat_sim is built for inference: call it under torch.no_grad() in eval() mode "
-                                      "(training this model on the GPU is not implemented)")
+        if not self.hip_training and ((torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()))
+                                      or (self.training and self.dropout_p > 0)):
+            raise NotImplementedError("DGT_concat_sim is built for inference by default: call it under torch.no_grad() in eval() mode, or set "
+                                      "model.hip_training = True for the HIP training path (jodo_amd.losses.get_step_fn does)")
         return super().forward(t, xh, node_mask, edge_mask, context, *args, **kwargs)

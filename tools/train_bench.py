@@ -4,11 +4,18 @@ double forward, dropout 0.1, loss.backward() through jodo_train_backward, AdamW 
 
     python tools/train_bench.py [--workload qm9|geom] [--batch B] [--steps K] [--warmup W]
     python tools/train_bench.py --workload zinc2d|moses2d [--steps K] [--warmup W] [--runs R]
+    python tools/train_bench.py --workload sim [--steps K] [--warmup W] [--runs R]
 
 The 2-D workloads (DGT_concat_2D, batch 128, atom counts from tests/golden/n_nodes_2d.json, a new CPU batch every step) time the HIP
 step (csrc/dgt2d_train.hip, fused and op-by-op form) and, on the same GPU under the same loss, optimiser and batches, the dense
 torch step — autograd through tests/oracle2d.forward_dense on the device, the baseline of tools/bench_2d.py.  The forms alternate inside
 one command, R runs each; the result (with the spread of the runs) is written to profiles/train2d_{zinc,moses}_b128.json.
+
+The sim workload is the QM9 training benchmark with the model name switched to DGT_concat_sim (the 3-D score network without extra
+attention heads: csrc/dgt_train.hip with n_extra = 0), batch 128, a new CPU batch every step, forward + backward + optimiser.  A
+DGT_concat leg alternates with it inside the command on the same batches, R >= 3 runs each, timed with device events; step times, their
+ratio, the spread of the runs and the kernel launches of a step go to profiles/dgt_sim_train_qm9_b128.json.  `--workload sim --legs
+dgt_concat` times the DGT_concat leg alone (it needs nothing of the sim model: the same command runs on an older checkout's library).
 
 Work model: a grad-enabled forward + backward costs 3 x the forward's projection flops (forward, input gradient, weight gradient);
 the no-grad self-conditioning forward (half of the steps) one more; `gemm_flops_per_step` prices the projections only
@@ -276,6 +283,101 @@ def run_2d(workload='zinc2d', steps=10, warmup=3, seed=42, runs=2, batch=128):
     return out
 
 
+def count_launches(fn):
+    """Kernel launches of one call of fn() as torch's profiler sees them on the device (None when the profiler records no device activity)."""
+    from torch.profiler import ProfilerActivity, profile
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    n = sum(1 for e in prof.events() if str(getattr(e, 'device_type', '')).endswith('CUDA') and 'memcpy' not in e.name.lower()
+            and 'memset' not in e.name.lower())
+    return n or None
+
+
+def run_sim(steps=10, warmup=3, seed=42, runs=3, batch=128, legs=('dgt_concat', 'sim')):
+    """QM9 training step of DGT_concat_sim beside DGT_concat's: the legs alternate inside one command on the same CPU batches (a new one
+    every step, moved to the device inside the step as in the reference loop), `runs` runs each, HIP events around the `steps` timed steps
+    (the step has no host synchronisation of its own; the events bracket the device work of the whole window)."""
+    from jodo_amd import configs, losses as L
+    from jodo_amd.diffusion import NoiseScheduleVP
+    from jodo_amd.models import get_model_class, deterministic_init_, load_dataset_info, get_node_dist
+    from jodo_amd.models.ema import ExponentialMovingAverage
+    from jodo_amd.utils import get_data_scaler
+    if runs < 3:
+        raise ValueError("--workload sim: at least three runs per leg (got %d)" % runs)
+    dev = torch.device('cuda:0')
+    names = dict(dgt_concat='DGT_concat', sim='DGT_concat_sim')
+    torch.manual_seed(seed)
+    dist_ = get_node_dist(load_dataset_info('qm9_with_h'))
+    base = configs.get('vpsde_qm9_uncond_jodo')
+    n_batches = warmup + steps
+    counts = [dist_.sample(batch).tolist() for _ in range(n_batches)]
+    batches = [synthetic_batch(base, nk, seed + 1 + k) for k, nk in enumerate(counts)]
+
+    def make(leg):
+        cfg = configs.get('vpsde_qm9_uncond_jodo')
+        cfg.model.name = names[leg]
+        cfg.device = dev
+        model = deterministic_init_(get_model_class(cfg.model.name)(cfg), seed=seed).to(dev)
+        ns = NoiseScheduleVP(cfg.sde.schedule, continuous_beta_0=cfg.sde.continuous_beta_0, continuous_beta_1=cfg.sde.continuous_beta_1)
+        state = dict(model=model, optimizer=L.get_optimizer(cfg, model.parameters()),
+                     ema=ExponentialMovingAverage(model.parameters(), decay=cfg.model.ema_decay), step=1)
+        return state, L.get_step_fn(ns, True, L.optimization_manager(cfg), get_data_scaler(cfg), cfg)
+
+    made = {leg: make(leg) for leg in legs}
+    times = {leg: [] for leg in legs}
+    losses, launches = {}, {}
+    for r in range(runs):
+        for leg in legs:                                      # the legs alternate inside one command
+            state, step_fn = made[leg]
+            torch.manual_seed(seed + r)
+            random.seed(seed + r)
+            for k in range(warmup):
+                float(step_fn(state, batches[k]))
+            torch.cuda.synchronize()
+            n_selfcond = _same_coin_flips(seed + 7, steps)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            held = [step_fn(state, batches[warmup + k]).detach() for k in range(steps)]
+            e1.record()
+            torch.cuda.synchronize()
+            times[leg].append(e0.elapsed_time(e1) / steps)
+            losses[leg] = float(held[-1])
+    for leg in legs:                                          # kernel launches of one step with / without the self-conditioning forward
+        state, step_fn = made[leg]
+        launches[leg] = {}
+        for what in ('self_conditioned_step', 'plain_step'):
+            want = what == 'self_conditioned_step'
+            s_ = 0
+            while True:                                       # a python-random seed whose first draw takes / skips the self-conditioning branch
+                random.seed(s_)
+                if (random.random() < 0.5) == want:
+                    break
+                s_ += 1
+            random.seed(s_)
+            try:
+                launches[leg][what] = count_launches(lambda: step_fn(state, batches[0]))
+            except Exception as exc:                          # the count is a by-product: the timings stand without it
+                launches[leg][what] = None
+                launches[leg]['error'] = repr(exc)[:200]
+    out = dict(workload='vpsde_qm9_uncond_jodo', batch=batch, steps=steps, warmup=warmup, runs=runs,
+               self_conditioned_steps='%d of %d in every timed window' % (n_selfcond, steps),
+               mean_sum_n2=sum(sum(n * n for n in c) for c in counts) / n_batches, legs={})
+    for leg in legs:
+        ts = sorted(times[leg])
+        med = ts[len(ts) // 2] if len(ts) % 2 else 0.5 * (ts[len(ts) // 2 - 1] + ts[len(ts) // 2])
+        out['legs'][leg] = dict(model=names[leg], ms_per_step_runs=times[leg], ms_per_step=med, ms_per_step_best=ts[0], spread_ms=ts[-1] - ts[0],
+                                molecules_per_s=batch / (med * 1e-3), loss_last=losses[leg], kernel_launches=launches[leg])
+    if 'sim' in out['legs'] and 'dgt_concat' in out['legs']:
+        out['sim_over_dgt_concat'] = out['legs']['sim']['ms_per_step'] / out['legs']['dgt_concat']['ms_per_step']
+    out['note'] = ('one optimiser step = (50 %: no-grad self-conditioning forward) + grad forward + backward + FlatAdam / clipping / EMA on a new CPU '
+                   'batch of the QM9 atom-count histogram, dropout 0.1 active; both legs see the same batches and the same coin flips; '
+                   'ms_per_step = median of the runs (HIP events around the timed window / steps), spread_ms = max - min over the runs; every leg '
+                   'keeps its model and optimiser state across the runs; kernel_launches: device kernels of one step (torch profiler)')
+    return out
+
+
 def cpu_step(workload='qm9', batch=16, steps=2, seed=42, threads=16):
     """The same optimiser-free step on the host: forward + loss.backward() through the port of the reference's sparse formulation
     (oracle.forward_faithful under torch.autograd, eval-mode dropout) — what the reference's CPU training step costs, per molecule."""
@@ -319,8 +421,19 @@ if __name__ == '__main__':
     ap.add_argument('--cpu', action='store_true', help='also time the host port of the same forward + backward (small batch)')
     ap.add_argument('--train-opt', action='append', default=[], help='jodo_train_set_option=value (A/B runs), e.g. 0=0 1=0: op-by-op forward / backward')
     ap.add_argument('--save-always', action='store_true', help='the no-grad self-conditioning forward keeps its activations too (round-4 behaviour)')
-    ap.add_argument('--runs', type=int, default=2, help='2-D workloads: runs per form (the forms alternate)')
+    ap.add_argument('--runs', type=int, default=2, help='2-D workloads: runs per form (the forms alternate); --workload sim: runs per leg (at least 3)')
+    ap.add_argument('--legs', default='dgt_concat,sim', help='--workload sim: the legs to time (dgt_concat alone runs on a checkout without the sim training path)')
     a = ap.parse_args()
+    if a.workload == 'sim':
+        legs = tuple(a.legs.split(','))
+        out = run_sim(a.steps, a.warmup, runs=max(a.runs, 3), batch=a.batch or 128, legs=legs)
+        if (a.batch or 128) == 128 and set(legs) == {'dgt_concat', 'sim'}:
+            os.makedirs(os.path.join(ROOT, 'profiles'), exist_ok=True)
+            with open(os.path.join(ROOT, 'profiles', 'dgt_sim_train_qm9_b128.json'), 'w') as f:
+                json.dump(out, f, indent=1)
+                f.write('\n')
+        print(json.dumps(out))
+        sys.exit(0)
     if a.workload in ('zinc2d', 'moses2d'):
         out = run_2d(a.workload, a.steps, a.warmup, runs=a.runs, batch=a.batch or 128)
         if (a.batch or 128) == 128:
