@@ -417,6 +417,55 @@ int jodo_train_gemm_s(int tA, int tB, int M, int N, int K, const float* A, int l
                       const float* bias, int acc, int act, float* out2, float* dbias, float dropout_p, uint64_t seed, int site,
                       float* ws, size_t ws_floats, void* stream);
 
+/* tests: ONE public function of csrc/train_fused.h on caller-owned device arrays (csrc/train_debug.hip; tests/test_fused_kernels_gpu.py
+ * compares every array the kernel stores with a float64 restatement).  The entry adds no kernel: it fills FusedDims / FusedBlockParams /
+ * FusedTopo / AttnTopo / Drop from the struct and calls the host function named by `op`.  It is the safety boundary of those tests, so
+ * nothing is launched unless every check below holds:
+ *   - the op's availability predicate (fused_available, fused_chain_b_available, fused2d_available, fused_attention_available; F in
+ *     {128, 256, 384} for the node pair, 2 <= De <= 129 for the Gaussian backward) -> JODO_ERR_UNSUPPORTED naming the values;
+ *   - the topology is HOST memory: every index is checked against R / Nn / B / N, the offsets for monotonicity and consistency with nn
+ *     (node_off[b + 1] = node_off[b] + nn[b], edge_off[b + 1] = edge_off[b] + nn[b]^2, totals Nn and R, node_mol constant on a molecule's
+ *     rows); the entry uploads it into topo_dev (int32, topo_dev_count >= what the op uploads) on `stream` in front of the launch;
+ *   - every array the op reads or writes is a slot a[JODO_FT_*] with its element count n[.]: non-NULL, 16-byte aligned (4 for the strided arrays, which are
+ *     read float by float), and at least as long as what the op touches (strided arrays: (rows - 1) ld + width);
+ *   - a NULL pointer, a non-positive count, an unknown op, an offset or stride that does not hold its columns -> JODO_ERR_ARG.
+ * Slots an op does not use are ignored.  Which slot is which argument: the table in front of each case in csrc/train_debug.hip;
+ * the node pair reads a / res_b from E_IN / N2E and dy from DE_OUT, writes XH / RS / E_OUT (y) and DE_PREV (dx); the attention's q | k | v
+ * and d q | d k | d v are three slots each with their own row stride (they may point into one merged array); the Gaussian backward reads
+ * its row gradient from DG (ldg, gcol).  Optional slots (NULL allowed): N2E of JODO_FT_NODE_LN_MOD (no residual), DD2. */
+enum { JODO_FT_PACK = 0, JODO_FT_PACK_BWD, JODO_FT_PACK_2D, JODO_FT_PACK_2D_BWD, JODO_FT_CHAIN_A, JODO_FT_CHAIN_B, JODO_FT_CHAIN_C,
+       JODO_FT_BWD_A, JODO_FT_BWD_B, JODO_FT_BWD_C, JODO_FT_CHAIN_A_2D, JODO_FT_BWD_A_2D, JODO_FT_NODE_LN_MOD, JODO_FT_NODE_LN_MOD_BWD,
+       JODO_FT_ATTN_FWD, JODO_FT_ATTN_BWD, JODO_FT_GBF_BWD, JODO_FT_N_OPS };
+enum { JODO_FT_EDGE_EMB_W = 0, JODO_FT_EDGE_EMB_B, JODO_FT_LE0, JODO_FT_LE1, JODO_FT_FF3_W, JODO_FT_FF3_B, JODO_FT_FF4_W, JODO_FT_FF4_B,
+       JODO_FT_ERO_W, JODO_FT_ERO_B, JODO_FT_IN_W, JODO_FT_IN_B, JODO_FT_C0_W, JODO_FT_C0_B, JODO_FT_C2_W, JODO_FT_N2E_B, JODO_FT_GBF_MEANS,
+       JODO_FT_GBF_STDS, JODO_FT_PACKED, JODO_FT_POS, JODO_FT_GM, JODO_FT_E_IN, JODO_FT_EMOD, JODO_FT_D2, JODO_FT_G, JODO_FT_XH, JODO_FT_RS,
+       JODO_FT_ET, JODO_FT_T0, JODO_FT_T1, JODO_FT_N2E, JODO_FT_EN, JODO_FT_F3, JODO_FT_A3, JODO_FT_F4, JODO_FT_E_OUT, JODO_FT_EH, JODO_FT_HR,
+       JODO_FT_HC, JODO_FT_QMOD, JODO_FT_U, JODO_FT_C0PRE, JODO_FT_C0A, JODO_FT_INV, JODO_FT_DINV, JODO_FT_DC0, JODO_FT_DU, JODO_FT_DPRE,
+       JODO_FT_DE, JODO_FT_DG, JODO_FT_DE_OUT, JODO_FT_F4D, JODO_FT_DF4, JODO_FT_DHID, JODO_FT_DEN, JODO_FT_DE_PREV, JODO_FT_DT1, JODO_FT_DT0,
+       JODO_FT_DET, JODO_FT_DE1, JODO_FT_MODS, JODO_FT_Q, JODO_FT_K, JODO_FT_V, JODO_FT_ADJ2D, JODO_FT_ADJSP, JODO_FT_ALPHA, JODO_FT_HHAT,
+       JODO_FT_DHHAT, JODO_FT_DS, JODO_FT_DQ, JODO_FT_DK, JODO_FT_DV, JODO_FT_DXP, JODO_FT_DD2, JODO_FT_PART_M, JODO_FT_PART_S,
+       JODO_FT_N_SLOTS };
+typedef struct {
+    int32_t op;
+    int32_t D, De, r, QK, ce, nco;                 /* FusedDims (De = D / 4; node pair: D = F; Gaussian backward: De alone) */
+    int32_t R, Nn, B, N;                           /* edge rows, node rows, molecules, atoms of the largest molecule */
+    int32_t save;                                  /* FusedTopo::save */
+    int32_t H, XH, SC, one_wave;                   /* attention: heads, adjacency heads in front, channels per learned score head */
+    int32_t ldqk, ldv, ldd_qk, ldd_v;              /* AttnTopo row strides */
+    int32_t ld_eh, eh_col;                         /* chain B: row stride and first column of the readout inside the head input */
+    int32_t ldm, g_off, sh_off, sc_off, acc;       /* node pair: stride and column offsets of mods; acc also of the Gaussian backward */
+    int32_t ldg, gcol;                             /* Gaussian backward: row stride and first column of d G */
+    int32_t site_a3, site_f4;                      /* dropout sites of chain B / B' (Drop::site) */
+    float drop_p, inv_sqrt_c;
+    uint64_t seed;
+    const int32_t *edge_a, *edge_c, *edge_mol, *row_mol, *node_mol, *nn, *node_off, *edge_off;    /* HOST: [R] x 3, [Nn] x 2, [B], [B + 1] x 2 */
+    int32_t* topo_dev;                             /* DEVICE scratch the entry uploads the topology into */
+    size_t topo_dev_count;
+    float* a[JODO_FT_N_SLOTS];                     /* DEVICE arrays */
+    size_t n[JODO_FT_N_SLOTS];                     /* their element counts */
+} jodo_fused_test_args;
+int jodo_train_debug_fused(const jodo_fused_test_args* args, void* stream);
+
 /* ---- optimiser side of the training step on flat buffers (csrc/train_step.hip; host mirror: jodo_amd/optim.py) ----------------------
  * jodo_adam_step  <- optimizer.step() of the optimisers get_optimizer builds, losses.py:14-26: torch.optim.AdamW(amsgrad=True,
  *   weight_decay=1e-12) (decoupled = 1) or torch.optim.Adam (decoupled = 0: L2 term added to the gradient), torch's single-tensor

@@ -231,6 +231,42 @@ def bind_cdgs_train(L):
     dhost.restype = p
 
 
+# ---- tests: jodo_train_debug_fused (include/jodo_hip.h; csrc/train_debug.hip) — one fused training kernel on caller-owned arrays.
+# The two name lists are the header's enums in order (tests/test_fused_kernels_host.py reads the header and compares).
+FT_OPS = ('PACK', 'PACK_BWD', 'PACK_2D', 'PACK_2D_BWD', 'CHAIN_A', 'CHAIN_B', 'CHAIN_C', 'BWD_A', 'BWD_B', 'BWD_C', 'CHAIN_A_2D', 'BWD_A_2D',
+          'NODE_LN_MOD', 'NODE_LN_MOD_BWD', 'ATTN_FWD', 'ATTN_BWD', 'GBF_BWD')
+FT_SLOTS = ('EDGE_EMB_W', 'EDGE_EMB_B', 'LE0', 'LE1', 'FF3_W', 'FF3_B', 'FF4_W', 'FF4_B', 'ERO_W', 'ERO_B', 'IN_W', 'IN_B', 'C0_W', 'C0_B', 'C2_W',
+            'N2E_B', 'GBF_MEANS', 'GBF_STDS', 'PACKED', 'POS', 'GM', 'E_IN', 'EMOD', 'D2', 'G', 'XH', 'RS', 'ET', 'T0', 'T1', 'N2E', 'EN', 'F3', 'A3',
+            'F4', 'E_OUT', 'EH', 'HR', 'HC', 'QMOD', 'U', 'C0PRE', 'C0A', 'INV', 'DINV', 'DC0', 'DU', 'DPRE', 'DE', 'DG', 'DE_OUT', 'F4D', 'DF4',
+            'DHID', 'DEN', 'DE_PREV', 'DT1', 'DT0', 'DET', 'DE1', 'MODS', 'Q', 'K', 'V', 'ADJ2D', 'ADJSP', 'ALPHA', 'HHAT', 'DHHAT', 'DS', 'DQ', 'DK',
+            'DV', 'DXP', 'DD2', 'PART_M', 'PART_S')
+FT_TOPO = ('edge_a', 'edge_c', 'edge_mol', 'row_mol', 'node_mol', 'nn', 'node_off', 'edge_off')
+
+
+class FusedTestArgs(ctypes.Structure):
+    """jodo_fused_test_args"""
+    _fields_ = ([(k, ctypes.c_int32) for k in (
+        'op', 'D', 'De', 'r', 'QK', 'ce', 'nco', 'R', 'Nn', 'B', 'N', 'save', 'H', 'XH', 'SC', 'one_wave', 'ldqk', 'ldv', 'ldd_qk', 'ldd_v', 'ld_eh',
+        'eh_col', 'ldm', 'g_off', 'sh_off', 'sc_off', 'acc', 'ldg', 'gcol', 'site_a3', 'site_f4')]
+                + [('drop_p', ctypes.c_float), ('inv_sqrt_c', ctypes.c_float), ('seed', ctypes.c_uint64)]
+                + [(k, ctypes.c_void_p) for k in FT_TOPO]
+                + [('topo_dev', ctypes.c_void_p), ('topo_dev_count', ctypes.c_size_t),
+                   ('a', ctypes.c_void_p * len(FT_SLOTS)), ('n', ctypes.c_size_t * len(FT_SLOTS))])
+
+
+def train_debug_fused(args, stream=None):
+    """jodo_train_debug_fused(args) -> its return code (0, or a negative JODO_ERR_* with the text in jodo_last_error())."""
+    L = lib()
+    try:
+        fn = L.jodo_train_debug_fused
+    except AttributeError as e:
+        raise JodoHipError("%s lacks the fused-kernel test entry (%s): rebuild it with python -c 'import __graft_entry__ as g; g.build()'"
+                           % (LIB_PATH, e))
+    fn.argtypes = [ctypes.POINTER(FusedTestArgs), ctypes.c_void_p]
+    fn.restype = ctypes.c_int
+    return fn(ctypes.byref(args), stream if stream is not None else ctypes.c_void_p(0))
+
+
 def check(code, what=''):
     if code != 0:
         msg = lib().jodo_last_error()
