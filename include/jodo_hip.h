@@ -773,6 +773,31 @@ int jodo_egnn_train_forward(jodo_egnn_train* t, const void* desc_dev, const floa
 int jodo_egnn_train_backward(jodo_egnn_train* t, const void* desc_dev, const float* const* params_dev, float* const* grads_dev, int n_params,
                              const float* d_out, void* workspace, void* stream);
 
+/* tests: ONE fused edge kernel of the classifier on caller-owned device arrays (csrc/egnn_train.hip; tests/test_egnn_kernels_gpu.py
+ * compares every array the kernel stores with a float64 restatement).  The entry adds no kernel: it builds the descriptor tables as
+ * jodo_egnn_train_create does, makes the two tiled images of W2 with kegnn_pack (kinds 0 and 1), and calls the host launcher that
+ * jegnn::run / the training backward call, through the same switch over hidden_nf / 32.
+ *   op JODO_ET_OP_FWD: kegnn_edge                       reads P, XC, WR, W2, B2 (WA, BA); writes AGG [Nn, nf]
+ *   op JODO_ET_OP_BWD: kegnn_edge_bwd, kegnn_tgt_sum    reads the same and DAGG [Nn, nf]; writes EA, EZ2, EZ1 [E, nf] (compact edge rows
+ *                      e = eoff_b + i (n - 1) + (j < i ? j : j - 1)), DP [Nn, 2 nf] (both halves), Q [Nn, 2 nf], QB [Nn]
+ * P [Nn, 2 nf] = P_src + b1 | P_tgt, XC [Nn, 4], WR [nf], W2 [nf, nf] in the PyTorch layout, B2 [nf], WA [nf] and BA [1] (both NULL:
+ * no attention), Nn = sum n, E = sum n (n - 1).  Scratch: DESC (3 B + Nn floats' worth of int32), IMG (2 nf^2: the two images).
+ * grid_cap: 0 = the production cap of the persistent grid, otherwise at most that many workgroups.
+ * Nothing is launched unless every check holds: nf in {64, 128, 192, 256} and 1 <= n <= 255 for every molecule (n > 255:
+ * JODO_ERR_UNSUPPORTED; n < 1: JODO_ERR_ARG), a HIP device (JODO_ERR_UNSUPPORTED); every slot the op uses non-NULL (unless it has no
+ * element: E = 0 is legal), 16-byte aligned (BA: 4) and with exactly the op's element count in n[.], scratch slots at least theirs
+ * (JODO_ERR_ARG).  Slots an op does not use are ignored. */
+enum { JODO_ET_OP_FWD = 0, JODO_ET_OP_BWD, JODO_ET_N_OPS };
+enum { JODO_ET_P = 0, JODO_ET_XC, JODO_ET_DAGG, JODO_ET_WR, JODO_ET_W2, JODO_ET_B2, JODO_ET_WA, JODO_ET_BA, JODO_ET_DESC, JODO_ET_IMG,
+       JODO_ET_AGG, JODO_ET_EA, JODO_ET_EZ2, JODO_ET_EZ1, JODO_ET_DP, JODO_ET_Q, JODO_ET_QB, JODO_ET_N_SLOTS };
+typedef struct {
+    int32_t op, nf, B, grid_cap;
+    const int32_t* n_nodes;                        /* HOST [B] */
+    float* a[JODO_ET_N_SLOTS];                     /* DEVICE arrays */
+    size_t n[JODO_ET_N_SLOTS];                     /* their element counts */
+} jodo_egnn_edge_test_args;
+int jodo_egnn_debug_edge(const jodo_egnn_edge_test_args* args, void* stream);
+
 /* ---- evaluation: atom and molecule stability of decoded molecules (csrc/eval_kernels.hip; evaluation/stability.py:17-161 of the
  * reference: check_stability, and check_2D_stability for molecules without aromatic bonds) ----
  * Inputs are the decode's device tensors (jodo_decode): pos f32 [B,N,3], atom_type u8 [B,N], fc i8 [B,N], edge_type u8 [B,N,N],

@@ -267,6 +267,31 @@ def train_debug_fused(args, stream=None):
     return fn(ctypes.byref(args), stream if stream is not None else ctypes.c_void_p(0))
 
 
+# ---- tests: jodo_egnn_debug_edge (include/jodo_hip.h; csrc/egnn_train.hip) — one fused edge kernel of the classifier on caller-owned
+# arrays.  The two name lists are the header's JODO_ET_* enums in order (tests/test_egnn_kernels_host.py reads the header and compares).
+ET_OPS = ('OP_FWD', 'OP_BWD')
+ET_SLOTS = ('P', 'XC', 'DAGG', 'WR', 'W2', 'B2', 'WA', 'BA', 'DESC', 'IMG', 'AGG', 'EA', 'EZ2', 'EZ1', 'DP', 'Q', 'QB')
+
+
+class EgnnEdgeTestArgs(ctypes.Structure):
+    """jodo_egnn_edge_test_args"""
+    _fields_ = ([(k, ctypes.c_int32) for k in ('op', 'nf', 'B', 'grid_cap')] + [('n_nodes', ctypes.c_void_p)]
+                + [('a', ctypes.c_void_p * len(ET_SLOTS)), ('n', ctypes.c_size_t * len(ET_SLOTS))])
+
+
+def egnn_debug_edge(args, stream=None):
+    """jodo_egnn_debug_edge(args) -> its return code (0, or a negative JODO_ERR_* with the text in jodo_last_error())."""
+    L = lib()
+    try:
+        fn = L.jodo_egnn_debug_edge
+    except AttributeError as e:
+        raise JodoHipError("%s lacks the edge-kernel test entry (%s): rebuild it with python -c 'import __graft_entry__ as g; g.build()'"
+                           % (LIB_PATH, e))
+    fn.argtypes = [ctypes.POINTER(EgnnEdgeTestArgs), ctypes.c_void_p]
+    fn.restype = ctypes.c_int
+    return fn(ctypes.byref(args), stream if stream is not None else ctypes.c_void_p(0))
+
+
 def check(code, what=''):
     if code != 0:
         msg = lib().jodo_last_error()

@@ -139,13 +139,7 @@ __global__ __launch_bounds__(64) void kegnn_gemm(EGemm G) {
 }
 
 // ---- fused edge kernel ----------------------------------------------------------------------------------------------------------------
-struct EEdge {
-    const int *mol_n, *mol_noff, *node_b;
-    int Nn;
-    const float *P, *xc;         // P [Nn, 2 nf] = [P_src + b1 | P_tgt], xc [Nn, 4]
-    const float *wr, *W2, *b2, *wa, *ba;     // wa NULL: no attention
-    float* agg;                  // [Nn, nf]
-};
+using jegnn::EEdge;                  // egnn_internal.h
 
 // One wave per row atom i; sources j in chunks of 32, lane pair (j, h): source r0 + j, half h of its features (natural-half slots).
 // The first edge layer is formed in registers (the B operand of the second), the second runs on the MFMA with W2 as A operand from LDS
@@ -289,8 +283,8 @@ int gemm(hipStream_t st, EGemm G) {
 }
 
 template <int NB, bool LDSW>
-int edge_launch(hipStream_t st, const EEdge& A) {
-    const int grid = (A.Nn + 3) / 4 < jegnn::EDGE_GRID_MAX ? (A.Nn + 3) / 4 : jegnn::EDGE_GRID_MAX;      // persistent: a workgroup stages W2 once and walks its atoms
+int edge_launch(hipStream_t st, const EEdge& A, int grid_cap) {
+    const int grid = (A.Nn + 3) / 4 < grid_cap ? (A.Nn + 3) / 4 : grid_cap;      // persistent: a workgroup stages W2 once and walks its atoms
     LEG((kegnn_edge<NB, LDSW>), grid, 256, A);
     return JODO_OK;
 }
@@ -323,6 +317,15 @@ extern "C" int jodo_egnn_fill_desc(const jodo_egnn_cfg* cfg, int B, int N, const
     return JODO_OK;
 }
 
+int jegnn::edge_forward(hipStream_t st, int NB, const EEdge& A, int grid_cap) {
+    switch (NB) {
+        case 2: return edge_launch<2, true>(st, A, grid_cap);
+        case 4: return edge_launch<4, true>(st, A, grid_cap);
+        case 6: return edge_launch<6, false>(st, A, grid_cap);
+        default: return edge_launch<8, false>(st, A, grid_cap);
+    }
+}
+
 int jegnn::row_gemm(hipStream_t st, const float* X0, int ld0, int nk0, const float* X1, int ld1, int nk1, const float* X2, int ld2, int nk2, float* Y,
                     int ldy, const float* W, const float* bias, int rows, int nb, int act, const float* R) {
     EGemm G{X0, X1, X2, ld0, ld1, ld2, nk0, nk1, nk2, Y, ldy, W, bias, rows, nb, act, R, ldy};
@@ -352,14 +355,7 @@ int jegnn::run(const jodo_egnn_cfg* cfg, int B, int N, int Nn, const void* desc_
         if (int rc = row_gemm(h, nf, NK, nullptr, 0, 0, nullptr, 0, 0, p, 2 * nf, wl[JEL_P_W], wl[JEL_P_B], Nn, 2 * NB, 0, nullptr)) return rc;
         EEdge E{mol_n, mol_noff, node_b, Nn, p, xc, W(wl[JEL_WR]), W(wl[JEL_W2]), W(wl[JEL_B2]),
                 cfg->attention ? W(wl[JEL_ATT_W]) : nullptr, cfg->attention ? W(wl[JEL_ATT_B]) : nullptr, agg};
-        int rc;
-        switch (NB) {
-            case 2: rc = edge_launch<2, true>(st, E); break;
-            case 4: rc = edge_launch<4, true>(st, E); break;
-            case 6: rc = edge_launch<6, false>(st, E); break;
-            default: rc = edge_launch<8, false>(st, E); break;
-        }
-        if (rc) return rc;
+        if (int rc = edge_forward(st, NB, E)) return rc;
         if (int rc2 = row_gemm(h, nf, NK, agg, nf, NK, a0, 64, cfg->node_attr ? 1 : 0, t, nf, wl[JEL_N0_W], wl[JEL_N0_B], Nn, NB, 1, nullptr)) return rc2;
         if (int rc2 = row_gemm(t, nf, NK, nullptr, 0, 0, nullptr, 0, 0, bf.h[ly + 1], nf, wl[JEL_N2_W], wl[JEL_N2_B], Nn, NB, 0, h)) return rc2;
     }

@@ -39,6 +39,29 @@ struct Bufs {
 int run(const jodo_egnn_cfg* cfg, int B, int N, int Nn, const void* desc_dev, const float* packed_w, const int64_t* woff, const float* h0,
         const float* x, float* out, const Bufs& bufs, int max_layers, hipStream_t st);
 
+// Arguments of the two fused edge kernels (kegnn_edge in egnn_forward.hip, kegnn_edge_bwd in egnn_train.hip).
+struct EEdge {
+    const int *mol_n, *mol_noff, *node_b;
+    int Nn;
+    const float *P, *xc;         // P [Nn, 2 nf] = [P_src + b1 | P_tgt], xc [Nn, 4]
+    const float *wr, *W2, *b2, *wa, *ba;     // wa NULL: no attention
+    float* agg;                  // [Nn, nf]
+};
+struct EBwd {
+    const int *mol_n, *mol_noff, *node_b, *eoff;
+    int Nn;
+    const float *P, *xc, *dagg;              // P [Nn, 2 nf] = [P_src + b1 | P_tgt], xc [Nn, 4], dagg [Nn, nf]
+    const float *wr, *W2, *W2T, *b2, *wa, *ba;       // wa NULL: no attention
+    float *dP, *Q, *qb;                      // dP [Nn, 2 nf] (columns 0 .. nf written here), Q [Nn, 2 nf] = dw_r | dw_a partial rows, qb [Nn]
+    float *ea, *ez1, *ez2;                   // compact edge rows [E, nf]
+};
+
+// The host launchers of the edge kernels: the instantiation for NB = nf / 32 (2, 4: W2 in LDS; 6, 8: streamed) on a persistent grid of
+// at most grid_cap workgroups.  jegnn::run and the training backward call them at the default; the test entry jodo_egnn_debug_edge
+// (egnn_train.hip) also with smaller caps.  edge_backward is kegnn_edge_bwd followed by kegnn_tgt_sum (the second half of dP).
+int edge_forward(hipStream_t st, int NB, const EEdge& A, int grid_cap = EDGE_GRID_MAX);
+int edge_backward(hipStream_t st, int NB, const EBwd& A, int grid_cap = EDGE_GRID_MAX);
+
 // kegnn_gemm on its own: Y[rows, 32 nb] = epi([X0 | X1 | X2] W^T + bias), K chunks of 64 (nk0 + nk1 + nk2), act 1 = SiLU, R = residual
 int row_gemm(hipStream_t st, const float* X0, int ld0, int nk0, const float* X1, int ld1, int nk1, const float* X2, int ld2, int nk2, float* Y,
              int ldy, const float* W, const float* bias, int rows, int nb, int act, const float* R);

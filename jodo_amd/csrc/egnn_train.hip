@@ -21,6 +21,7 @@
 //   kegnn_colsum_part / _fin     dw_r, dw_a, db_a: column sums of the per-atom partial rows in 64-row chunks, then over chunks
 //   jt::gemm                     dW_src / dW_tgt / db1 from dP and h_l; d h_l = d h_{l+1} + dt N0_h + dP_src W_src + dP_tgt W_tgt
 // No floating-point atomics, no scatter: every sum has a fixed order, two runs give the same bits.
+// Tests: jodo_egnn_debug_edge (at the end) runs kegnn_edge or kegnn_edge_bwd + kegnn_tgt_sum alone on caller-owned arrays.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -95,14 +96,7 @@ __global__ void kegnn_pack(PackTable T) {
 }
 
 // ---- fused edge backward ----------------------------------------------------------------------------------------------------------------
-struct EBwd {
-    const int *mol_n, *mol_noff, *node_b, *eoff;
-    int Nn;
-    const float *P, *xc, *dagg;              // P [Nn, 2 nf] = [P_src + b1 | P_tgt], xc [Nn, 4], dagg [Nn, nf]
-    const float *wr, *W2, *W2T, *b2, *wa, *ba;       // wa NULL: no attention
-    float *dP, *Q, *qb;                      // dP [Nn, 2 nf] (columns 0 .. nf written here), Q [Nn, 2 nf] = dw_r | dw_a partial rows, qb [Nn]
-    float *ea, *ez1, *ez2;                   // compact edge rows [E, nf]
-};
+using jegnn::EBwd;                   // egnn_internal.h
 
 // One wave per row atom i, sources in chunks of 32, lane pair (j, h) as in kegnn_edge.  LDSW: W2 and its transposed image are staged
 // in LDS once per persistent workgroup (nf 64: 32 KiB, nf 128: 128 KiB); otherwise both stream from L2 and z2 / dz2 wait in LDS
@@ -331,12 +325,50 @@ __global__ void kegnn_bcast_mol(int Nn, int nf, const int* node_b, const float* 
 }
 
 template <int NB, bool LDSW>
-void edge_bwd_launch(hipStream_t st, const EBwd& A) {
-    const int grid = (A.Nn + 3) / 4 < jegnn::EDGE_GRID_MAX ? (A.Nn + 3) / 4 : jegnn::EDGE_GRID_MAX;     // the forward's persistent grid
+void edge_bwd_launch(hipStream_t st, const EBwd& A, int grid_cap) {
+    const int grid = (A.Nn + 3) / 4 < grid_cap ? (A.Nn + 3) / 4 : grid_cap;     // the forward's persistent grid
     LEGT((kegnn_edge_bwd<NB, LDSW>), grid, 256, A);
 }
 
+// the three pieces of the weight image that a call of the edge kernels needs, as pack_tape makes them
+PackJob tiled_job(float* dst, const float* s0, int rows0, int ld, int c0, int K, const float* s1 = nullptr, int rows1 = 0, int c1 = 0) {
+    PackJob J{s0, s1, dst, rows0, rows1, ld, c0, c1, K, (rows0 + rows1 + 31) / 32, (K + 63) / 64, 0, 0};
+    return J;
+}
+PackJob transposed_job(float* dst, const float* w, int nf) {     // the transposed image of edge_mlp.2 for da = W2^T dz2
+    PackJob J{w, nullptr, dst, nf, 0, nf, 0, 0, nf, nf / 32, nf / 64, 1, 0};
+    return J;
+}
+void launch_pack(hipStream_t st, const PackTable& T) {
+    int most = 0;
+    for (int i = 0; i < T.n; ++i) { const int cnt = T.j[i].kind == 2 ? T.j[i].n : T.j[i].nb * T.j[i].nk * 2048; most = cnt > most ? cnt : most; }
+    LEGT(kegnn_pack, dim3((most + 255) / 256, T.n), 256, T);
+}
+
+// n_b [B] | noff_b [B] | (b << 8 | i) [Nn] | eoff_b [B]: the descriptor of the training path (3 B + Nn ints)
+void fill_tables(int B, const int32_t* n_nodes, long Nn, int* tables) {
+    int noff = 0, node = 0;
+    long eo = 0;
+    for (int b = 0; b < B; ++b) {
+        const int n = n_nodes[b];
+        tables[b] = n; tables[B + b] = noff; tables[(size_t)2 * B + Nn + b] = (int)eo;
+        for (int i = 0; i < n; ++i) tables[2 * B + node++] = (b << 8) | i;
+        noff += n; eo += (long)n * (n - 1);
+    }
+}
+
 }  // namespace
+
+int jegnn::edge_backward(hipStream_t st, int NB, const EBwd& A, int grid_cap) {
+    switch (NB) {
+        case 2: edge_bwd_launch<2, true>(st, A, grid_cap); break;
+        case 4: edge_bwd_launch<4, true>(st, A, grid_cap); break;
+        case 6: edge_bwd_launch<6, false>(st, A, grid_cap); break;
+        default: edge_bwd_launch<8, false>(st, A, grid_cap); break;
+    }
+    LEGT(kegnn_tgt_sum, A.Nn, NB * 32, A.mol_n, A.mol_noff, A.node_b, A.eoff, NB * 32, (const float*)A.ez1, A.dP);
+    return JODO_OK;
+}
 
 struct jodo_egnn_train {
     jodo_egnn_cfg cfg;
@@ -400,22 +432,17 @@ struct Ctx {
 
 void pack_tape(const Ctx& c) {
     const jodo_egnn_train& t = c.t; hipStream_t st = c.s;
-    const int nf = t.cfg.hidden_nf, in = t.cfg.in_node_nf, L = t.cfg.n_layers, nb = nf / 32, nk = nf / 64;
+    const int nf = t.cfg.hidden_nf, in = t.cfg.in_node_nf, L = t.cfg.n_layers;
     float* tape = c.b.tape;
     const int64_t* wo = t.woff.data();
     auto tiled = [&](int64_t off, const float* s0, int rows0, int ld, int c0, int K, const float* s1 = nullptr, int rows1 = 0, int c1 = 0) {
-        PackJob J{s0, s1, tape + off, rows0, rows1, ld, c0, c1, K, (rows0 + rows1 + 31) / 32, (K + 63) / 64, 0, 0};
-        return J;
+        return tiled_job(tape + off, s0, rows0, ld, c0, K, s1, rows1, c1);
     };
     auto vec = [&](int64_t off, const float* s0, int len, int stride, int n) {
         PackJob J{s0, nullptr, tape + off, len, 0, stride, 0, 0, 0, 0, 0, 2, n};
         return J;
     };
-    auto launch = [&](const PackTable& T) {
-        int most = 0;
-        for (int i = 0; i < T.n; ++i) { const int cnt = T.j[i].kind == 2 ? T.j[i].n : T.j[i].nb * T.j[i].nk * 2048; most = cnt > most ? cnt : most; }
-        LEGT(kegnn_pack, dim3((most + 255) / 256, T.n), 256, T);
-    };
+    auto launch = [&](const PackTable& T) { launch_pack(st, T); };
     PackTable T;
     T.n = 0;
     T.j[T.n++] = tiled(wo[JE_EMB_W], c.p(t.emb.w), nf, in, 0, in);
@@ -439,10 +466,7 @@ void pack_tape(const Ctx& c) {
         T.j[T.n++] = vec(wl[JEL_WR], c.p(ix.e0.w) + 2 * nf, nf, K0, nf);
         T.j[T.n++] = tiled(wl[JEL_W2], c.p(ix.e2.w), nf, nf, 0, nf);
         T.j[T.n++] = vec(wl[JEL_B2], c.p(ix.e2.b), nf, 1, nf);
-        {   // the transposed image of edge_mlp.2 for da = W2^T dz2, outside the forward's slot table
-            PackJob J{c.p(ix.e2.w), nullptr, c.b.w2t + (size_t)l * nf * nf, nf, 0, nf, 0, 0, nf, nb, nk, 1, 0};
-            T.j[T.n++] = J;
-        }
+        T.j[T.n++] = transposed_job(c.b.w2t + (size_t)l * nf * nf, c.p(ix.e2.w), nf);      // outside the forward's slot table
         if (t.cfg.attention) {
             T.j[T.n++] = vec(wl[JEL_ATT_W], c.p(ix.att.w), nf, 1, nf);
             T.j[T.n++] = vec(wl[JEL_ATT_B], c.p(ix.att.b), 1, 1, 1);
@@ -517,13 +541,7 @@ int backward(const Ctx& c, const void* desc_dev, const float* d_out) {
         EBwd A{mol_n, mol_noff, node_b, eoff, Nn, b.fw.p[l], b.fw.xc, b.dagg, tape + wl[JEL_WR], tape + wl[JEL_W2], b.w2t + (size_t)l * nf * nf,
                tape + wl[JEL_B2], t.cfg.attention ? tape + wl[JEL_ATT_W] : nullptr, t.cfg.attention ? tape + wl[JEL_ATT_B] : nullptr,
                b.dP, b.Q, b.qb, b.ea, b.ez1, b.ez2};
-        switch (NB) {
-            case 2: edge_bwd_launch<2, true>(st, A); break;
-            case 4: edge_bwd_launch<4, true>(st, A); break;
-            case 6: edge_bwd_launch<6, false>(st, A); break;
-            default: edge_bwd_launch<8, false>(st, A); break;
-        }
-        LEGT(kegnn_tgt_sum, Nn, nf, mol_n, mol_noff, node_b, eoff, nf, (const float*)b.ez1, b.dP);
+        if (int rc = jegnn::edge_backward(st, NB, A)) return rc;      // kegnn_edge_bwd, then kegnn_tgt_sum
         if (t.E > 0) c.lin_dw(b.ez2, nf, t.E, nf, b.ea, nf, nf, c.g(ix.e2.w), nf, c.g(ix.e2.b));
         c.colsum(Nn, 2 * nf, b.Q, 2 * nf);
         c.colsum_fin(Nn, nf, b.part, 2 * nf, c.g(ix.e0.w) + 2 * nf, K0);
@@ -562,16 +580,7 @@ int jodo_egnn_train_create(const jodo_egnn_cfg* cfg, int B, int N, const int32_t
     jodo_egnn_train* t = new jodo_egnn_train();
     t->cfg = *cfg; t->B = B; t->N = N; t->Nn = (int)Nn; t->E = E;
     t->tables.assign((size_t)3 * B + Nn, 0);
-    {
-        int noff = 0, node = 0;
-        long eo = 0;
-        for (int b = 0; b < B; ++b) {
-            const int n = n_nodes[b];
-            t->tables[b] = n; t->tables[B + b] = noff; t->tables[(size_t)2 * B + Nn + b] = (int)eo;
-            for (int i = 0; i < n; ++i) t->tables[2 * B + node++] = (b << 8) | i;
-            noff += n; eo += (long)n * (n - 1);
-        }
-    }
+    fill_tables(B, n_nodes, Nn, t->tables.data());
     std::unordered_map<std::string, int> ix;
     t->n_params = n_params; t->numel.resize(n_params);
     for (int i = 0; i < n_params; ++i) {
@@ -671,6 +680,84 @@ int jodo_egnn_train_backward(jodo_egnn_train* t, const void* desc_dev, const flo
     Ctx c{*t, params_dev, grads_dev, bufs, static_cast<hipStream_t>(stream)};
     if (int rc = backward(c, desc_dev, d_out)) return rc;
     return jodo_check_launch("jodo_egnn_train_backward");
+}
+
+// tests: one edge kernel on caller-owned arrays (include/jodo_hip.h).  No kernel lives here; the entry is the safety boundary of
+// tests/test_egnn_kernels_gpu.py: everything is checked on the host before anything is launched.
+int jodo_egnn_debug_edge(const jodo_egnn_edge_test_args* args, void* stream) {
+    static const char* const SLOT[JODO_ET_N_SLOTS] = {"p", "xc", "dagg", "wr", "w2", "b2", "wa", "ba", "desc", "img", "agg", "ea", "ez2", "ez1",
+                                                     "dp", "q", "qb"};
+    if (!args) return jodo_set_error(JODO_ERR_ARG, "jodo_egnn_debug_edge: args is a null pointer");
+    const jodo_egnn_edge_test_args& a = *args;
+    if (a.op < 0 || a.op >= JODO_ET_N_OPS) return jodo_set_error(JODO_ERR_ARG, "jodo_egnn_debug_edge: unknown op %d", a.op);
+    if (a.nf != 64 && a.nf != 128 && a.nf != 192 && a.nf != 256)
+        return jodo_set_error(JODO_ERR_UNSUPPORTED, "jodo_egnn_debug_edge: hidden_nf %d is not one of 64, 128, 192, 256", a.nf);
+    if (a.B <= 0 || a.B >= (1 << 22) || !a.n_nodes) return jodo_set_error(JODO_ERR_ARG, "jodo_egnn_debug_edge: B %d or a null n_nodes", a.B);
+    if (a.grid_cap < 0) return jodo_set_error(JODO_ERR_ARG, "jodo_egnn_debug_edge: grid_cap %d", a.grid_cap);
+    long Nn = 0, E = 0;
+    for (int b = 0; b < a.B; ++b) {
+        const int n = a.n_nodes[b];
+        if (n < 1) return jodo_set_error(JODO_ERR_ARG, "jodo_egnn_debug_edge: n_nodes[%d] = %d below 1", b, n);
+        if (n > 255) return jodo_set_error(JODO_ERR_UNSUPPORTED, "jodo_egnn_debug_edge: n_nodes[%d] = %d above 255", b, n);
+        Nn += n; E += (long)n * (n - 1);
+    }
+    if (Nn >= (1L << 31) / (2 * a.nf) || E > (1L << 30))
+        return jodo_set_error(JODO_ERR_UNSUPPORTED, "jodo_egnn_debug_edge: batch too large (%ld atoms, %ld edges)", Nn, E);
+    const size_t nf = (size_t)a.nf, N = (size_t)Nn, Ee = (size_t)E, words = (size_t)3 * a.B + N;
+    const bool bwd = a.op == JODO_ET_OP_BWD, att = a.a[JODO_ET_WA] || a.a[JODO_ET_BA];
+    // slot -> element count the op touches (exact for the arrays, a minimum for the scratch); -1: not used
+    long need[JODO_ET_N_SLOTS];
+    for (int s = 0; s < JODO_ET_N_SLOTS; ++s) need[s] = -1;
+    need[JODO_ET_P] = (long)(N * 2 * nf); need[JODO_ET_XC] = (long)(N * 4); need[JODO_ET_WR] = need[JODO_ET_B2] = (long)nf;
+    need[JODO_ET_W2] = (long)(nf * nf); need[JODO_ET_DESC] = (long)words; need[JODO_ET_IMG] = (long)(2 * nf * nf);
+    if (att) { need[JODO_ET_WA] = (long)nf; need[JODO_ET_BA] = 1; }
+    if (bwd) {
+        need[JODO_ET_DAGG] = (long)(N * nf);
+        need[JODO_ET_EA] = need[JODO_ET_EZ2] = need[JODO_ET_EZ1] = (long)(Ee * nf);
+        need[JODO_ET_DP] = need[JODO_ET_Q] = (long)(N * 2 * nf); need[JODO_ET_QB] = (long)N;
+    } else {
+        need[JODO_ET_AGG] = (long)(N * nf);
+    }
+    for (int s = 0; s < JODO_ET_N_SLOTS; ++s) {
+        if (need[s] < 0) continue;
+        const bool scratch = s == JODO_ET_DESC || s == JODO_ET_IMG;
+        if (scratch ? a.n[s] < (size_t)need[s] : a.n[s] != (size_t)need[s])
+            return jodo_set_error(JODO_ERR_ARG, "jodo_egnn_debug_edge: array %s has %zu elements, the op touches %ld", SLOT[s], a.n[s], need[s]);
+        if (need[s] == 0) continue;
+        if (!a.a[s]) return jodo_set_error(JODO_ERR_ARG, "jodo_egnn_debug_edge: array %s is a null pointer", SLOT[s]);
+        const uintptr_t align = s == JODO_ET_BA ? 4 : 16;
+        if (((uintptr_t)a.a[s] & (align - 1)) != 0)
+            return jodo_set_error(JODO_ERR_ARG, "jodo_egnn_debug_edge: array %s is not %d-byte aligned", SLOT[s], (int)align);
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        (void)hipGetLastError();
+        return jodo_set_error(JODO_ERR_UNSUPPORTED, "jodo_egnn_debug_edge: no HIP device");
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    std::vector<int> tables(words, 0);
+    fill_tables(a.B, a.n_nodes, Nn, tables.data());
+    int* desc = reinterpret_cast<int*>(a.a[JODO_ET_DESC]);
+    if (hipMemcpyAsync(desc, tables.data(), words * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        return jodo_set_error(JODO_ERR_LAUNCH, "jodo_egnn_debug_edge: upload of the descriptor failed");      // (tables is pageable and local: wait)
+    float *img = a.a[JODO_ET_IMG], *imgT = img + nf * nf;
+    PackTable T;
+    T.n = 0;
+    T.j[T.n++] = tiled_job(img, a.a[JODO_ET_W2], a.nf, a.nf, 0, a.nf);
+    if (bwd) T.j[T.n++] = transposed_job(imgT, a.a[JODO_ET_W2], a.nf);
+    launch_pack(st, T);
+    const int B = a.B, NB = a.nf / 32, cap = a.grid_cap > 0 ? a.grid_cap : jegnn::EDGE_GRID_MAX;
+    const int *mol_n = desc, *mol_noff = desc + B, *node_b = desc + 2 * B, *eoff = desc + 2 * B + Nn;
+    const float *wa = att ? a.a[JODO_ET_WA] : nullptr, *ba = att ? a.a[JODO_ET_BA] : nullptr;
+    if (bwd) {
+        EBwd A{mol_n, mol_noff, node_b, eoff, (int)Nn, a.a[JODO_ET_P], a.a[JODO_ET_XC], a.a[JODO_ET_DAGG], a.a[JODO_ET_WR], img, imgT, a.a[JODO_ET_B2],
+               wa, ba, a.a[JODO_ET_DP], a.a[JODO_ET_Q], a.a[JODO_ET_QB], a.a[JODO_ET_EA], a.a[JODO_ET_EZ1], a.a[JODO_ET_EZ2]};
+        if (int rc = jegnn::edge_backward(st, NB, A, cap)) return rc;
+    } else {
+        jegnn::EEdge A{mol_n, mol_noff, node_b, (int)Nn, a.a[JODO_ET_P], a.a[JODO_ET_XC], a.a[JODO_ET_WR], img, a.a[JODO_ET_B2], wa, ba, a.a[JODO_ET_AGG]};
+        if (int rc = jegnn::edge_forward(st, NB, A, cap)) return rc;
+    }
+    return jodo_check_launch("jodo_egnn_debug_edge");
 }
 
 }  // extern "C"

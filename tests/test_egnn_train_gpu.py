@@ -143,6 +143,34 @@ def test_each_edge_backward_instantiation_past_one_trip(tag):
     print("%s: worst gradient error / bound %.4f" % (tag, worst))
 
 
+@pytest.mark.parametrize("nf", [64, 192])
+def test_wide_molecules_gradients(nf):
+    """The training path at the forward's size edges (test_egnn_scale_gpu.test_wide_molecules): n = 255 (eight source chunks, the last
+    with 31 sources; compact edge rows up to 64 770 per molecule) and 181 beside 1 and 2 at padded width 255, 16 real-valued input
+    channels, node_attr and attention, one layer; W2 in LDS (nf 64) and streamed (nf 192).  97 352 edge rows: the workspace sizing and
+    the capped split-K of the edge_mlp.2 weight gradient at that many rows."""
+    n_nodes, N = [255, 1, 2, 181], 255
+    assert sum(n * (n - 1) for n in n_nodes) == 97352
+    st = S.settings(nf, 1, 1, 1, in_nf=16)
+    model, sd = S.make_model(st, 37)
+    h0, x = S.batch(n_nodes, N, 41, 16, False)
+    d_out = torch.randn(len(n_nodes), generator=torch.Generator().manual_seed(29))
+    _, g64 = OET.grads(sd, st, h0, x, n_nodes, d_out, torch.float64, chunk=1)
+    _, g32 = OET.grads(sd, st, h0, x, n_nodes, d_out, torch.float32, chunk=1)
+    assert min(float(v.abs().max()) for v in g64.values()) > 1e-3              # no gradient tensor vanishes
+    reference = S.call(model, h0, x, n_nodes, N)
+    model.hip_training = True
+    try:
+        model.requires_grad_(True)
+        out, grads = _grads(model, h0, x, n_nodes, d_out)
+    finally:
+        model.hip_training = False
+        model.zero_grad(set_to_none=True)
+    assert torch.equal(out, reference)
+    worst = compare_grads(grads, g64, want32=g32, what='egnn train wide nf%d' % nf)
+    print("wide nf %d: worst gradient error / bound %.4f" % (nf, worst))
+
+
 def test_forward_and_gradients_follow_the_live_weights():
     tag = C.CASES[1]
     _, st, _, h0, x, n_nodes, d_out = C.case(tag)
