@@ -1034,6 +1034,60 @@ int jodo_cdgs_train_backward(jodo_cdgs_train* t, const void* desc_dev, const flo
                              const float* x, const float* edge_x, const float* d_out_x, const float* d_out_e, float dropout_p, uint64_t seed,
                              void* workspace, void* stream);
 
+/* tests: ONE launch sequence (or one single launch) of the CDGS training step on caller-owned device arrays (csrc/cdgs_train.hip;
+ * tests/test_cdgs_kernels_gpu.py compares every array an op stores with a float64 restatement).  The entry adds no kernel and no copy of
+ * a launch sequence: every multi-launch op is the host function that jodo_cdgs_train_forward / _backward call on the workspace.
+ * Geometry: n_nodes [B] in HOST memory, uploaded by the entry into nn_dev (device, nn_dev_count >= B int32); M = B N node rows (b N + i),
+ * R = B N^2 tile rows ((b N + r) N + c), G = D / 8 GroupNorm groups.  `rows` = 0: every row of the op's tensor (M in mode 1, R in
+ * modes 0 and 2); otherwise the op runs on the first `rows` rows of it (SCALE, RELU, RELU_BWD, NORM_GRADS only; 1 <= rows <= that count).
+ * op                  kernels                                            reads                          writes
+ * RW                  kc_adj, kc_adnorm, kc_rw_step x K, kc_onehot,      EDGE_X [R, ch]                 ADJ, AD, CNT [R], ONEHOT [R, K + 1],
+ *                     kc_deg                                                                            LAND [M, K], DEG [M, ch]; PA, PB [R] scratch
+ * ADDT                kc_addt (mode 1 | 2)                               X [rows, F], TB [B, F]         Y [rows, F]
+ * SCALE               kc_scale (mode 0 | 1 | 2, acc, dropout)            X [rows, F] (acc: and Y)       Y [rows, F]
+ * RELU / RELU_BWD     kc_relu / kc_relu_bwd                              X [rows, F]                    Y [rows, F] (RELU_BWD: in place on Y)
+ * PAIR / PAIR_BWD     kc_pair / kc_pair_bwd                              X [M, D] / X [R, D]            Y [R, D] / Y [M, D]
+ * OUT_NODES           kc_out_nodes                                       X [M, F]                       Y [M, F]
+ * OUT_EDGES           kc_out_edges                                       X [R, ch]                      Y [R, ch]
+ * SUMS                kc_sum_cols, kc_sum_nodes (mode = masked 0 | 1)    X [R, F]                       Y [M, F], Z [B, F]
+ * GINE                kc_gine                                            EPS [1], HS [M, D], HE [R, D], ADJ [R]    AGG [M, D]
+ * GINE_BWD            kc_gine_bwd_e, kc_gine_bwd_n                       the same and DAGG [M, D]       DHE [R, D], DHS [M, D]
+ * GN_FWD              kc_gn_fwd (amask, acc, dropout)                    H, A [M, D], GAMMA, BETA [D] (acc: and Y)   XHAT [M, D], RSTD [M, G], Y [M, D]
+ * GN_BWD              kc_gn_bwd (acc)                                    DY, XHAT [M, D], RSTD [M, G], GAMMA [D] (acc: and DX)   DX [M, D]
+ * EGN_FWD             kc_egn_part mode 0, kc_egn_fin, kc_egn_apply       XHAT [R, D] (x, turned into xhat IN PLACE), GAMMA, BETA [D]   XHAT, RSTD [B, G], Y [R, D]
+ * EGN_BWD             kc_egn_part mode 2 with gamma, kc_egn_fin,         DY [R, D], XHAT [R, D], RSTD [B, G], GAMMA [D]   DX [R, D]
+ *                     kc_egn_bwd
+ * NORM_GRADS          kc_colsum_part, _mid, _fin (mode 1 | 2)            DY, XHAT [rows, F]             DBETA, DGAMMA [F]
+ * ATTN_FWD            kc_attn_logit, kc_attn_softmax, kc_attn_msg        Q, K, V [M, D], G0, G1 [R, D]  ALPHA [R, H] (logits, then alpha in place), ATT [M, D]
+ * ATTN_BWD            the seven kc_attn_bwd_* kernels                    DATT [M, D], Q, K, V, G0, G1, ALPHA [R, H]   DV, DQ, DK [M, D], DAL [R, H] (d alpha,
+ *                                                                                                       then d logit in place), DT1, DT0 [R, D]
+ * Double scratch (sizes in floats, the engine's own rule): PART >= 4 M G (EGN_*) or 4 (nchunk + nchunk / 32 + 1) F with
+ * nchunk = ceil(rows / 64) (NORM_GRADS); GSUM >= 4 B G (EGN_*).  isc multiplies the logits (the step passes 1 / sqrt(D / H)).
+ * Nothing is launched unless every check holds: a known op, B, N >= 1, B N^2 <= 2^30, every n_nodes[b] in 1 .. N, D % 8 == 0, H
+ * dividing D, F, K >= 1, ch >= 2, D, F <= 4096 and K, ch <= 256 (JODO_ERR_UNSUPPORTED for the sizes, JODO_ERR_ARG for the rest), mode / acc /
+ * amask / rows in the op's range, 0 <= drop_p < 1, and every slot the op touches non-NULL, 16-byte aligned and with exactly the op's
+ * element count in n[.] (scratch slots and nn_dev: at least theirs) (JODO_ERR_ARG).  Slots an op does not use are ignored. */
+enum { JODO_CT_OP_RW = 0, JODO_CT_OP_ADDT, JODO_CT_OP_SCALE, JODO_CT_OP_RELU, JODO_CT_OP_RELU_BWD, JODO_CT_OP_PAIR, JODO_CT_OP_PAIR_BWD,
+       JODO_CT_OP_OUT_NODES, JODO_CT_OP_OUT_EDGES, JODO_CT_OP_SUMS, JODO_CT_OP_GINE, JODO_CT_OP_GINE_BWD, JODO_CT_OP_GN_FWD, JODO_CT_OP_GN_BWD,
+       JODO_CT_OP_EGN_FWD, JODO_CT_OP_EGN_BWD, JODO_CT_OP_NORM_GRADS, JODO_CT_OP_ATTN_FWD, JODO_CT_OP_ATTN_BWD, JODO_CT_N_OPS };
+enum { JODO_CT_EDGE_X = 0, JODO_CT_ADJ, JODO_CT_AD, JODO_CT_PA, JODO_CT_PB, JODO_CT_CNT, JODO_CT_ONEHOT, JODO_CT_LAND, JODO_CT_DEG, JODO_CT_X,
+       JODO_CT_TB, JODO_CT_Y, JODO_CT_Z, JODO_CT_EPS, JODO_CT_HS, JODO_CT_HE, JODO_CT_AGG, JODO_CT_DAGG, JODO_CT_DHE, JODO_CT_DHS, JODO_CT_H,
+       JODO_CT_A, JODO_CT_GAMMA, JODO_CT_BETA, JODO_CT_XHAT, JODO_CT_RSTD, JODO_CT_DY, JODO_CT_DX, JODO_CT_PART, JODO_CT_GSUM, JODO_CT_DBETA,
+       JODO_CT_DGAMMA, JODO_CT_Q, JODO_CT_K, JODO_CT_V, JODO_CT_G0, JODO_CT_G1, JODO_CT_ALPHA, JODO_CT_ATT, JODO_CT_DATT, JODO_CT_DV,
+       JODO_CT_DAL, JODO_CT_DT1, JODO_CT_DT0, JODO_CT_DQ, JODO_CT_DK, JODO_CT_N_SLOTS };
+typedef struct {
+    int32_t op, B, N, D, H, F, K, ch, mode, acc, amask, drop_site;
+    float isc, drop_p;
+    uint64_t drop_seed;
+    int64_t rows;
+    const int32_t* n_nodes;                        /* HOST [B] */
+    int32_t* nn_dev;                               /* DEVICE scratch: the entry uploads n_nodes here */
+    size_t nn_dev_count;                           /* its int32 count, >= B */
+    float* a[JODO_CT_N_SLOTS];                     /* DEVICE arrays */
+    size_t n[JODO_CT_N_SLOTS];                     /* their element counts (floats) */
+} jodo_cdgs_op_test_args;
+int jodo_cdgs_train_debug_op(const jodo_cdgs_op_test_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -292,6 +292,38 @@ def egnn_debug_edge(args, stream=None):
     return fn(ctypes.byref(args), stream if stream is not None else ctypes.c_void_p(0))
 
 
+# ---- tests: jodo_cdgs_train_debug_op (include/jodo_hip.h; csrc/cdgs_train.hip) — one launch sequence of the CDGS training step on
+# caller-owned arrays.  The two name lists are the header's JODO_CT_* enums in order (tests/test_cdgs_kernels_host.py reads the header and
+# compares).
+CT_OPS = ('OP_RW', 'OP_ADDT', 'OP_SCALE', 'OP_RELU', 'OP_RELU_BWD', 'OP_PAIR', 'OP_PAIR_BWD', 'OP_OUT_NODES', 'OP_OUT_EDGES', 'OP_SUMS', 'OP_GINE',
+          'OP_GINE_BWD', 'OP_GN_FWD', 'OP_GN_BWD', 'OP_EGN_FWD', 'OP_EGN_BWD', 'OP_NORM_GRADS', 'OP_ATTN_FWD', 'OP_ATTN_BWD')
+CT_SLOTS = ('EDGE_X', 'ADJ', 'AD', 'PA', 'PB', 'CNT', 'ONEHOT', 'LAND', 'DEG', 'X', 'TB', 'Y', 'Z', 'EPS', 'HS', 'HE', 'AGG', 'DAGG', 'DHE', 'DHS', 'H', 'A',
+            'GAMMA', 'BETA', 'XHAT', 'RSTD', 'DY', 'DX', 'PART', 'GSUM', 'DBETA', 'DGAMMA', 'Q', 'K', 'V', 'G0', 'G1', 'ALPHA', 'ATT', 'DATT', 'DV', 'DAL',
+            'DT1', 'DT0', 'DQ', 'DK')
+
+
+class CdgsOpTestArgs(ctypes.Structure):
+    """jodo_cdgs_op_test_args"""
+    _fields_ = ([(k, ctypes.c_int32) for k in ('op', 'B', 'N', 'D', 'H', 'F', 'K', 'ch', 'mode', 'acc', 'amask', 'drop_site')]
+                + [('isc', ctypes.c_float), ('drop_p', ctypes.c_float), ('drop_seed', ctypes.c_uint64), ('rows', ctypes.c_int64),
+                   ('n_nodes', ctypes.c_void_p), ('nn_dev', ctypes.c_void_p), ('nn_dev_count', ctypes.c_size_t),
+                   ('a', ctypes.c_void_p * len(CT_SLOTS)), ('n', ctypes.c_size_t * len(CT_SLOTS))])
+
+
+def cdgs_debug_op(args, stream=None, library=None):
+    """jodo_cdgs_train_debug_op(args) -> its return code (0, or a negative JODO_ERR_* with the text in jodo_last_error()).  library: a
+    handle to call instead of libjodo_hip.so (the host build of the same source the CPU suite drives)."""
+    L = lib() if library is None else library
+    try:
+        fn = L.jodo_cdgs_train_debug_op
+    except AttributeError as e:
+        raise JodoHipError("%s lacks the CDGS kernel test entry (%s): rebuild it with python -c 'import __graft_entry__ as g; g.build()'"
+                           % (LIB_PATH if library is None else 'the given library', e))
+    fn.argtypes = [ctypes.POINTER(CdgsOpTestArgs), ctypes.c_void_p]
+    fn.restype = ctypes.c_int
+    return fn(ctypes.byref(args), stream if stream is not None else ctypes.c_void_p(0))
+
+
 def check(code, what=''):
     if code != 0:
         msg = lib().jodo_last_error()

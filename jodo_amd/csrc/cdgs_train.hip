@@ -14,6 +14,7 @@
 // barriers, no atomics: bit-deterministic, and the host emulation build of the CPU suite runs these very kernels.
 // Gradient buffers are fully written (zeroed, then accumulated in a fixed launch order).  No gradient flows through the random-walk
 // features or the thresholded adjacency (torch.no_grad in the reference); the GINE eps buffers are inputs without a gradient.
+// Tests: jodo_cdgs_train_debug_op (at the end) runs one launch sequence of the step ("launch sequences" below) on caller-owned arrays.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
@@ -487,6 +488,93 @@ __global__ void kc_out_edges(Geo g, int ch, const float* __restrict__ src, float
     dst[i_] = edge_live(g, er) ? (src[i_] + src[((b * g.N + j) * g.N + i) * ch + c]) * 0.5f : 0.f;
 }
 
+// ================================================================ launch sequences ============================================
+// The multi-launch sequences of the step on explicit pointers: forward() / backward() call them on the workspace, the test entry
+// jodo_cdgs_train_debug_op (at the end) on the caller's arrays.
+// floats of the double scratch: (sum, sum) per (tile row, group) of the edge GroupNorm; per (chunk, column) + per (group of chunks, column)
+// of the column sums
+size_t egn_part_floats(size_t M, size_t G) { return 2 * 2 * M * G; }
+size_t colsum_part_floats(size_t rows, size_t F) { const size_t nchunk = (rows + 63) / 64; return 2 * 2 * (nchunk + nchunk / COLSUM_PER + 1) * F; }
+
+// thresholded adjacency and random-walk features: adj, AD, cnt [B N^2], onehot [B N^2, K + 1], land [B N, K], deg [B N, ch]; pa, pb hold
+// the powers in turn
+void rw_prologue(hipStream_t s, const Geo& g, int K, int ch, const float* edge_x, float* adj, float* AD, float* pa, float* pb, float* cnt, float* onehot,
+                 float* land, float* deg) {
+    const long M = (long)g.B * g.N, R = M * g.N;
+    JT_LAUNCH(kc_adj, R, s, g, ch, edge_x, adj);
+    JT_LAUNCH(kc_adnorm, R, s, g, (const float*)adj, AD, pa, cnt);
+    for (int m = 0; m < K; ++m)
+        JT_LAUNCH(kc_rw_step, R, s, g, K, m, (const float*)((m & 1) ? pb : pa), (const float*)AD, (m & 1) ? pa : pb, cnt, land);
+    JT_LAUNCH(kc_onehot, R * (K + 1), s, R, K + 1, (const float*)cnt, onehot);
+    JT_LAUNCH(kc_deg, M * ch, s, g, ch, edge_x, deg);
+}
+void gine_backward(hipStream_t s, const Geo& g, int D, const float* eps, const float* hs, const float* he, const float* adj, const float* dagg, float* dhe,
+                   float* dhs) {
+    const long M = (long)g.B * g.N, R = M * g.N;
+    JT_LAUNCH(kc_gine_bwd_e, R * D, s, g, D, hs, he, adj, dagg, dhe);
+    JT_LAUNCH(kc_gine_bwd_n, M * D, s, g, D, eps, dagg, (const float*)dhe, dhs);
+}
+// norm2_edge over the padded tile: x -> xhat in place, e_out, rstd [B, D / 8]; part, gsum: double scratch
+void egn_forward(hipStream_t s, const Geo& g, int D, float* x, const float* gamma, const float* beta, double* part, double* gsum, float* rstd, float* eout) {
+    const int G = D / GW;
+    const long M = (long)g.B * g.N, R = M * g.N;
+    JT_LAUNCH(kc_egn_part, M * G, s, g, 0, D, (const float*)x, (const float*)nullptr, (const float*)nullptr, part);
+    JT_LAUNCH(kc_egn_fin, (long)g.B * G, s, g, G, (const double*)part, gsum);
+    JT_LAUNCH(kc_egn_apply, R * D, s, g, D, (const double*)gsum, x, gamma, beta, rstd, eout);
+}
+void egn_backward(hipStream_t s, const Geo& g, int D, const float* de, const float* xhat, const float* rstd, const float* gamma, double* part, double* gsum,
+                  float* dpre) {
+    const int G = D / GW;
+    const long M = (long)g.B * g.N, R = M * g.N;
+    JT_LAUNCH(kc_egn_part, M * G, s, g, 2, D, de, xhat, gamma, part);
+    JT_LAUNCH(kc_egn_fin, (long)g.B * G, s, g, G, (const double*)part, gsum);
+    JT_LAUNCH(kc_egn_bwd, R * D, s, g, D, (const double*)gsum, de, xhat, rstd, gamma, dpre);
+}
+// norm weights: dbeta = column sums of dy over the live rows, dgamma = of dy xhat.  Three levels, each in a fixed order: 64-row chunks,
+// groups of COLSUM_PER chunks, then the groups (at QM9 batch 128: 1 458 chunks -> 46 groups, instead of one thread per column walking
+// all 1 458)
+void colsum_grads(hipStream_t s, const Geo& g, int mode, long rows, int F, const float* dy, const float* xhat, double* part, float* dbeta, float* dgamma) {
+    const long nchunk = (rows + 63) / 64;
+    const long ngroup = (nchunk + COLSUM_PER - 1) / COLSUM_PER;
+    double* mid = part + 2 * nchunk * F;
+    JT_LAUNCH(kc_colsum_part, nchunk * F, s, g, mode, rows, F, dy, xhat, part);
+    JT_LAUNCH(kc_colsum_mid, ngroup * F, s, nchunk, COLSUM_PER, F, (const double*)part, mid);
+    JT_LAUNCH(kc_colsum_fin, F, s, ngroup, F, (const double*)mid, dbeta, dgamma);
+}
+// per-molecule sums of an edge tensor: cols [B N, F] = over the real pairs of a tile row, out [B, F] = over the tile rows (masked: the
+// molecule's own only)
+void tile_sums(hipStream_t s, const Geo& g, int F, const float* x, float* cols, int masked, float* out) {
+    JT_LAUNCH(kc_sum_cols, (long)g.B * g.N * F, s, g, F, x, cols);
+    JT_LAUNCH(kc_sum_nodes, (long)g.B * F, s, g, masked, F, (const float*)cols, out);
+}
+// alpha [B N^2, H] (logits, then the softmax in place), att [B N, D]
+void attn_forward(hipStream_t s, const Geo& g, int D, int H, float isc, const float* q, const float* k, const float* v, const float* g0, const float* g1,
+                  float* alpha, float* att) {
+    const long M = (long)g.B * g.N, R = M * g.N;
+    JT_LAUNCH(kc_attn_logit, R * H, s, g, D, H, isc, q, k, g0, alpha);
+    JT_LAUNCH(kc_attn_softmax, M * H, s, g, H, alpha);
+    JT_LAUNCH(kc_attn_msg, M * D, s, g, D, H, v, g1, (const float*)alpha, att);
+}
+struct AttnBwd { const float *datt, *q, *k, *v, *g0, *g1, *alpha; float *dv, *dal, *dt1, *dt0, *dq, *dk; };
+// the seven kernels in the step's order; dal: d alpha, turned into d logit in place.  `done(stage)` runs when dv (0), dt1 (1), dt0 (2),
+// dq (3), dk (4) is complete: the step consumes each of them in its GEMMs right there, so dt1 / dt0 and dq / dk may share a buffer
+template <class Fn>
+void attn_backward(hipStream_t s, const Geo& g, int D, int H, float isc, const AttnBwd& a, Fn&& done) {
+    const long M = (long)g.B * g.N, R = M * g.N;
+    JT_LAUNCH(kc_attn_bwd_v, M * D, s, g, D, H, a.datt, a.g1, a.alpha, a.dv);
+    done(0);
+    JT_LAUNCH(kc_attn_bwd_alpha, R * H, s, g, D, H, a.datt, a.v, a.g1, a.dal);
+    JT_LAUNCH(kc_attn_bwd_softmax, M * H, s, g, H, a.alpha, a.dal);
+    JT_LAUNCH(kc_attn_bwd_t1, R * D, s, g, D, H, a.datt, a.v, a.g1, a.alpha, a.dt1);
+    done(1);
+    JT_LAUNCH(kc_attn_bwd_t0, R * D, s, g, D, H, isc, (const float*)a.dal, a.q, a.k, a.g0, a.dt0);
+    done(2);
+    JT_LAUNCH(kc_attn_bwd_q, M * D, s, g, D, H, isc, (const float*)a.dal, a.k, a.g0, a.dq);
+    done(3);
+    JT_LAUNCH(kc_attn_bwd_k, M * D, s, g, D, H, isc, (const float*)a.dal, a.q, a.g0, a.dk);
+    done(4);
+}
+
 }  // namespace
 
 struct jodo_cdgs_train {
@@ -531,8 +619,7 @@ void layout(const jodo_cdgs_train& t, Arena& a, Bufs& b) {
     for (int s = 0; s < 2; ++s) b.sB[s] = a.f(B * 2 * D);
     b.dtact = a.f(B * D); b.dein = a.f(R * D); b.dnin = a.f(M * D); b.dah = a.f(M * t.Kc); b.dbh = a.f(R * t.Kc); b.dEp = a.f(R * t.ch);
     b.da3 = a.f(M * t.ach);
-    const size_t nchunk = (R + 63) / 64;                      // doubles: (sum, sum) per (tile row, group), or per (chunk, column) + per (group of chunks, column)
-    b.part = a.f(2 * 2 * std::max<size_t>(M * G, (nchunk + nchunk / COLSUM_PER + 1) * D));
+    b.part = a.f(std::max(egn_part_floats(M, G), colsum_part_floats(R, D)));          // doubles, shared by the edge GroupNorm and the column sums
     b.gsum = a.f(2 * 2 * B * G);
     b.splitk_floats = std::min<size_t>((size_t)32 << 20, ((R + 511) / 512 + 1) * (F * D + F));
     b.splitk = a.f(b.splitk_floats);
@@ -584,15 +671,7 @@ struct Ctx {
     }
     // norm weights: beta gradient = column sums of dy over the live rows, gamma gradient = of dy xhat
     void norm_grads(int mode, long rows, int F, const float* dy, const float* xhat, Lin n) const {
-        const long nchunk = (rows + 63) / 64;
-        double* part = reinterpret_cast<double*>(b.part);
-        // three levels, each in a fixed order: 64-row chunks, groups of COLSUM_PER chunks, then the groups (at QM9 batch 128: 1 458
-        // chunks -> 46 groups, instead of one thread per column walking all 1 458)
-        const long ngroup = (nchunk + COLSUM_PER - 1) / COLSUM_PER;
-        double* mid = part + 2 * nchunk * F;
-        JT_LAUNCH(kc_colsum_part, nchunk * F, s, g, mode, rows, F, dy, xhat, part);
-        JT_LAUNCH(kc_colsum_mid, ngroup * F, s, nchunk, COLSUM_PER, F, (const double*)part, mid);
-        JT_LAUNCH(kc_colsum_fin, F, s, ngroup, F, (const double*)mid, gr(n.b), gr(n.w));
+        colsum_grads(s, g, mode, rows, F, dy, xhat, reinterpret_cast<double*>(b.part), gr(n.b), gr(n.w));
     }
 };
 
@@ -632,12 +711,7 @@ void forward(const Ctx& c, const float* tt, const float* freq, const float* x, c
     c.lin_silu(b.tin, B, D, c.p(t.time0.w), 2 * D, c.p(t.time0.b), b.t1p, b.t1a, c.nod());
     c.lin_silu(b.t1a, B, 2 * D, c.p(t.time1.w), D, c.p(t.time1.b), b.temb, b.tact, c.nod());
     // thresholded adjacency and random-walk features (no gradient)
-    JT_LAUNCH(kc_adj, R, s, g, ch, edge_x, b.adj);
-    JT_LAUNCH(kc_adnorm, R, s, g, (const float*)b.adj, b.AD, b.pa, b.cnt);
-    for (int m = 0; m < K; ++m)
-        JT_LAUNCH(kc_rw_step, R, s, g, K, m, (const float*)((m & 1) ? b.pb : b.pa), (const float*)b.AD, (m & 1) ? b.pa : b.pb, b.cnt, b.land);
-    JT_LAUNCH(kc_onehot, R * (K + 1), s, R, K + 1, (const float*)b.cnt, b.onehot);
-    JT_LAUNCH(kc_deg, M * ch, s, g, ch, edge_x, b.deg);
+    rw_prologue(s, g, K, ch, edge_x, b.adj, b.AD, b.pa, b.pb, b.cnt, b.onehot, b.land, b.deg);
     // embeddings: ein = [cate | exist | spd] masked, e = lin(ein) masked; nin = [degree | cate | rw], h = lin(nin)
     c.lin(edge_x + 1, ch, R, ch - 1, c.p(t.ecate.w), ch - 1, t.w_ec, c.p(t.ecate.b), b.ein, D, 0);
     c.lin(edge_x, ch, R, 1, c.p(t.eexist.w), 1, t.w_ec, c.p(t.eexist.b), b.ein + t.w_ec, D, 0);
@@ -668,9 +742,7 @@ void forward(const Ctx& c, const float* tt, const float* freq, const float* x, c
         c.fwd(ix.value, k.hs, M, D, D, k.v);
         c.lin_tanh(he, R, D, c.p(ix.le0), D, k.t0);
         c.lin_tanh(he, R, D, c.p(ix.le1), D, k.t1);
-        JT_LAUNCH(kc_attn_logit, R * H, s, g, D, H, isc, (const float*)k.q, (const float*)k.k, (const float*)k.t0, k.alpha);
-        JT_LAUNCH(kc_attn_softmax, M * H, s, g, H, k.alpha);
-        JT_LAUNCH(kc_attn_msg, M * D, s, g, D, H, (const float*)k.v, (const float*)k.t1, (const float*)k.alpha, tmpN);
+        attn_forward(s, g, D, H, isc, k.q, k.k, k.v, k.t0, k.t1, k.alpha, tmpN);
         JT_LAUNCH(kc_gn_fwd, M * G, s, g, M, D, (const float*)b.h[l], (const float*)tmpN, c.drop(l, 2), 0, c.p(ix.na.w), c.p(ix.na.b), k.xh2, k.rs2, k.hc, 1);
         // node feed-forward (sites 3, 4), norm2_node
         c.lin_silu(k.hc, M, D, c.p(ix.ff1.w), F, c.p(ix.ff1.b), k.f1p, k.a1, c.drop(l, 3));
@@ -683,9 +755,7 @@ void forward(const Ctx& c, const float* tt, const float* freq, const float* x, c
         c.scale(0, R, D, k.xhe, c.drop(l, 6), k.xhe, 0);
         JT_LAUNCH(k_add, R * D, s, R * D, k.xhe, (const float*)b.e[l]);
         double *part = reinterpret_cast<double*>(b.part), *gsum = reinterpret_cast<double*>(b.gsum);
-        JT_LAUNCH(kc_egn_part, M * G, s, g, 0, D, (const float*)k.xhe, (const float*)nullptr, (const float*)nullptr, part);
-        JT_LAUNCH(kc_egn_fin, (long)B * G, s, g, G, (const double*)part, gsum);
-        JT_LAUNCH(kc_egn_apply, R * D, s, g, D, (const double*)gsum, k.xhe, c.p(ix.ne.w), c.p(ix.ne.b), k.rse, b.e[l + 1]);
+        egn_forward(s, g, D, k.xhe, c.p(ix.ne.w), c.p(ix.ne.b), part, gsum, k.rse, b.e[l + 1]);
         // readouts straight into the head inputs
         c.lin(b.h[l + 1], D, M, D, c.p(ix.ro_n.w), D, t.cat, c.p(ix.ro_n.b), b.ahid + l * t.cat, t.Kc, 0);
         c.lin(b.e[l + 1], D, R, D, c.p(ix.ro_e.w), D, t.cat, c.p(ix.ro_e.b), b.bhid + l * t.cat, t.Kc, 0);
@@ -739,9 +809,7 @@ void backward(const Ctx& c, const float* x, const float* edge_x, const float* d_
         c.lin_dx(b.dbh + l * t.cat, t.Kc, R, t.cat, c.p(ix.ro_e.w), D, D, de, D, 1);
         // ---- norm2_edge over the padded tile: d pre at every position -> de_prev (the residual's share of d e[l])
         c.norm_grads(2, R, D, de, k.xhe, ix.ne);
-        JT_LAUNCH(kc_egn_part, M * G, s, g, 2, D, (const float*)de, (const float*)k.xhe, c.p(ix.ne.w), part);
-        JT_LAUNCH(kc_egn_fin, (long)B * G, s, g, G, (const double*)part, gsum);
-        JT_LAUNCH(kc_egn_bwd, R * D, s, g, D, (const double*)gsum, (const float*)de, (const float*)k.xhe, (const float*)k.rse, c.p(ix.ne.w), de_prev);
+        egn_backward(s, g, D, de, k.xhe, k.rse, c.p(ix.ne.w), part, gsum, de_prev);
         // ---- edge feed-forward, every row of the tile
         c.scale(0, R, D, de_prev, c.drop(l, 6), E1, 0);                                           // d f4
         c.bwd(ix.ff4, E1, R, D, k.a3, F, b.sE_F, 0);
@@ -773,28 +841,26 @@ void backward(const Ctx& c, const float* x, const float* edge_x, const float* d_
         // ---- GINE: he recomputed; d he written into E2, d hs into dhs
         float *he = E0, *dhe = E2, *dhs = N3;
         JT_LAUNCH(kc_addt, R * D, s, g, 2, R, D, (const float*)b.e[l], (const float*)k.te, he);
-        JT_LAUNCH(kc_gine_bwd_e, R * D, s, g, D, (const float*)k.hs, (const float*)he, (const float*)b.adj, (const float*)N2, dhe);
-        JT_LAUNCH(kc_gine_bwd_n, M * D, s, g, D, c.p(ix.eps), (const float*)N2, (const float*)dhe, dhs);
+        gine_backward(s, g, D, c.p(ix.eps), k.hs, he, b.adj, N2, dhe, dhs);
         // ---- attention
+        // ---- attention: d t1 and d t0 share E1, d q and d k share N2; each is consumed by its GEMMs as soon as it is complete
         float *dv = N0, *dq = N2;
-        JT_LAUNCH(kc_attn_bwd_v, M * D, s, g, D, H, (const float*)datt, (const float*)k.t1, (const float*)k.alpha, dv);
-        c.bwd(ix.value, dv, M, D, k.hs, D, dhs, 1);
-        JT_LAUNCH(kc_attn_bwd_alpha, R * H, s, g, D, H, (const float*)datt, (const float*)k.v, (const float*)k.t1, b.sE_H);
-        JT_LAUNCH(kc_attn_bwd_softmax, M * H, s, g, H, (const float*)k.alpha, b.sE_H);
-        JT_LAUNCH(kc_attn_bwd_t1, R * D, s, g, D, H, (const float*)datt, (const float*)k.v, (const float*)k.t1, (const float*)k.alpha, E1);
-        c.lin_dw(E1, D, R, D, he, D, D, c.gr(ix.le1), D);
-        c.lin_dx(E1, D, R, D, c.p(ix.le1), D, D, dhe, D, 1);
-        JT_LAUNCH(kc_attn_bwd_t0, R * D, s, g, D, H, isc, (const float*)b.sE_H, (const float*)k.q, (const float*)k.k, (const float*)k.t0, E1);
-        c.lin_dw(E1, D, R, D, he, D, D, c.gr(ix.le0), D);
-        c.lin_dx(E1, D, R, D, c.p(ix.le0), D, D, dhe, D, 1);
-        JT_LAUNCH(kc_attn_bwd_q, M * D, s, g, D, H, isc, (const float*)b.sE_H, (const float*)k.k, (const float*)k.t0, dq);
-        c.bwd(ix.query, dq, M, D, k.hs, D, dhs, 1);
-        JT_LAUNCH(kc_attn_bwd_k, M * D, s, g, D, H, isc, (const float*)b.sE_H, (const float*)k.q, (const float*)k.t0, dq);
-        c.bwd(ix.key, dq, M, D, k.hs, D, dhs, 1);
+        const AttnBwd ab{datt, k.q, k.k, k.v, k.t0, k.t1, k.alpha, dv, b.sE_H, E1, E1, dq, dq};
+        attn_backward(s, g, D, H, isc, ab, [&](int stage) {
+            const Lin le{stage == 1 ? ix.le1 : ix.le0, -1};
+            switch (stage) {
+                case 0: c.bwd(ix.value, dv, M, D, k.hs, D, dhs, 1); break;
+                case 1: case 2:
+                    c.lin_dw(E1, D, R, D, he, D, D, c.gr(le.w), D);
+                    c.lin_dx(E1, D, R, D, c.p(le.w), D, D, dhe, D, 1);
+                    break;
+                case 3: c.bwd(ix.query, dq, M, D, k.hs, D, dhs, 1); break;
+                default: c.bwd(ix.key, dq, M, D, k.hs, D, dhs, 1); break;
+            }
+        });
         // ---- he = (e + t_edge) * edge mask, hs = (h + t_node) * node mask: per-molecule sums for the time shifts
         c.scale(2, R, D, dhe, c.nod(), de_prev, 1);
-        JT_LAUNCH(kc_sum_cols, M * D, s, g, D, (const float*)dhe, N0);
-        JT_LAUNCH(kc_sum_nodes, (long)B * D, s, g, 0, D, (const float*)N0, b.sB[0]);
+        tile_sums(s, g, D, dhe, N0, 0, b.sB[0]);
         c.bwd(ix.t_edge, b.sB[0], B, D, b.tact, D, b.dtact, 1);
         c.scale(1, M, D, dhs, c.nod(), dh_prev, 1);
         JT_LAUNCH(kc_sum_nodes, (long)B * D, s, g, 1, D, (const float*)dhs, b.sB[0]);
@@ -978,6 +1044,155 @@ int jodo_cdgs_train_backward(jodo_cdgs_train* t, const void* desc_dev, const flo
     Ctx c{*t, g, params_dev, grads_dev, bufs, static_cast<hipStream_t>(stream), dropout_p, seed, t->split};
     backward(c, x, edge_x, d_out_x, d_out_e);
     return jodo_check_launch("jodo_cdgs_train_backward");
+}
+
+// tests: one launch sequence of the step on caller-owned arrays (include/jodo_hip.h).  No kernel and no launch sequence lives here;
+// the entry is the safety boundary of tests/test_cdgs_kernels_gpu.py: everything is checked on the host before anything is launched.
+int jodo_cdgs_train_debug_op(const jodo_cdgs_op_test_args* args, void* stream) {
+    static const char* const OP[JODO_CT_N_OPS] = {"RW", "ADDT", "SCALE", "RELU", "RELU_BWD", "PAIR", "PAIR_BWD", "OUT_NODES", "OUT_EDGES", "SUMS", "GINE",
+                                                  "GINE_BWD", "GN_FWD", "GN_BWD", "EGN_FWD", "EGN_BWD", "NORM_GRADS", "ATTN_FWD", "ATTN_BWD"};
+    static const char* const SLOT[JODO_CT_N_SLOTS] = {"edge_x", "adj", "ad", "pa", "pb", "cnt", "onehot", "land", "deg", "x", "tb", "y", "z", "eps", "hs", "he",
+                                                      "agg", "dagg", "dhe", "dhs", "h", "a", "gamma", "beta", "xhat", "rstd", "dy", "dx", "part", "gsum",
+                                                      "dbeta", "dgamma", "q", "k", "v", "g0", "g1", "alpha", "att", "datt", "dv", "dal", "dt1", "dt0", "dq", "dk"};
+    if (!args) return jodo_set_error(JODO_ERR_ARG, "jodo_cdgs_train_debug_op: args is a null pointer");
+    const jodo_cdgs_op_test_args& a = *args;
+    if (a.op < 0 || a.op >= JODO_CT_N_OPS) return jodo_set_error(JODO_ERR_ARG, "jodo_cdgs_train_debug_op: unknown op %d", a.op);
+    const char* op = OP[a.op];
+    if (a.B < 1 || a.N < 1 || !a.n_nodes) return jodo_set_error(JODO_ERR_ARG, "jodo_cdgs_train_debug_op(%s): B %d, N %d or a null n_nodes", op, a.B, a.N);
+    if ((long)a.B * a.N * a.N > (1L << 30)) return jodo_set_error(JODO_ERR_UNSUPPORTED, "jodo_cdgs_train_debug_op(%s): %ld tile rows", op, (long)a.B * a.N * a.N);
+    for (int b = 0; b < a.B; ++b)
+        if (a.n_nodes[b] < 1 || a.n_nodes[b] > a.N)
+            return jodo_set_error(JODO_ERR_ARG, "jodo_cdgs_train_debug_op(%s): n_nodes[%d] = %d outside 1..%d", op, b, a.n_nodes[b], a.N);
+    if (a.D < GW || a.D % GW || a.H < 1 || a.D % a.H || a.F < 1 || a.K < 1 || a.ch < 2)
+        return jodo_set_error(JODO_ERR_ARG, "jodo_cdgs_train_debug_op(%s): D %d (a multiple of %d) / H %d (dividing D) / F %d / K %d / ch %d", op, a.D, GW, a.H, a.F,
+                              a.K, a.ch);
+    if (a.D > 4096 || a.F > 4096 || a.K > 256 || a.ch > 256)
+        return jodo_set_error(JODO_ERR_UNSUPPORTED, "jodo_cdgs_train_debug_op(%s): D %d / F %d above 4096 or K %d / ch %d above 256", op, a.D, a.F, a.K, a.ch);
+    if (!(a.drop_p >= 0.f && a.drop_p < 1.f) || a.drop_site < 0) return jodo_set_error(JODO_ERR_ARG, "jodo_cdgs_train_debug_op(%s): dropout %g at site %d", op, a.drop_p, a.drop_site);
+    if ((a.acc != 0 && a.acc != 1) || (a.amask != 0 && a.amask != 1)) return jodo_set_error(JODO_ERR_ARG, "jodo_cdgs_train_debug_op(%s): acc %d / amask %d", op, a.acc, a.amask);
+    const int o = a.op;
+    const int mode_lo = (o == JODO_CT_OP_ADDT || o == JODO_CT_OP_NORM_GRADS) ? 1 : 0;
+    const int mode_hi = (o == JODO_CT_OP_ADDT || o == JODO_CT_OP_NORM_GRADS || o == JODO_CT_OP_SCALE) ? 2 : o == JODO_CT_OP_SUMS ? 1 : 0;
+    if (a.mode < mode_lo || a.mode > mode_hi) return jodo_set_error(JODO_ERR_ARG, "jodo_cdgs_train_debug_op(%s): mode %d outside %d..%d", op, a.mode, mode_lo, mode_hi);
+    const size_t B = (size_t)a.B, M = B * a.N, R = M * a.N, D = (size_t)a.D, G = D / GW, H = (size_t)a.H, F = (size_t)a.F, K = (size_t)a.K, ch = (size_t)a.ch;
+    // rows of the flat ops: the whole tensor (M node rows in mode 1, R tile rows otherwise), or a leading part of it where the op allows
+    const size_t full = a.mode == 1 && o != JODO_CT_OP_SUMS ? M : R;
+    const bool partial = o == JODO_CT_OP_SCALE || o == JODO_CT_OP_RELU || o == JODO_CT_OP_RELU_BWD || o == JODO_CT_OP_NORM_GRADS;
+    if (a.rows < 0 || (size_t)a.rows > full || (a.rows != 0 && !partial))
+        return jodo_set_error(JODO_ERR_ARG, "jodo_cdgs_train_debug_op(%s): rows %ld (0, or 1..%zu where the op takes a leading part)", op, (long)a.rows, full);
+    const size_t rows = a.rows ? (size_t)a.rows : full;
+    // slot -> element count the op touches; kind 1 = array (exactly that many), 2 = scratch (at least that many)
+    size_t need[JODO_CT_N_SLOTS];
+    int kind[JODO_CT_N_SLOTS];
+    for (int s = 0; s < JODO_CT_N_SLOTS; ++s) { need[s] = 0; kind[s] = 0; }
+    auto use = [&](int s, size_t n) { need[s] = n; kind[s] = 1; };
+    auto scratch = [&](int s, size_t n) { need[s] = n; kind[s] = 2; };
+    switch (o) {
+        case JODO_CT_OP_RW:
+            use(JODO_CT_EDGE_X, R * ch); use(JODO_CT_ADJ, R); use(JODO_CT_AD, R); use(JODO_CT_CNT, R); use(JODO_CT_ONEHOT, R * (K + 1)); use(JODO_CT_LAND, M * K);
+            use(JODO_CT_DEG, M * ch); scratch(JODO_CT_PA, R); scratch(JODO_CT_PB, R);
+            break;
+        case JODO_CT_OP_ADDT: use(JODO_CT_X, rows * F); use(JODO_CT_TB, B * F); use(JODO_CT_Y, rows * F); break;
+        case JODO_CT_OP_SCALE: case JODO_CT_OP_RELU: case JODO_CT_OP_RELU_BWD: use(JODO_CT_X, rows * F); use(JODO_CT_Y, rows * F); break;
+        case JODO_CT_OP_PAIR: use(JODO_CT_X, M * D); use(JODO_CT_Y, R * D); break;
+        case JODO_CT_OP_PAIR_BWD: use(JODO_CT_X, R * D); use(JODO_CT_Y, M * D); break;
+        case JODO_CT_OP_OUT_NODES: use(JODO_CT_X, M * F); use(JODO_CT_Y, M * F); break;
+        case JODO_CT_OP_OUT_EDGES: use(JODO_CT_X, R * ch); use(JODO_CT_Y, R * ch); break;
+        case JODO_CT_OP_SUMS: use(JODO_CT_X, R * F); use(JODO_CT_Y, M * F); use(JODO_CT_Z, B * F); break;
+        case JODO_CT_OP_GINE: case JODO_CT_OP_GINE_BWD:
+            use(JODO_CT_EPS, 1); use(JODO_CT_HS, M * D); use(JODO_CT_HE, R * D); use(JODO_CT_ADJ, R);
+            if (o == JODO_CT_OP_GINE) use(JODO_CT_AGG, M * D);
+            else { use(JODO_CT_DAGG, M * D); use(JODO_CT_DHE, R * D); use(JODO_CT_DHS, M * D); }
+            break;
+        case JODO_CT_OP_GN_FWD:
+            use(JODO_CT_H, M * D); use(JODO_CT_A, M * D); use(JODO_CT_GAMMA, D); use(JODO_CT_BETA, D); use(JODO_CT_XHAT, M * D); use(JODO_CT_RSTD, M * G);
+            use(JODO_CT_Y, M * D);
+            break;
+        case JODO_CT_OP_GN_BWD: use(JODO_CT_DY, M * D); use(JODO_CT_XHAT, M * D); use(JODO_CT_RSTD, M * G); use(JODO_CT_GAMMA, D); use(JODO_CT_DX, M * D); break;
+        case JODO_CT_OP_EGN_FWD:
+            use(JODO_CT_XHAT, R * D); use(JODO_CT_GAMMA, D); use(JODO_CT_BETA, D); use(JODO_CT_RSTD, B * G); use(JODO_CT_Y, R * D);
+            scratch(JODO_CT_PART, egn_part_floats(M, G)); scratch(JODO_CT_GSUM, 2 * 2 * B * G);
+            break;
+        case JODO_CT_OP_EGN_BWD:
+            use(JODO_CT_DY, R * D); use(JODO_CT_XHAT, R * D); use(JODO_CT_RSTD, B * G); use(JODO_CT_GAMMA, D); use(JODO_CT_DX, R * D);
+            scratch(JODO_CT_PART, egn_part_floats(M, G)); scratch(JODO_CT_GSUM, 2 * 2 * B * G);
+            break;
+        case JODO_CT_OP_NORM_GRADS:
+            use(JODO_CT_DY, rows * F); use(JODO_CT_XHAT, rows * F); use(JODO_CT_DBETA, F); use(JODO_CT_DGAMMA, F); scratch(JODO_CT_PART, colsum_part_floats(rows, F));
+            break;
+        case JODO_CT_OP_ATTN_FWD: case JODO_CT_OP_ATTN_BWD:
+            use(JODO_CT_Q, M * D); use(JODO_CT_K, M * D); use(JODO_CT_V, M * D); use(JODO_CT_G0, R * D); use(JODO_CT_G1, R * D); use(JODO_CT_ALPHA, R * H);
+            if (o == JODO_CT_OP_ATTN_FWD) use(JODO_CT_ATT, M * D);
+            else {
+                use(JODO_CT_DATT, M * D); use(JODO_CT_DV, M * D); use(JODO_CT_DAL, R * H); use(JODO_CT_DT1, R * D); use(JODO_CT_DT0, R * D); use(JODO_CT_DQ, M * D);
+                use(JODO_CT_DK, M * D);
+            }
+            break;
+    }
+    for (int s = 0; s < JODO_CT_N_SLOTS; ++s) {
+        if (!kind[s]) continue;
+        if (kind[s] == 2 ? a.n[s] < need[s] : a.n[s] != need[s])
+            return jodo_set_error(JODO_ERR_ARG, "jodo_cdgs_train_debug_op(%s): array %s has %zu elements, the op touches %zu", op, SLOT[s], a.n[s], need[s]);
+        if (!a.a[s]) return jodo_set_error(JODO_ERR_ARG, "jodo_cdgs_train_debug_op(%s): array %s is a null pointer", op, SLOT[s]);
+        if (((uintptr_t)a.a[s] & 15) != 0) return jodo_set_error(JODO_ERR_ARG, "jodo_cdgs_train_debug_op(%s): array %s is not 16-byte aligned", op, SLOT[s]);
+    }
+    if (!a.nn_dev || a.nn_dev_count < B || ((uintptr_t)a.nn_dev & 15) != 0)
+        return jodo_set_error(JODO_ERR_ARG, "jodo_cdgs_train_debug_op(%s): nn_dev is null, misaligned or holds %zu counts of %zu", op, a.nn_dev_count, B);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (hipMemcpyAsync(a.nn_dev, a.n_nodes, B * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+        return jodo_set_error(JODO_ERR_LAUNCH, "jodo_cdgs_train_debug_op(%s): upload of the counts failed", op);      // (the caller may free n_nodes: wait)
+    const Geo g{a.B, a.N, a.nn_dev};
+    Drop d; d.p = a.drop_p; d.seed = a.drop_seed; d.site = (unsigned)a.drop_site;
+    auto A = [&](int slot) { return a.a[slot]; };
+    auto C = [&](int slot) { return (const float*)a.a[slot]; };
+    const long Ml = (long)M, Rl = (long)R, rl = (long)rows;
+    switch (o) {
+        case JODO_CT_OP_RW:
+            rw_prologue(s, g, a.K, a.ch, C(JODO_CT_EDGE_X), A(JODO_CT_ADJ), A(JODO_CT_AD), A(JODO_CT_PA), A(JODO_CT_PB), A(JODO_CT_CNT), A(JODO_CT_ONEHOT),
+                        A(JODO_CT_LAND), A(JODO_CT_DEG));
+            break;
+        case JODO_CT_OP_ADDT: JT_LAUNCH(kc_addt, rl * a.F, s, g, a.mode, rl, a.F, C(JODO_CT_X), C(JODO_CT_TB), A(JODO_CT_Y)); break;
+        case JODO_CT_OP_SCALE: JT_LAUNCH(kc_scale, rl * a.F, s, g, a.mode, rl, a.F, C(JODO_CT_X), d, A(JODO_CT_Y), a.acc); break;
+        case JODO_CT_OP_RELU: JT_LAUNCH(kc_relu, rl * a.F, s, rl * a.F, C(JODO_CT_X), A(JODO_CT_Y)); break;
+        case JODO_CT_OP_RELU_BWD: JT_LAUNCH(kc_relu_bwd, rl * a.F, s, rl * a.F, C(JODO_CT_X), A(JODO_CT_Y)); break;
+        case JODO_CT_OP_PAIR: JT_LAUNCH(kc_pair, Rl * a.D, s, g, a.D, C(JODO_CT_X), A(JODO_CT_Y)); break;
+        case JODO_CT_OP_PAIR_BWD: JT_LAUNCH(kc_pair_bwd, Ml * a.D, s, g, a.D, C(JODO_CT_X), A(JODO_CT_Y)); break;
+        case JODO_CT_OP_OUT_NODES: JT_LAUNCH(kc_out_nodes, Ml * a.F, s, g, a.F, C(JODO_CT_X), A(JODO_CT_Y)); break;
+        case JODO_CT_OP_OUT_EDGES: JT_LAUNCH(kc_out_edges, Rl * a.ch, s, g, a.ch, C(JODO_CT_X), A(JODO_CT_Y)); break;
+        case JODO_CT_OP_SUMS: tile_sums(s, g, a.F, C(JODO_CT_X), A(JODO_CT_Y), a.mode, A(JODO_CT_Z)); break;
+        case JODO_CT_OP_GINE: JT_LAUNCH(kc_gine, Ml * a.D, s, g, a.D, C(JODO_CT_EPS), C(JODO_CT_HS), C(JODO_CT_HE), C(JODO_CT_ADJ), A(JODO_CT_AGG)); break;
+        case JODO_CT_OP_GINE_BWD:
+            gine_backward(s, g, a.D, C(JODO_CT_EPS), C(JODO_CT_HS), C(JODO_CT_HE), C(JODO_CT_ADJ), C(JODO_CT_DAGG), A(JODO_CT_DHE), A(JODO_CT_DHS));
+            break;
+        case JODO_CT_OP_GN_FWD:
+            JT_LAUNCH(kc_gn_fwd, Ml * (long)G, s, g, Ml, a.D, C(JODO_CT_H), C(JODO_CT_A), d, a.amask, C(JODO_CT_GAMMA), C(JODO_CT_BETA), A(JODO_CT_XHAT),
+                      A(JODO_CT_RSTD), A(JODO_CT_Y), a.acc);
+            break;
+        case JODO_CT_OP_GN_BWD:
+            JT_LAUNCH(kc_gn_bwd, Ml * (long)G, s, g, Ml, a.D, C(JODO_CT_DY), C(JODO_CT_XHAT), C(JODO_CT_RSTD), C(JODO_CT_GAMMA), A(JODO_CT_DX), a.acc);
+            break;
+        case JODO_CT_OP_EGN_FWD:
+            egn_forward(s, g, a.D, A(JODO_CT_XHAT), C(JODO_CT_GAMMA), C(JODO_CT_BETA), reinterpret_cast<double*>(A(JODO_CT_PART)),
+                        reinterpret_cast<double*>(A(JODO_CT_GSUM)), A(JODO_CT_RSTD), A(JODO_CT_Y));
+            break;
+        case JODO_CT_OP_EGN_BWD:
+            egn_backward(s, g, a.D, C(JODO_CT_DY), C(JODO_CT_XHAT), C(JODO_CT_RSTD), C(JODO_CT_GAMMA), reinterpret_cast<double*>(A(JODO_CT_PART)),
+                         reinterpret_cast<double*>(A(JODO_CT_GSUM)), A(JODO_CT_DX));
+            break;
+        case JODO_CT_OP_NORM_GRADS:
+            colsum_grads(s, g, a.mode, rl, a.F, C(JODO_CT_DY), C(JODO_CT_XHAT), reinterpret_cast<double*>(A(JODO_CT_PART)), A(JODO_CT_DBETA), A(JODO_CT_DGAMMA));
+            break;
+        case JODO_CT_OP_ATTN_FWD:
+            attn_forward(s, g, a.D, a.H, a.isc, C(JODO_CT_Q), C(JODO_CT_K), C(JODO_CT_V), C(JODO_CT_G0), C(JODO_CT_G1), A(JODO_CT_ALPHA), A(JODO_CT_ATT));
+            break;
+        case JODO_CT_OP_ATTN_BWD: {
+            const AttnBwd ab{C(JODO_CT_DATT), C(JODO_CT_Q), C(JODO_CT_K), C(JODO_CT_V), C(JODO_CT_G0), C(JODO_CT_G1), C(JODO_CT_ALPHA), A(JODO_CT_DV),
+                             A(JODO_CT_DAL), A(JODO_CT_DT1), A(JODO_CT_DT0), A(JODO_CT_DQ), A(JODO_CT_DK)};
+            attn_backward(s, g, a.D, a.H, a.isc, ab, [](int) {});
+            break;
+        }
+    }
+    return jodo_check_launch("jodo_cdgs_train_debug_op");
 }
 
 }  // extern "C"

@@ -9,7 +9,16 @@ neither symmetric nor masked):
   w12/w9  QM9  [9, 4, 7, 2] at N = 12 / 9     no molecule reaches the width at N = 12: the padded rows carry gradient
   geom    GEOM [3, 40, 1], N = 44             6 blocks, 254 parameters, readout width 85, n > 32
   b65     QM9  65 molecules, n = 1, 2, 3 ..   time-MLP rows across the 64-row strip of the GEMM
-  single  QM9  one-atom molecules only        the yardstick's gradients of modules 2 - 5 are exactly zero, the engine's must be too"""
+  single  QM9  one-atom molecules only        the yardstick's gradients of modules 2 - 5 are exactly zero, the engine's must be too
+  wide    GEOM with n_layers = 1, [100, 65, 1], N = 100 (device only)   the first run of the engine above N = 44 and above 64: 30 000
+                                              tile rows per tensor, which float64 autograd on a CPU affords at one block
+  full    GEOM with n_layers = 1, [181, 2], N = 181 (device only, forward and kept activations only)   the config's own max_node
+The two one-block cases draw a SPARSE adjacency (a path through every molecule plus one chord per four atoms, as molecules have; the
+attention still walks every real pair): with half of all pairs adjacent, as the other cases draw them, N = 100 evaluates 1.8 million
+GINE ReLU arguments and no input seed keeps them all RELU_MARGIN from zero.
+
+kept_yardsticks / check_kept: the tensors the training forward keeps in its workspace (jodo_cdgs_train_debug_locate selectors 0 - 3: h and
+e after every block, alpha and the xhat of norm2_edge of every block) against the oracle's per-block tensors under helpers.close64."""
 import functools
 
 import torch
@@ -22,7 +31,10 @@ from jodo_amd.sampling import build_masks
 from train2d_common import GRAD_REL, GRAD_REF_REL, K32, assert_all_nonzero, compare_grads  # noqa: F401  (re-exported)
 
 CFG = {'qm9': 'vpsde_qm9_2d_cdgs', 'geom': 'vpsde_geom_2d_cdgs'}
+ONE_BLOCK = {'geom1': 'geom'}              # `which` -> the config it is, with model.n_layers = 1
 CASES = {
+    'wide': ('geom1', [100, 65, 1], 100),
+    'full': ('geom1', [181, 2], 181),
     'mixed': ('qm9', [1, 2, 5, 17, 29, 9], 29),
     'w12': ('qm9', [9, 4, 7, 2], 12),
     'w9': ('qm9', [9, 4, 7, 2], 9),
@@ -41,16 +53,20 @@ MODEL_SEED = 7
 RELU_MARGIN = 5e-6
 
 
+def config_for(which):
+    return make_config(CFG[ONE_BLOCK[which]], n_layers=1) if which in ONE_BLOCK else make_config(CFG[which])
+
+
 @functools.lru_cache(maxsize=None)
 def model_for(which, seed=MODEL_SEED):
     """(cfg, CPU model in eval mode, CPU float32 state_dict): shared, never modified (tests that change weights build their own)."""
-    cfg = make_config(CFG[which])
+    cfg = config_for(which)
     model = deterministic_init_(get_model_class('CDGS')(cfg), seed=seed).eval()
     return cfg, model, {k: v.detach().clone() for k, v in model.state_dict().items()}
 
 
 def fresh_model(which, seed=MODEL_SEED, device='cpu'):
-    cfg = make_config(CFG[which])
+    cfg = config_for(which)
     return cfg, deterministic_init_(get_model_class('CDGS')(cfg), seed=seed).to(device).eval()
 
 
@@ -69,13 +85,17 @@ def random_case(name, seed=5):
         c['N'] = N
         return c
     which, n_nodes, N = CASES[name]
-    cfg = make_config(CFG[which])
+    cfg = config_for(which)
     g = torch.Generator().manual_seed(seed)
     B = len(n_nodes)
     nm, em = build_masks(list(n_nodes), N, 'cpu')
     x = torch.randn(B, N, cfg.data.atom_types, generator=g) * nm
     ex = torch.randn(B, N, N, cfg.model.edge_ch, generator=g)
     ex = (ex + ex.transpose(1, 2)) * em.reshape(B, N, N, 1)
+    if which in ONE_BLOCK:                   # sparse adjacency (first channel >= 0): a path and one chord per four atoms
+        r, c_ = torch.arange(N)[:, None], torch.arange(N)[None, :]
+        bond = ((r - c_).abs() == 1) | (((r - c_).abs() == 7) & (torch.minimum(r, c_) % 4 == 0))
+        ex[..., 0] = torch.where(bond[None], ex[..., 0].abs() + 0.1, -ex[..., 0].abs() - 0.1) * em.reshape(B, N, N)
     t = torch.rand(B, generator=g) * 0.999 + 1e-3
     d_x, d_e = torch.randn(B, N, cfg.data.atom_types, generator=g), torch.randn(B, N, N, cfg.model.edge_ch, generator=g)
     return dict(which=which, cfg=cfg, hp=OC.hparams(cfg), n_nodes=list(n_nodes), N=N, B=B, nm=nm, em=em, t=t, x=x, ex=ex, d_x=d_x, d_e=d_e)
@@ -137,3 +157,43 @@ def param_names(model):
     """state_dict keys, and which of them are parameters (the GINE eps buffers are not)."""
     keys = list(model.state_dict().keys())
     return keys, [k for k in keys if not k.endswith('local_model.eps')]
+
+
+# ---- the kept activations ---------------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def kept_yardsticks(name, p=0.0, drop_seed=0):
+    """(case, {dtype: (atom, bond, states, taps)}) of random_case(name) through the no-grad oracle (masked form when p > 0), in float64
+    and float32: computed once, shared, left unchanged."""
+    c = random_case(name)
+    _, _, sd = model_for(c['which'])
+    hp = c['hp']
+    out = {}
+    for dtype in (torch.float64, torch.float32):
+        masks = OCT.drop_masks(drop_seed, p, c['B'], c['N'], hp.n_layers, hp.nf, dtype=dtype) if p > 0 else None
+        taps = []
+        with torch.no_grad():
+            px, pe, states = OCT.forward_drop({k: v.to(dtype) for k, v in sd.items()}, hp, c['t'], c['x'], c['nm'], c['em'], c['ex'], drop=masks,
+                                              return_blocks=True, taps=taps)
+        out[dtype] = (px, pe, states, taps)
+    return c, out
+
+
+def check_kept(fetch, c, yard, what=''):
+    """fetch(selector, layer) -> flat float32 tensor (TrainEngineCDGS.debug_fetch after a training-mode forward).  Every block's selectors
+    0 - 3 under helpers.close64; alpha off the real pairs, e off the real pairs and h on the padded rows (after a block) exactly 0."""
+    from helpers import close64
+    (_, _, st64, tp64), (_, _, st32, tp32) = yard[torch.float64], yard[torch.float32]
+    B, N, L = c['B'], c['N'], c['hp'].n_layers
+    dead_n, dead_e = (c['nm'].reshape(B, N) == 0), (c['em'].reshape(B, N, N) == 0)
+    for l in range(L + 1):
+        h, e = fetch(0, l).cpu().reshape(st64[l][0].shape), fetch(1, l).cpu().reshape(st64[l][1].shape)
+        close64(h, st32[l][0], st64[l][0], '%s kept h %d' % (what, l))
+        close64(e, st32[l][1], st64[l][1], '%s kept e %d' % (what, l))
+        assert float(e[dead_e].abs().max() if bool(dead_e.any()) else 0.0) == 0.0, '%s: e %d is not exactly zero off the real pairs' % (what, l)
+        if l > 0 and bool(dead_n.any()):
+            assert float(h[dead_n].abs().max()) == 0.0, '%s: h %d is not exactly zero on the padded rows' % (what, l)
+        if l < L:
+            al, xh = fetch(2, l).cpu().reshape(tp64[l]['alpha'].shape), fetch(3, l).cpu().reshape(tp64[l]['xhat'].shape)
+            close64(al, tp32[l]['alpha'], tp64[l]['alpha'], '%s kept alpha %d' % (what, l))
+            close64(xh, tp32[l]['xhat'], tp64[l]['xhat'], '%s kept xhat %d' % (what, l))
+            assert float(al[dead_e].abs().max() if bool(dead_e.any()) else 0.0) == 0.0, '%s: alpha %d is not exactly zero off the real pairs' % (what, l)

@@ -61,7 +61,7 @@ def ones_masks(B, N, n_layers, C, dtype=torch.float64):
     return {(l, s): torch.ones(shapes[s], dtype=dtype) for l in range(n_layers) for s in SITES}
 
 
-def _block(sd, pre, hp, h, e, adj, nm, em, temb_act, dm, margins=None):
+def _block(sd, pre, hp, h, e, adj, nm, em, temb_act, dm, margins=None, taps=None):
     lin = OC._lin
     B, N, C = h.shape
     H, Ch = hp.n_heads, C // hp.n_heads
@@ -100,14 +100,17 @@ def _block(sd, pre, hp, h, e, adj, nm, em, temb_act, dm, margins=None):
     ff = lambda a, b, x, sa, sb: dm(sb, lin(sd, pre + b, dm(sa, F.silu(lin(sd, pre + a, x)))))
     h = gn('norm2_node', h + ff('ff_linear1', 'ff_linear2', h, 3, 4)) * nm
     e = e_in + ff('ff_linear3', 'ff_linear4', pair, 5, 6)
+    if taps is not None:                        # what the training path keeps besides h and e: alpha, and the xhat of norm2_edge
+        taps.append(dict(alpha=alpha.detach(), xhat=F.group_norm(e.permute(0, 3, 1, 2), min(C // 4, 32), None, None, 1e-6).permute(0, 2, 3, 1).detach()))
     e = F.group_norm(e.permute(0, 3, 1, 2), min(C // 4, 32), sd[pre + 'norm2_edge.weight'], sd[pre + 'norm2_edge.bias'], 1e-6)
     e = e.permute(0, 2, 3, 1) * em[..., None]
     return h, e
 
 
-def forward_drop(sd, hp, t, x, node_mask, edge_mask, edge_x, drop=None, return_blocks=False, margins=None):
+def forward_drop(sd, hp, t, x, node_mask, edge_mask, edge_x, drop=None, return_blocks=False, margins=None, taps=None):
     """(atom_score, bond_score[, states]) as oracle_cdgs.forward; drop: None (no dropout) or {(layer, site): multipliers}; margins: a list
-    that receives, per block, the smallest |argument| of the two ReLUs (GINE message, GINE nn) over the positions that carry gradient."""
+    that receives, per block, the smallest |argument| of the two ReLUs (GINE message, GINE nn) over the positions that carry gradient;
+    taps: a list that receives, per block, dict(alpha [B, N, N, H] (source, target), xhat [B, N, N, C] of norm2_edge)."""
     lin = OC._lin
     any_w = sd['all_modules.0.weight']
     dt, dev = any_w.dtype, any_w.device
@@ -135,7 +138,7 @@ def forward_drop(sd, hp, t, x, node_mask, edge_mask, edge_x, drop=None, return_b
     a_hids, b_hids = [], []
     for l in range(L):
         dm = (lambda s, v: v) if drop is None else (lambda s, v, l=l: v * c(drop[(l, s)]))
-        h, e = _block(sd, M(10 + 3 * l) + '.', hp, h, e, adj, nm, em, temb_act, dm, margins)
+        h, e = _block(sd, M(10 + 3 * l) + '.', hp, h, e, adj, nm, em, temb_act, dm, margins, taps)
         states.append((h, e))
         a_hids.append(lin(sd, M(11 + 3 * l), h))
         b_hids.append(lin(sd, M(12 + 3 * l), e))

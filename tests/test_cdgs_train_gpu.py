@@ -69,6 +69,32 @@ def test_forward_and_all_gradients_match_the_oracle(name):
     C.compare_grads(grads, want, want32=want32, what=name)
 
 
+def test_wide_case_forward_and_all_gradients_match_the_oracle():
+    """GEOM with one block at [100, 65, 1], N = 100: the first run of the engine above N = 44 and above 64 (30 000 tile rows)."""
+    c, (px, pe, want), (px32, pe32, want32) = C.yardsticks('wide')
+    assert c['relu_margin'] > C.RELU_MARGIN
+    (out_x, out_e), grads = module_grads(shared_model(c['which']), c)
+    close64(out_x, px32, px, 'wide train x')
+    close64(out_e, pe32, pe, 'wide train e')
+    B, N = c['B'], c['N']
+    assert float((out_x.cpu() * (1 - c['nm'])).abs().max()) == 0.0 and float((out_e.cpu() * (1 - c['em'].reshape(B, N, N, 1))).abs().max()) == 0.0
+    assert torch.equal(out_e, out_e.transpose(1, 2))
+    C.assert_all_nonzero(want)
+    assert len(grads) == len(want) == 74
+    C.compare_grads(grads, want, want32=want32, what='wide')
+
+
+@pytest.mark.parametrize('name,p', [('mixed', 0.0), ('mixed', 0.1), ('geom', 0.0), ('geom', 0.1), ('full', 0.0)])
+def test_kept_activations_match_the_oracle(name, p):
+    """After a training-mode forward: h and e after every block, alpha and the xhat of norm2_edge of every block (debug_fetch selectors
+    0 - 3) against the oracle's per-block tensors; `full` is the GEOM config's own width, [181, 2] at N = 181, one block, forward only."""
+    c, yard = C.kept_yardsticks(name, p, 12345)
+    eng, _, out, _ = engine_run(shared_model(c['which']), c, p, 12345, backward=False)
+    close64(out[0], yard[torch.float32][0], yard[torch.float64][0], '%s dropout %g x' % (name, p))
+    close64(out[1], yard[torch.float32][1], yard[torch.float64][1], '%s dropout %g e' % (name, p))
+    C.check_kept(eng.debug_fetch, c, yard, '%s dropout %g' % (name, p))
+
+
 def test_one_atom_molecules_have_exactly_zero_edge_embedding_gradients():
     c, (px, pe, want), (px32, pe32, want32) = C.yardsticks('single')
     (out_x, out_e), grads = module_grads(shared_model('qm9'), c)

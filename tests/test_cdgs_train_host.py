@@ -198,6 +198,17 @@ def test_all_parameter_gradients_match_autograd_through_the_oracle(emul, name):
     C.compare_grads(grads, want, want32=want32, what=name)
 
 
+@pytest.mark.parametrize('name,p', [('mixed', 0.0), ('mixed', 0.1), ('geom', 0.0), ('geom', 0.1)])
+def test_kept_activations_match_the_oracle(emul, name, p):
+    """After a training-mode forward: h and e after every block, alpha and the xhat of norm2_edge of every block (debug_fetch selectors
+    0 - 3) against the oracle's per-block tensors."""
+    c, yard = C.kept_yardsticks(name, p, 12345)
+    eng, out, _ = run(emul, c, p, 12345, backward=False)
+    close64(out[0], yard[torch.float32][0], yard[torch.float64][0], '%s dropout %g x' % (name, p))
+    close64(out[1], yard[torch.float32][1], yard[torch.float64][1], '%s dropout %g e' % (name, p))
+    C.check_kept(eng.debug_fetch, c, yard, '%s dropout %g' % (name, p))
+
+
 def test_unconditioned_inputs_are_reported(emul):
     """REPORTED, not asserted on the gradients: `mixed` at input seed 5, which the conditioning rule of cdgs_train_common rejects (a ReLU
     argument of the float64 yardstick 4.5e-7 from zero in block 1).  Shows what one ReLU taking the other branch in a float32
